@@ -1,11 +1,15 @@
 """KM-BART vcg_base training throughput on MI355X (BASELINE.json metric: training tokens/sec, whole node).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_PER_GPU]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_PER_GPU] [--dump-outputs DIR]
 
 A step = forward (dropout 0.1 as config/vcg_base.json) + backward + gradient all-reduce (N > 1) + fused
 AdamW on one synthetic VCG batch per GPU (36 regions x 2052-d, 64 encoder tokens, 32 decoder tokens;
 SURVEY.md section 8d), inputs resident in HBM.  For N > 1 the driver launches one rank per GPU with
 torch.distributed.run; RCCL ("nccl") carries the all-reduce.  Rank 0 prints ONE JSON line.
+
+--steps K is the number of timed steps (split over --windows timed windows); `ms_per_step` is the time of one of them.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs); the inputs and the
+initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -252,6 +256,38 @@ def bench_batch_check(model, dev, bsz, chunk=64):
     return out
 
 
+DUMP_SAMPLE = 1 << 22   # elements of each arena sample: 2 x 16 MB of float32
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step receives after its last call: the loss it returned (loss.npy, float64 [1]) and the
+    model it left behind -- the fp32 parameters after the AdamW update (params_sample.npy) and the gradients of that step
+    (grads_sample.npy), both at the same DUMP_SAMPLE positions of the engine's parameter arena, drawn from a fixed seed
+    (the arena holds ~140 M values; the whole of it would be 1.1 GB).  Returns the names written."""
+    import numpy as np
+    eng = model._engine
+    if eng.params.is_cuda:
+        torch.cuda.synchronize()
+    n = eng.params.numel()
+    gen = torch.Generator().manual_seed(20240601)
+    idx = torch.randint(0, n, (min(n, DUMP_SAMPLE),), generator=gen).sort().values.to(eng.params.device)
+    arrays = {
+        "loss": loss.detach().reshape(-1).to(torch.float64).cpu().numpy(),
+        "params_sample": eng.params[idx].cpu().numpy().astype(np.float32),
+        "grads_sample": eng.grads[idx].cpu().numpy().astype(np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
+def window_sizes(n_steps, n_windows):
+    """--steps timed steps split over at most --windows windows (no window is empty; the first ones take the remainder)."""
+    w = max(1, min(n_windows, n_steps))
+    return [n_steps // w + (1 if i < n_steps % w else 0) for i in range(w)]
+
+
 def timed_steps(step, n_warm, n_steps):
     for _ in range(n_warm):
         step()
@@ -487,7 +523,8 @@ def main():
                          "with every doubling (`batch_sweep` reports 64 .. 2048: 0.79 / 1.53 / 1.72 / 1.80 / 1.89 M "
                          "tokens/s); rounds 1-2 quoted 512; the reference default is 64")
     ap.add_argument("--windows", type=int, default=3,
-                    help="timed windows of --steps steps each; `value` / `ms_per_step` are the median window's")
+                    help="timed windows the --steps timed steps are split into; `value` / `ms_per_step` are the median "
+                         "window's")
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -497,7 +534,12 @@ def main():
     ap.add_argument("--serial", action="store_true",
                     help="profiling aid: weight-gradient GEMMs on the main stream (no overlap), so a rocprofv3 "
                          "kernel trace shows every kernel's stand-alone duration; not the product configuration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         "< 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -571,19 +613,19 @@ def main():
 
     for _ in range(args.warmup):
         loss = step()
-    # THREE timed windows of exactly --steps steps each, every one bracketed by barrier + synchronize and reduced with
+    # exactly --steps timed steps in (up to) THREE windows, every one bracketed by barrier + synchronize and reduced with
     # MAX over ranks; `value` is the MEDIAN window, `value_min` / `value_max` and `clock_mhz` (shader clock held inside each
     # window) go beside it: a round whose gains are <= 3 % cannot be read off one window on one box
     probe = ClockProbe(_lib.load(), dev)
     power = PowerProbe(dev) if rank == 0 else None
     if power is not None:
         power.start()
-    windows = []
-    for _w in range(args.windows):
+    windows = []   # (seconds per step, clock) of each window
+    for n_w in window_sizes(args.steps, args.windows):
         fence()
         probe.stamp(0)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(n_w):
             loss = step()
         probe.stamp(1)
         fence()
@@ -592,30 +634,35 @@ def main():
             t = torch.tensor([wdt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             wdt = float(t)
-        windows.append((wdt, probe.mhz()))
+        windows.append((wdt / n_w, probe.mhz()))
     board_power = power.report() if power is not None else None
     order = sorted(range(len(windows)), key=lambda i: windows[i][0])
-    dt, clock = windows[order[len(order) // 2]]
+    step_s, clock = windows[order[len(order) // 2]]
     last_loss = float(loss)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before any other leg moves the weights on
+        dumped = dump_outputs(args.dump_outputs, model, loss)
 
     tokens_per_step = world * args.batch * (S_ENC + T_DEC)
-    value = tokens_per_step * args.steps / dt
+    value = tokens_per_step / step_s
     out = {
         "metric": "train_tokens_per_sec", "value": round(value, 1), "unit": "tokens/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_s * 1e3, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
         "config": {"workload": "vcg_base train step (fwd+bwd+allreduce+AdamW), dropout 0.1, %d regions x 2052-d, "
                                "%d enc tokens, %d dec tokens, random-init weights" % (REGIONS, S_ENC, T_DEC),
                    "global_batch": world * args.batch, "per_gpu_batch": args.batch, "parallelism": "dp%d" % world,
-                   "target_tokens_per_sec": round(world * args.batch * T_DEC * args.steps / dt, 1)},
-        "windows": len(windows), "value_min": round(tokens_per_step * args.steps / windows[order[-1]][0], 1),
-        "value_max": round(tokens_per_step * args.steps / windows[order[0]][0], 1),
-        "ms_per_step_windows": [round(w[0] / args.steps * 1e3, 3) for w in windows],
+                   "target_tokens_per_sec": round(world * args.batch * T_DEC / step_s, 1)},
+        "windows": len(windows), "value_min": round(tokens_per_step / windows[order[-1]][0], 1),
+        "value_max": round(tokens_per_step / windows[order[0]][0], 1),
+        "ms_per_step_windows": [round(w[0] * 1e3, 3) for w in windows],
         "clock_mhz": clock, "clock_mhz_windows": [w[1] for w in windows], "board_power": board_power,
         "final_loss": round(last_loss, 4),
         "model_tflops_per_gpu": round(value / world * GFLOP_PER_TOKEN / 1e3, 1),
         "mfma_frac_whole_step": round(value / world * GFLOP_PER_TOKEN / 1e3 / PEAK_BF16_TFLOPS, 4),
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "names": dumped}
     if parity is not None:
         out["ce_loss_rel_delta_vs_oracle_b2"] = float("%.3e" % parity[0])
 
@@ -676,7 +723,7 @@ def main():
             sweep[str(bsz)] = {"tokens_per_sec": round(bsz * (S_ENC + T_DEC) / sdt, 1), "ms_per_step": round(sdt * 1e3, 3)}
             if bsz in (64, 256, 512, 1024):
                 leg_steps[bsz] = (sstep, sweep[str(bsz)])
-        sweep[str(args.batch)] = {"tokens_per_sec": round(value, 1), "ms_per_step": round(dt / args.steps * 1e3, 3)}
+        sweep[str(args.batch)] = {"tokens_per_sec": round(value, 1), "ms_per_step": round(step_s * 1e3, 3)}
         out["batch_sweep"] = sweep
         out["legs"] = sweep   # the same objects: b = 64 / 256 / 512 / 1024 get their GEMM roofline below
         # (3) the measured batch computes what its 64-sample chunks compute (reported in `bench_batch_check.ok`, folded into `self_checks_ok`)
@@ -702,7 +749,7 @@ def main():
                 "algorithmic_bytes_per_launch")}
     if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
         print("[bench] GPU leg done: %.1f tokens/s, %.3f ms/step; timing the CPU baseline..." %
-              (value, dt / args.steps * 1e3), file=sys.stderr, flush=True)
+              (value, step_s * 1e3), file=sys.stderr, flush=True)
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)
