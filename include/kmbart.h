@@ -313,6 +313,21 @@ int kmb_beam_step(const float* logits, int ld, int V, int B, int num_beams, cons
 int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, int force_token, int ban_token,
                       int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
                       float* scratch, int64_t scratch_floats, int reorder_step, void* stream);
+/* One decode step's sampling tail of generate(do_sample=True, num_beams=1) (transformers 3.0.2 _generate_no_beam_search as
+ * reached from the reference's nucleus sampling, src/generation.py:22-32; filter = src/model/model.py top_k_top_p_filtering),
+ * ONE launch, no sort; stateless like kmb_beam_step.  Per row r < R of logits [R, ld] (fp32, V real columns):
+ * x = logits[r, :V] with x[ban_token] = -inf (ban_token -1: none; the min_length EOS ban), NaN read as -inf; x / temperature
+ * (correctly rounded); top_k > 0: remove x < the min(top_k, V)-th largest value (ties with it stay); top_p < 1: over the
+ * survivors ranked by (value descending, index ascending), keep a token iff the softmax mass ranked before it is <= top_p
+ * (the first always); token = argmax over the kept i of softmax_i / noise[r, i] (lowest index on ties), noise [R, ld_noise]
+ * fp32 Exp(1) draws supplied by the caller and read at kept tokens only -- torch.multinomial(p, 1)'s exponential race.
+ * unfinished (int64 [R], or NULL): a finished row takes pad_token, then unfinished[r] &= token != eos_token (-1: none).
+ * The token goes to next_tokens[r] (int64, the next kmb_gen_step's input) and, when ids != NULL, to ids[r * ld_ids + t];
+ * flag (int32, or NULL) is OR-ed with 1 when a row is still unfinished; info_out (fp32 [R, 2], or NULL) receives the number
+ * of kept tokens and the smallest kept value.  Deterministic: integer atomics only.  1 <= V <= 65536. */
+int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
+                    const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                    int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, void* stream);
 int64_t kmb_gen_workspace_bytes(const kmb_handle* h, int B, int S, int num_beams, int max_length, int n_features);
 
 /* Data-parallel runs share the GPU between the GEMMs and RCCL's all-reduce kernel (reference: torch DDP's NCCL streams,

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "kernels.h"
+#include "sample.h"
 
 extern "C" const char* kmb_last_error(void);
 int kmb_set_error(const char* msg);  // engine.cpp
@@ -218,5 +219,22 @@ int kmb_logsoftmax_topk_ws(const float* logits, int ld, int V, int rows, const f
                                             scratch_floats > 0 ? (size_t)scratch_floats : 0, (hipStream_t)stream), "logsoftmax_topk");
 }
 int64_t kmb_logsoftmax_topk_scratch(int rows) { return (int64_t)kmb_logsoftmax_topk_scratch_floats(rows); }
+int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
+                    const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                    int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, void* stream) {
+  if (!logits || !noise || !next_tokens) return kmb_set_error("kmb_sample_step: logits, noise and next_tokens are required");
+  if (V < 1 || V > KMB_SAMPLE_MAX_V || R < 0 || ld < V || ld_noise < V)
+    return kmb_set_error("kmb_sample_step: need 1 <= V <= 65536, R >= 0, ld >= V, ld_noise >= V");
+  if (!(temperature > 0.f) || std::isinf(temperature)) return kmb_set_error("kmb_sample_step: temperature must be finite and > 0");
+  if (top_k < 0) return kmb_set_error("kmb_sample_step: top_k must be >= 0");
+  if (!(top_p >= 0.f && top_p <= 1.f)) return kmb_set_error("kmb_sample_step: top_p must lie in [0, 1]");
+  if (ban_token < -1 || ban_token >= V) return kmb_set_error("kmb_sample_step: ban_token must be -1 or a token id < V");
+  if (unfinished && (pad_token < 0 || pad_token >= V || eos_token < -1 || eos_token >= V))
+    return kmb_set_error("kmb_sample_step: pad_token must be a token id, eos_token -1 or a token id");
+  if (ids && (t < 0 || t >= ld_ids)) return kmb_set_error("kmb_sample_step: need 0 <= t < ld_ids");
+  return hipfail(kmb_sample_step_launch(logits, ld, V, R, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished,
+                                        pad_token, eos_token, next_tokens, ids, t, ld_ids, flag, info_out, (hipStream_t)stream),
+                 "sample_step");
+}
 
 }  // extern "C"

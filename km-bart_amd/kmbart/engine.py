@@ -628,6 +628,29 @@ class Engine:
             self.gen_reorder(nidx, reorder_step)
         return cand, nscore, ntok, nidx
 
+    def sample_step(self, logits, noise, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, unfinished=None, pad_token=0,
+                    eos_token=-1, next_tokens=None, ids=None, t=0, flag=None, info_out=None):
+        """One decode step's sampling tail (kmb_sample_step): EOS ban, temperature, top-k, top-p and the exponential-race
+        draw on `noise` (fp32 [R, >= V] Exp(1) draws) in one launch.  `logits` may be gen_step's padded view.  Returns
+        next_tokens (int64 [R]); unfinished (int64 [R]) and the id buffer ids (int64 [R, ld], column t) are updated in place;
+        flag (int32, one element) is OR-ed with 1 while a row is unfinished; info_out (fp32 [R, 2]): kept count, smallest
+        kept value."""
+        R, V = logits.shape[0], int(self.config.vocab_size)
+        for x, dt in ((logits, torch.float32), (noise, torch.float32), (unfinished, torch.int64), (ids, torch.int64),
+                      (flag, torch.int32), (info_out, torch.float32)):
+            assert x is None or (x.device == self.device and x.dtype == dt and x.stride(-1) == 1), "sample_step: bad tensor"
+        assert noise.shape[0] == R and (unfinished is None or unfinished.numel() == R) and (ids is None or ids.shape[0] == R)
+        assert info_out is None or info_out.is_contiguous() and info_out.numel() == 2 * R
+        if next_tokens is None:
+            next_tokens = torch.empty((R,), dtype=torch.int64, device=self.device)
+        assert next_tokens.is_contiguous() and next_tokens.numel() == R and next_tokens.dtype == torch.int64
+        with torch.cuda.device(self.device):
+            check(self.lib.kmb_sample_step(ptr(logits), logits.stride(0), V, R, float(temperature), int(top_k), float(top_p),
+                                           int(ban_token), ptr(noise), noise.stride(0), ptr(unfinished), int(pad_token),
+                                           int(eos_token), ptr(next_tokens), ptr(ids), int(t),
+                                           ids.stride(0) if ids is not None else 0, ptr(flag), ptr(info_out), _stream()))
+        return next_tokens
+
     def _topk_scratch_for(self, R):
         nscr = int(self.lib.kmb_logsoftmax_topk_scratch(R))
         scr = self.__dict__.get("_topk_scratch")

@@ -679,6 +679,10 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                 eng.check_inputs_begin()
         cur_len = 1
 
+        if num_beams == 1 and do_sample and not processors_on and not fp32 and getattr(self, "_device_sampling", True):
+            return self._sample_on_device(eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id,
+                                          eos_token_id, decoder_start_token_id)
+
         if num_beams == 1:
             # Greedy / sampling without beams (transformers 3.0.2 _generate_no_beam_search): everything stays on the
             # device; the "every sentence has finished" test is read one step late from a pinned flag, so step t+1 is
@@ -888,6 +892,45 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             eng.check_inputs_end()
         out = out.to(dev)
         return (out, torch.tensor(best_scores)) if return_scores else out
+
+    def _sample_on_device(self, eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id, eos_token_id,
+                          decoder_start_token_id):
+        """generate(do_sample=True, num_beams=1) without score post-processing: every decode step is gen_step -> Exp(1)
+        noise -> kmb_sample_step (EOS ban, temperature, top-k, top-p, draw and the finished-row bookkeeping in one launch).
+        The noise is drawn as torch.multinomial(probs, 1) draws it ([B, V] exponential_ on the default generator), so a
+        seeded run consumes the random stream the torch path consumes and picks the same tokens except where fp32 rounding
+        decides a near-tie.  model._device_sampling = False selects the torch path."""
+        dev = eng.device
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        ids = torch.full((B, max_length), pad_token_id if pad_token_id is not None else 0, dtype=torch.long, device=dev)
+        ids[:, 0] = decoder_start_token_id
+        toks = [ids[:, 0].contiguous(), torch.empty(B, dtype=torch.long, device=dev)]   # ping-pong: step t reads one, writes the other
+        unfinished = torch.ones(B, dtype=torch.long, device=dev) if eos_token_id is not None else None
+        noise = torch.empty((B, V), dtype=torch.float32, device=dev)
+        dflags = torch.zeros(max_length + 1, dtype=torch.int32, device=dev)
+        flags = eng.pinned((max_length + 1,), torch.int32)
+        cur_len, pending, keep = 1, None, None
+        while cur_len < max_length:
+            logits = eng.gen_step(toks[(cur_len - 1) % 2], cur_len - 1)
+            ban = eos if (eos >= 0 and cur_len < min_length) else -1
+            noise.exponential_(1)
+            eng.sample_step(logits, noise, temperature, top_k, top_p, ban_token=ban, unfinished=unfinished,
+                            pad_token=pad_token_id if unfinished is not None else 0, eos_token=eos,
+                            next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1])
+            cur_len += 1
+            if unfinished is not None:   # the finished flag, read one step late as in the torch path
+                flags[cur_len - 1].copy_(dflags[cur_len - 1], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                if pending is not None:
+                    pending[1].synchronize()
+                    if int(flags[pending[0] - 1]) == 0:
+                        keep = pending[0]
+                        break
+                pending = (cur_len, ev)
+        out = ids[:, :keep if keep is not None else cur_len].contiguous()
+        eng.check_inputs_end()
+        return out
 
     @staticmethod
     def _fp32_step_fn(eng, input_ids, image_features, attention_mask, num_beams):

@@ -2,6 +2,11 @@
 cross-attention K/V computed once per batch item.  Prints one JSON line.
 
     python tools/gen_bench.py [--batch 64] [--beams 5] [--max-length 20] [--reps 5]
+
+--do-sample with --beams 1 times sampled generation (the reference's nucleus sampling, batch x --num-gen rows): the device
+sampler (kmb_sample_step) and, unless --no-host, the torch path (model._device_sampling = False) alternated in one
+process, each generate timed to a device synchronise; one JSON line per path, the first row of each seeded output shared
+between them.  --host-sampling times the torch path alone.
 """
 import argparse
 import json
@@ -22,6 +27,13 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--beams", type=int, default=5)
 ap.add_argument("--max-length", type=int, default=20)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--do-sample", action="store_true")
+ap.add_argument("--top-p", type=float, default=1.0)
+ap.add_argument("--top-k", type=int, default=0)
+ap.add_argument("--temperature", type=float, default=1.0)
+ap.add_argument("--num-gen", type=int, default=1)
+ap.add_argument("--host-sampling", action="store_true", help="time the torch sampling path only")
+ap.add_argument("--no-host", action="store_true", help="time the device sampler only")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
@@ -29,6 +41,34 @@ model = MultiModalBartForConditionalGeneration(MultiModalBartConfig.from_dict(be
 b = make_batch(args.batch, seed=4321)
 ids, am = b["input_ids"].to(dev), b["attention_mask"].to(dev)
 feats = [f.to(dev) for f in b["image_features"]]
+if args.do_sample:
+    kw = dict(num_beams=args.beams, do_sample=True, top_p=args.top_p, top_k=args.top_k, temperature=args.temperature,
+              num_return_sequences=args.num_gen, max_length=args.max_length)
+    paths = ["host"] if args.host_sampling else (["device"] if args.no_host else ["device", "host"])
+    tot = {p: 0.0 for p in paths}
+    steps = {p: 0 for p in paths}
+    for rep in range(args.reps + 1):          # rep 0 warms both paths up
+        for p in paths:
+            model._device_sampling = p == "device"
+            torch.manual_seed(rep)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.generate(input_ids=ids, image_features=feats, attention_mask=am, **kw)
+            torch.cuda.synchronize()
+            if rep:
+                tot[p] += time.perf_counter() - t0
+                steps[p] += out.shape[1] - 1
+    for p in paths:
+        dt = tot[p] / args.reps
+        print(json.dumps({"metric": "sampled_generate_ms", "path": p, "value": round(dt * 1e3, 2), "unit": "ms/generate",
+                          "ms_per_decode_step": round(tot[p] / max(steps[p], 1) * 1e3, 3),
+                          "sequences_per_sec": round(args.batch * args.num_gen / dt, 1),
+                          "config": {"workload": "vcg_base generate, sampling", "batch": args.batch, "num_gen": args.num_gen,
+                                     "rows": args.batch * args.num_gen, "top_k": args.top_k, "top_p": args.top_p,
+                                     "temperature": args.temperature, "max_length": args.max_length,
+                                     "decoder_steps": steps[p] / args.reps},
+                          "dtype": "bf16", "data": "synthetic", "n_gpus": 1}))
+    sys.exit(0)
 kw = dict(num_beams=args.beams, num_return_sequences=1, max_length=args.max_length, early_stopping=True)
 out = model.generate(input_ids=ids, image_features=feats, attention_mask=am, **kw)
 torch.cuda.synchronize()
