@@ -265,8 +265,19 @@ int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_
  * forward's return tuple (src/model/model.py:384-397 returns decoder_outputs + encoder_outputs) */
 int kmb_gen_encoder_states(kmb_handle* h, kmb_bf16* enc_out, void* stream);
 /* one cached decoder step (src/model/mixins.py:386-398 -> model.py:384-397): tokens [B*num_beams]
- * at position `step` (0-based), logits_out fp32 [B*num_beams, kmb_logits_ld()] */
+ * at position `step` (0-based), logits_out fp32 [B*num_beams, kmb_logits_ld()].  A non-NULL `tokens` is always embedded.
+ * tokens = NULL: the step runs on the tokens the preceding kmb_gen_beam_step(reorder_step = step - 1) chose and already
+ * embedded (no embedding launch); fails when no such embedding is pending for `step` (kmb_gen_embedded_step). */
 int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_out, void* stream);
+/* the step whose tokens the last kmb_gen_beam_step embedded for a kmb_gen_step(tokens = NULL), or -1: none pending (any
+ * kmb_gen_step or kmb_gen_beam_step since, or that beam step did not embed -- KMB_GEN_FOLD_EMBED=0, no reorder, or the
+ * decoder states kmb_gen_last_hidden returns still lived where the embedding goes).  Host state only: no stream work. */
+int kmb_gen_embedded_step(const kmb_handle* h);
+/* the number of 256-column blocks of (maximum, sum-exp) statistics the last kmb_gen_step's vocabulary projection left for `logits` (the
+ * logits_out it was given), or 0: none -- another GEMM kernel ran (not 257 .. 320 beam rows), KMB_GEN_HEAD_STATS=0, no projection, or other
+ * logits.  While it is > 0, kmb_gen_beam_step on those logits without a forced token selects from the statistics in one launch.  Host state
+ * only: no stream work. */
+int kmb_gen_stats_blocks(const kmb_handle* h, const float* logits);
 /* _reorder_cache (src/model/mixins.py:419-434): self-attention caches follow beam_idx [B*num_beams] */
 int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream);
 /* The final decoder states of the last kmb_gen_step as bf16 [rows, d_model] (the `decoder_outputs[0]` of a cached bare-model
@@ -309,7 +320,10 @@ int kmb_beam_step(const float* logits, int ld, int V, int B, int num_beams, cons
  * KMB_GEN_HEAD_STATS=0 in the environment: kmb_beam_step itself.  Reference: one step of transformers 3.0.2
  * _generate_beam_search as reached from src/model/mixins.py:336-361, scores adjusted as in mixins.py:386-417.
  * reorder_step >= 0: the call is also kmb_gen_reorder(h, next_beam_idx, reorder_step, stream) (_reorder_cache,
- * src/model/mixins.py:419-434) -- with the history index by the launch that has just chosen the beams; -1: no reorder. */
+ * src/model/mixins.py:419-434) -- with the history index by the launch that has just chosen the beams; -1: no reorder.  It
+ * then usually also embeds next_tokens for step reorder_step + 1: kmb_gen_embedded_step() tells, and kmb_gen_step(h, NULL,
+ * reorder_step + 1, ...) uses them.  The statistics belong to the logits as kmb_gen_step wrote them: a caller that edits
+ * those logits (masks, penalties) between the two calls must use kmb_beam_step (+ kmb_gen_reorder) instead. */
 int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, int force_token, int ban_token,
                       int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
                       float* scratch, int64_t scratch_floats, int reorder_step, void* stream);

@@ -192,9 +192,9 @@ struct kmb_handle {
     // per-block (maximum, sum-exp) pairs the last kmb_gen_step's vocabulary projection left beside the logits at head_stats_for
     // (head_stats_blocks column blocks; 0: none -- the step ran another GEMM kernel, or no projection): kmb_gen_beam_step selects from them
     float* head_stats = nullptr; int head_stats_blocks = 0; const float* head_stats_for = nullptr;
-    // x0 already holds the embedded rows of decode step x0_step for the tokens at x0_tokens (kmb_gen_beam_step embedded the tokens it chose
-    // in its own launch): the kmb_gen_step of exactly that step and token buffer skips its embedding launch.  -1: no
-    int x0_step = -1; const int64_t* x0_tokens = nullptr;
+    // x0 already holds the embedded rows of decode step x0_step (kmb_gen_beam_step embedded the tokens it chose in its own launch): a
+    // kmb_gen_step(tokens = NULL) of exactly that step uses them instead of embedding.  -1: nothing pending
+    int x0_step = -1;
     uint64_t packed_version = 0; const bf16_t* packed_at = nullptr;   // the fragment-order copies at wp[0] were made from mirror version ...
   } gen;
 
@@ -1997,15 +1997,18 @@ int kmb_comm_gather_moments(kmb_handle* h, void* compute_stream) {
 // ================================================================================= generation
 namespace {
 
-struct GenLayout {
-  int32_t* status; bf16_t* xf; float* img_emb; int32_t* img_src; bf16_t* xe[2]; EncAct ea;
+struct GenLayout {   // (every pointer starts null: the product build leaves `bars` unset, and kmb_gen_begin copies it)
+  int32_t* status = nullptr; bf16_t* xf = nullptr; float* img_emb = nullptr; int32_t* img_src = nullptr;
+  bf16_t* xe[2] = {nullptr, nullptr}; EncAct ea{};
   std::vector<bf16_t*> ckv, kc[2], vc[2];
-  int32_t* kv_row; bf16_t *x0, *x1, *qkv, *o, *z, *y, *cq, *u, *hh; float *mean, *rstd;
-  float* slab;   // split-K partial sums of the residual projections of a decode step
+  int32_t* kv_row = nullptr;
+  bf16_t *x0 = nullptr, *x1 = nullptr, *qkv = nullptr, *o = nullptr, *z = nullptr, *y = nullptr, *cq = nullptr, *u = nullptr, *hh = nullptr;
+  float *mean = nullptr, *rstd = nullptr;
+  float* slab = nullptr;   // split-K partial sums of the residual projections of a decode step
   std::vector<bf16_t*> wp;   // per layer: self q|k|v, self out, cross q, cross out, fc1, fc2 in fragment order (decode.hip)
-  uint32_t* bars;            // group-barrier counters of the resident decoder-layers kernel (decode.hip)
-  int32_t* hist[2];          // history index of the self-attention caches [R, Tmax], ping-pong over beam reorders
-  float* head_stats;         // the all-rows vocabulary projection's per-block (maximum, sum-exp) pairs (kmb_gen_beam_step)
+  uint32_t* bars = nullptr;  // group-barrier counters of the resident decoder-layers kernel (decode.hip)
+  int32_t* hist[2] = {nullptr, nullptr};   // history index of the self-attention caches [R, Tmax], ping-pong over beam reorders
+  float* head_stats = nullptr;   // the all-rows vocabulary projection's per-block (maximum, sum-exp) pairs (kmb_gen_beam_step)
 };
 constexpr int GEN_MAX_SPLIT = 12;
 
@@ -2098,7 +2101,7 @@ int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_
   G.bars = g.bars;
   G.hist[0] = g.hist[0]; G.hist[1] = g.hist[1]; G.hcur = 0;
   G.head_stats = g.head_stats; G.head_stats_blocks = 0; G.head_stats_for = nullptr;
-  G.x0_step = -1; G.x0_tokens = nullptr;
+  G.x0_step = -1;
   { const char* he = getenv("KMB_GEN_HIST"); G.use_hist = !(he && he[0] == '0'); }
   // cross-attention K|V of every decoder layer, computed once per batch item (not per beam), all layers in ONE GEMM
   if (Ld > 0) {
@@ -2148,13 +2151,18 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
   const float eps = h->cfg.layer_norm_eps;
   const float scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f;
   const KmbDrop nodrop{0u, 0u, 1.f};
-  // BartDecoder with use_cache: only the last token, learned position (len-1) + 2
-  // (skipped when the beam step that chose these tokens has embedded them already: kmb_gen_beam_step, same row code)
-  if (!(G.x0_step == step && G.x0_tokens == tokens))
+  // BartDecoder with use_cache: only the last token, learned position (len-1) + 2.  tokens = NULL: the caller asks for the rows the
+  // preceding kmb_gen_beam_step(reorder_step = step - 1) embedded from the tokens it chose (same row code) -- requested, never
+  // inferred from an address: a caller may have edited that buffer since, or the allocator handed it to another tensor
+  if (!tokens) {
+    if (G.x0_step != step)
+      return fail("kmb_gen_step: tokens = NULL but no kmb_gen_beam_step embedded the tokens of step %d (pending: %d)", step, G.x0_step);
+  } else {
     HIPCHK(kmb_embed_ln_fwd_launch(tokens, nullptr, h->pf(h->shared), nullptr, h->pf(h->dec_pos),
                                    h->cfg.extra_pos_embeddings + step, 1, scale, h->pf(h->dec_lne_g),
                                    h->pf(h->dec_lne_b), nullptr, G.x0, nullptr, nullptr, R, d, eps, nodrop, s));
-  G.x0_step = -1; G.x0_tokens = nullptr;
+  }
+  G.x0_step = -1;
   bf16_t* x = G.x0; bf16_t* xn = G.x1;
   // residual projection + LayerNorm (BartDecoderLayer: x = LN(residual + dropout(proj(x)))).  With R = batch x beams rows
   // the projection has 18 output tiles of 128 x 128 and a serial K loop: split K over workgroups and let ONE kernel sum
@@ -2353,14 +2361,17 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
   // (G.x0 is free: the step's layers have run).  KMB_GEN_FOLD_EMBED=0: kmb_gen_step's own embedding launch, as before round 6.
   const char* fe_env = getenv("KMB_GEN_FOLD_EMBED");
   const int d = h->d;
-  const bool embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && !(fe_env && fe_env[0] == '0') && (d & 7) == 0 && d > 512 && d <= 1024;
+  // ... not when x0 still holds the step's final decoder states (the launch-per-operation path swaps x0 / x1 once per layer, so an even
+  // number of layers ends there): kmb_gen_last_hidden must keep returning them; the next kmb_gen_step embeds then
+  const bool embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && !(fe_env && fe_env[0] == '0') && (d & 7) == 0 && d > 512 && d <= 1024 &&
+                     G.last_x != G.x0;
   KmbEmbedNext en;
   if (embed) {
     en.E = h->pf(h->shared); en.prow = h->pf(h->dec_pos) + (size_t)(h->cfg.extra_pos_embeddings + reorder_step + 1) * d;
     en.gamma = h->pf(h->dec_lne_g); en.beta = h->pf(h->dec_lne_b); en.y = G.x0;
     en.scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f; en.D = d; en.eps = h->cfg.layer_norm_eps; en.V = h->V;
   }
-  G.x0_step = -1; G.x0_tokens = nullptr;
+  G.x0_step = -1;
   hipError_t e = hipErrorNotSupported;
   if (force_token < 0 && G.head_stats_blocks > 0 && G.head_stats_for == logits)
     e = kmb_beam_step_stats_launch(logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
@@ -2372,7 +2383,7 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
                              embed ? &en : nullptr);
   if (e == hipErrorNotSupported) return fail("kmb_gen_beam_step: unsupported shape (k <= 16, num_beams <= 16, num_beams * k <= 256)");
   HIPCHK(e);
-  if (embed) { G.x0_step = reorder_step + 1; G.x0_tokens = next_tokens; }
+  if (embed) G.x0_step = reorder_step + 1;
   if (fold) {
     G.hcur ^= 1;
     if (G.nb == 1) {   // independent rows: the row -> cross-attention item table follows (kmb_gen_reorder)
@@ -2399,6 +2410,14 @@ int kmb_gen_last_hidden(kmb_handle* h, kmb_bf16* out, void* stream) {
     return fail("kmb_gen_last_hidden: no kmb_gen_step has run since kmb_gen_begin");
   }
   return 0;
+}
+
+int kmb_gen_embedded_step(const kmb_handle* h) {
+  return h && h->gen.active ? h->gen.x0_step : -1;
+}
+
+int kmb_gen_stats_blocks(const kmb_handle* h, const float* logits) {
+  return h && h->gen.active && logits && h->gen.head_stats_for == logits ? h->gen.head_stats_blocks : 0;
 }
 
 int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream) {

@@ -1352,8 +1352,11 @@ __global__ __launch_bounds__(512) void gemm_kernel_allrows(const KmbGemm p, floa
       else __builtin_amdgcn_s_waitcnt(0x0F70);
     }
     // stage s is complete, and every wave is done reading stage s - 1.  NOT __syncthreads(): its fence is a vmcnt(0) -- the rounds 4-5
-    // form of this loop had one, so its counted vmcnt(9) never held and every step drained the stage it had just issued
+    // form of this loop had one, so its counted vmcnt(9) never held and every step drained the stage it had just issued.  The empty asm
+    // with a memory clobber keeps the compiler from hoisting the plain C++ LDS reads below above the wait and the barrier
+    // (tests/test_cabi_cpu.py checks the compiled loop)
     __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
     if (s == 0) KMB_STAMP(1);
     if (s == ns / 2) KMB_STAMP(3);
     // The stage three ahead goes into stage s - 1's buffer, one piece per eight MFMAs (a piece holds the issuing wave for 60-180 cycles;

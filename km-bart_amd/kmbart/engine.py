@@ -535,6 +535,8 @@ class Engine:
             self._gen_enc_shape = (B, S)
             self._gen_max_length = int(max_length)
             self._gen_logits = torch.empty((self._gen_rows, self.logits_ld), dtype=torch.float32, device=self.device)
+            self._gen_logits_version = None   # _gen_logits._version right after the last gen_step that wrote them
+            self._folded = None               # (ntok, its _version, step): the tokens the last beam_step embedded for that step
 
     def gen_encoder_states(self):
         """[B, S, d] bf16: the encoder output of the active gen_begin (a copy)."""
@@ -547,12 +549,21 @@ class Engine:
     def gen_step(self, tokens, step, want_logits=True):
         """tokens int64 [B*num_beams] (device) at 0-based position `step` -> fp32 logits [R, V] (padded view).
         want_logits=False: the decoder layers run (the KV cache gets position `step`) but the vocabulary projection is
-        skipped; the returned buffer then holds stale values (for steps whose token is forced)."""
+        skipped; the returned buffer then holds stale values (for steps whose token is forced).
+        When `tokens` is the very next_tokens tensor the last beam_step(reorder_step = step - 1) returned, unchanged since (same
+        _version), and that beam step embedded them, the step runs on that embedding (kmb_gen_step with tokens = NULL, no
+        embedding launch); any other tokens are embedded.  (Writes to that tensor that torch does not see -- a raw pointer
+        handed to other native code -- are the caller's to avoid.)"""
+        folded, self._folded = self.__dict__.get("_folded"), None
         with torch.cuda.device(self.device):
-            tokens = tokens.to(device=self.device, dtype=torch.int64).contiguous()
-            check(self.lib.kmb_gen_step(self.h, ptr(tokens), int(step), ptr(self._gen_logits) if want_logits else None,
-                                        _stream()))
+            if folded is not None and tokens is folded[0] and tokens._version == folded[1] and int(step) == folded[2]:
+                tok_ptr = None
+            else:
+                tokens = tokens.to(device=self.device, dtype=torch.int64).contiguous()
+                tok_ptr = ptr(tokens)
+            check(self.lib.kmb_gen_step(self.h, tok_ptr, int(step), ptr(self._gen_logits) if want_logits else None, _stream()))
             self._keep_tok = tokens
+        self._gen_logits_version = self._gen_logits._version if want_logits else None
         return self._gen_logits
 
     def gen_last_hidden(self):
@@ -595,6 +606,7 @@ class Engine:
         reorder_step), folded into the beam step's launch when `logits` are gen_step's)."""
         R = logits.shape[0]
         B = R // num_beams
+        self._folded = None
         # cand_out: a page-locked host tensor [B, k, 2] int32 the kernel writes directly (device-visible host memory: no copy
         # launch between two decode steps); the caller reads it after an event recorded behind this call
         cand = cand_out if cand_out is not None else torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
@@ -604,14 +616,18 @@ class Engine:
         if k <= 16 and num_beams <= 16 and num_beams * k <= 256 and logits.stride(0) % 4 == 0:
             # kmb_beam_step: the rows' top-k lists never leave the workgroup that merges them (one launch less per decode step)
             scr = self._topk_scratch_for(R)
-            if logits is self.__dict__.get("_gen_logits"):
+            if logits is self.__dict__.get("_gen_logits") and (force_token >= 0 or logits._version == self._gen_logits_version):
                 # the decode loop: kmb_gen_beam_step selects from the statistics the step's vocabulary projection left (one launch,
-                # no second pass over the logits) when there are any, and is kmb_beam_step otherwise
+                # no second pass over the logits) when there are any, and is kmb_beam_step otherwise.  Those statistics describe the
+                # logits as gen_step wrote them: logits edited in place since (their _version moved) take kmb_beam_step below.
+                # (A forced step reads no logits.)
                 with torch.cuda.device(self.device):
                     check(self.lib.kmb_gen_beam_step(self.h, ptr(logits), logits.stride(0), int(num_beams), ptr(add), int(force_token),
                                                      int(ban_token), int(k), ptr(cand), int(eos_token), ptr(nscore), ptr(ntok),
                                                      ptr(nidx), ptr(scr), scr.numel(), int(reorder_step), _stream()))
                     self._keep_idx = nidx
+                    if reorder_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == reorder_step + 1:
+                        self._folded = (ntok, ntok._version, reorder_step + 1)
                 return cand, nscore, ntok, nidx
             with torch.cuda.device(self.device):
                 check(self.lib.kmb_beam_step(ptr(logits), logits.stride(0), int(self.config.vocab_size), B, int(num_beams), ptr(add),

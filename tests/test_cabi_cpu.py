@@ -233,3 +233,38 @@ def test_tr_asm_hazard_checker_sees_a_violation(tmp_path):
         p.write_text(text)
         r = subprocess.run([sys.executable, tool, str(p)], capture_output=True, text=True)
         assert r.returncode == want, "%s: rc %d, expected %d\n%s" % (name, r.returncode, want, r.stdout + r.stderr)
+
+
+def test_allrows_kloop_reads_stay_behind_the_wait_and_barrier(tmp_path):
+    """csrc/gemm.hip gemm_kernel_allrows<*> (the decode step's vocabulary projection at 257-320 rows) waits for its oldest stage with a counted
+    `s_waitcnt vmcnt(N)`, meets the other waves at a bare `s_barrier` and then reads the stage's fragments with plain C++ LDS loads.  A property of
+    the COMPILED loop (tools/gemm_kloop_audit.py allrows_kloop_problems): no LDS read between the loop head and the barrier, the fourteen
+    ds_read_b128 after it, the counted immediates (10/5/0 and 8/4/0) in front of it, and no vector-memory instruction in the loop but the five
+    LDS-DMA pieces, which the immediates count.  The checker must also flag hand-edited copies that break each rule."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from gemm_kloop_audit import allrows_kloop_problems
+    out = _compile_to_isa("gemm.hip", str(tmp_path / "gemm.hip.s"))
+    found = allrows_kloop_problems(out)
+    assert len(found) == 2, sorted(found)          # <false> (plain) and <true> (statistics epilogue)
+    assert all(not p for p in found.values()), found
+    text = open(out).read()
+    name = next(k for k in found if "ILb1E" in k)
+    start = text.index(name + ":")
+    end = text.index(".Lfunc_end", start)
+    body = text[start:end].split("\n")
+    head = next(i for i, l in enumerate(body) if "Loop Header" in l)
+    bar = next(i for i in range(head, len(body)) if body[i].strip().startswith("s_barrier"))
+    rd = next(i for i in range(bar, len(body)) if body[i].strip().startswith("ds_read_b128"))
+    hoisted = body[:bar] + [body[rd]] + body[bar:rd] + body[rd + 1:]             # one fragment read above the barrier
+    extra_load = body[:rd] + ["\tglobal_load_dwordx4 v[250:253], v[0:1], off"] + body[rd:]   # a plain global load inside the loop
+    w = next(i for i in range(head, bar) if "vmcnt(10)" in body[i])
+    recounted = body[:w] + [body[w].replace("vmcnt(10)", "vmcnt(9)")] + body[w + 1:]         # a wait that no longer matches the pieces
+    for tag, edited, want in (("hoisted", hoisted, "between the loop head and the barrier"), ("extra_load", extra_load, "other than an LDS-DMA"),
+                              ("recounted", recounted, "counted 10 / 5 / 0")):
+        p = tmp_path / ("allrows_%s.s" % tag)
+        p.write_text(text[:start] + "\n".join(edited) + text[end:])
+        probs = allrows_kloop_problems(str(p))[name]
+        assert any(want in x for x in probs), (tag, probs)
+        other = next(k for k in found if k != name)
+        assert not allrows_kloop_problems(str(p))[other], tag   # the edit is local to the kernel it was made in

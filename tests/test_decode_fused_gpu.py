@@ -202,10 +202,11 @@ def test_decode_steps_match_oracle_and_unfused_path():
     assert d < 1.5e-2
 
 
-def _oracle_sequence_score(sd, ocfg, b, row, ids, length_penalty=1.0):
+def _oracle_sequence_score(sd, ocfg, b, row, ids, length_penalty=1.0, max_length=None):
     """The beam-search score the ORACLE gives a finished hypothesis of batch item `row`: the sum of its tokens' log-probabilities
     (teacher forced, decoder start token excluded) / len ** length_penalty with len = the position of </s> (or the full length),
-    transformers 3.0.2 BeamHypotheses.add as the search reaches it (src/model/mixins.py:336-361)."""
+    transformers 3.0.2 BeamHypotheses.add as the search reaches it (src/model/mixins.py:336-361).  A FORCED token counts log 1 = 0, as
+    in the search (adjust_logits_during_generation, mixins.py:400-405): <s> at position 1, and </s> at position max_length - 1."""
     ids = [int(t) for t in ids]
     while len(ids) > 1 and ids[-1] == ocfg.pad_token_id:
         ids.pop()
@@ -214,7 +215,8 @@ def _oracle_sequence_score(sd, ocfg, b, row, ids, length_penalty=1.0):
         logits = O.forward(sd, ocfg, b["input_ids"][row:row + 1], [b["image_features"][row]], b["attention_mask"][row:row + 1],
                            dec, torch.ones_like(dec), None)[1]
         lp = torch.log_softmax(logits[0].double(), -1)
-    total = float(sum(lp[t, ids[t + 1]] for t in range(len(ids) - 1)))
+    forced = {1} | ({max_length - 1} if max_length else set())
+    total = float(sum(lp[t, ids[t + 1]] for t in range(len(ids) - 1) if t + 1 not in forced))
     n = len(ids) - 1 if ids[-1] == ocfg.eos_token_id else len(ids)   # a hypothesis finished by </s> is scored at the length before it
     return total / (n ** length_penalty)
 
@@ -266,8 +268,8 @@ def test_full_size_beam5_search_matches_the_oracle(fused, sublayer_scale):
         if bool(same[r]):
             assert abs(float(sc[r]) - float(ref_sc[r])) < 3e-2, r
         else:
-            alt = _oracle_sequence_score(sd, ocfg, b, r, got[r].tolist())
-            best = _oracle_sequence_score(sd, ocfg, b, r, ref_ids[r].tolist())
+            alt = _oracle_sequence_score(sd, ocfg, b, r, got[r].tolist(), max_length=kw["max_length"])
+            best = _oracle_sequence_score(sd, ocfg, b, r, ref_ids[r].tolist(), max_length=kw["max_length"])
             assert abs(best - float(ref_sc[r])) < 1e-3, "the test's scorer must reproduce the oracle's own score"
             assert alt >= best - 2e-2, "row %d: the product's hypothesis is not a tie for the oracle (%.4f vs %.4f)" % (r, alt, best)
 

@@ -186,7 +186,9 @@ def test_generation_with_and_without_the_statistics_path_returns_the_same_ids(kn
 
 def _drive(eng, b, nb, steps, folded, fresh_token_buffer=False):
     """gen_step + beam_step for `steps` steps through the engine API; folded: the beam step also reorders (and embeds the next step's tokens),
-    otherwise gen_reorder is called separately (and gen_step embeds).  Returns the logits of every step and the chosen tokens."""
+    otherwise gen_reorder is called separately (and gen_step embeds).  fresh_token_buffer: the next step's input is ANOTHER tensor with
+    other contents (the chosen tokens reversed, every third row pad), so that a step run on the beam step's own embedding would show.
+    Returns the logits of every step and the chosen tokens."""
     V = eng.config.vocab_size
     B = b["input_ids"].shape[0]
     R = B * nb
@@ -201,7 +203,11 @@ def _drive(eng, b, nb, steps, folded, fresh_token_buffer=False):
         cand, add, ntok, nidx = eng.beam_step(lg, nb, k, add, eos_token=-1, reorder_step=t if folded else -1)
         if not folded:
             eng.gen_reorder(nidx, t)
-        tok = ntok.clone() if fresh_token_buffer else ntok    # a clone: another buffer -- the prepared embedding must not be used blindly
+        if fresh_token_buffer:      # another buffer, other tokens: the prepared embedding must not be used
+            tok = ntok.flip(0).clone()
+            tok[::3] = 1
+        else:
+            tok = ntok
         out.append(ntok.clone())
     torch.cuda.synchronize()
     return out
@@ -211,7 +217,8 @@ def _drive(eng, b, nb, steps, folded, fresh_token_buffer=False):
 def test_folded_reorder_and_embedding_equal_the_separate_calls(B, nb):
     """kmb_gen_beam_step(reorder_step = t) == kmb_gen_beam_step(-1) + kmb_gen_reorder(t) + kmb_gen_step's own embedding, bit for bit over
     four decode steps: 64 x 5 (statistics path), 300 x 1 (one beam per item: the row -> item table is gathered too), 12 x 4 (48 rows: the
-    two-launch beam step carries the fold); and a token buffer that is NOT the one the beam step embedded is embedded again."""
+    two-launch beam step carries the fold); and a token buffer that is NOT the one the beam step embedded, with other tokens, is embedded
+    again (compared with the unfolded run on the same tokens)."""
     from oracle import goldenlib as G
     from oracle import kmbart_oracle as O
     from src.data.synthetic import make_batch
@@ -226,8 +233,8 @@ def test_folded_reorder_and_embedding_equal_the_separate_calls(B, nb):
     model.to(DEV).eval()
     b = make_batch(B, seed=B + nb)
     eng = model._engine
-    want = _drive(eng, b, nb, 4, folded=False)
     for fresh in (False, True):
+        want = _drive(eng, b, nb, 4, folded=False, fresh_token_buffer=fresh)
         got = _drive(eng, b, nb, 4, folded=True, fresh_token_buffer=fresh)
         assert len(got) == len(want)
         for i, (g_, w_) in enumerate(zip(got, want)):

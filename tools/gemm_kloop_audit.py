@@ -107,6 +107,55 @@ def audit_file(path, src="gemm.hip", sig_for=()):
     return rows
 
 
+def allrows_kloop_problems(path):
+    """{kernel: [problem, ...]} for every gemm_kernel_allrows<*> in the device assembly `path` (tests/test_cabi_cpu.py).  The all-rows K loop
+    (csrc/gemm.hip) reads its fragments with plain C++ LDS loads behind a counted `s_waitcnt vmcnt(N)` and a bare `s_barrier`; nothing but the
+    compiler's scheduling keeps those reads behind the two.  In the compiled loop, from its header on:
+      * the counted waits, vmcnt 10 / 5 / 0 (waves 0-3) and 8 / 4 / 0 (waves 4-7), come before the one `s_barrier`, and no LDS read does;
+      * every LDS read of the step (fourteen `ds_read_b128`: four tied-matrix and ten row-panel fragments) comes after the barrier;
+      * the only vector-memory instructions are the stage's LDS-DMA pieces -- anything else would count against the vmcnt immediates."""
+    s = open(path).read()
+    out = {}
+    for name, b in kernels(s):
+        if "allrows" not in name:
+            continue
+        probs = out.setdefault(name, [])
+        lp = k_loop(b)
+        if lp is None:
+            probs.append("no K loop found")
+            continue
+        top = re.match(r"(\.LBB\d+_\d+):", b[lp[0]]).group(1)   # the loop runs to the LAST branch back to its top (k_loop stops at the first)
+        end = max(n for n, l in enumerate(b) if re.search(r"s_c?branch\S*\s+%s\b" % re.escape(top), l))
+        seg = [l.strip() for l in b[lp[0]:end + 1]]
+        head = next((i for i, l in enumerate(seg) if "Loop Header" in l), 0)
+        # one iteration in execution order: header .. back branch, then the latch blocks placed above the header
+        it = [l for l in seg[head:] + seg[:head] if l and not l.startswith(";") and not l.startswith(".")]
+        bars = [i for i, l in enumerate(it) if l.startswith("s_barrier")]
+        if len(bars) != 1:
+            probs.append("%d s_barrier in the loop, expected 1" % len(bars))
+            continue
+        bar = bars[0]
+        waits = sorted(int(re.search(r"vmcnt\((\d+)\)", l).group(1)) for l in it if l.startswith("s_waitcnt") and "vmcnt" in l)
+        waits_before = sorted(int(re.search(r"vmcnt\((\d+)\)", l).group(1)) for l in it[:bar] if l.startswith("s_waitcnt") and "vmcnt" in l)
+        if waits_before != [0, 0, 4, 5, 8, 10]:
+            probs.append("vmcnt waits before the barrier %s, expected the counted 10 / 5 / 0 and 8 / 4 / 0" % waits_before)
+        if waits != waits_before:
+            probs.append("vmcnt waits after the barrier: %s" % [w for w in waits if w not in waits_before or waits.count(w) > waits_before.count(w)])
+        early = [l for l in it[:bar] if l.startswith("ds_read")]
+        if early:
+            probs.append("LDS read between the loop head and the barrier: %s" % early[0])
+        reads = [l for l in it[bar + 1:] if l.startswith("ds_read")]
+        if len(reads) != 14 or any(not l.startswith("ds_read_b128") for l in reads):
+            probs.append("%d LDS reads after the barrier (%s), expected 14 ds_read_b128" % (len(reads), sorted({l.split()[0] for l in reads})))
+        vmem = [l for l in it if re.match(r"(global|buffer|flat|scratch)_", l)]
+        other = [l for l in vmem if not l.startswith("global_load_lds_dwordx4")]
+        if other:
+            probs.append("vector-memory instruction other than an LDS-DMA piece: %s" % other[0])
+        if len(vmem) != 5:
+            probs.append("%d LDS-DMA pieces in the loop, expected a stage's 5" % len(vmem))
+    return out
+
+
 def main():
     defines = [a for a in sys.argv[1:] if a.startswith("-D")]
     sig_for = [sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == "--sig"]
