@@ -342,6 +342,33 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
 int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
                     const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
                     int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, void* stream);
+/* One decode step of beam sampling (generate(do_sample=True, num_beams > 1): transformers 3.0.2 _generate_beam_search, sampling
+ * branch, reached from the reference's --num_beams with --do_sample, src/generation.py:22-32), two launches, stateless
+ * like kmb_beam_step.  Per row r = b * num_beams + j of logits [B * num_beams, ld] (fp32, V real columns, NaN read as -inf):
+ * s = log_softmax(row), s[ban_token] = -inf after the normalisation (-1: none; the min_length EOS ban), s += add[r] (NULL: 0),
+ * s /= temperature (correctly rounded, skipped at 1); top_k > 0: remove s < the min(max(top_k, 2), V)-th largest score (ties
+ * stay); top_p < 1: ranked by (score descending, index ascending), keep the first three and every token whose softmax mass
+ * ranked before it is <= top_p.  Per batch item, k = 2 * num_beams draws without replacement over its num_beams * V filtered
+ * scores -- torch.multinomial(softmax, k): the k largest s - log(noise), noise [B, ld_noise] fp32 Exp(1) draws supplied by the
+ * caller (column j * V + token, read at kept tokens only), exact ties to the lower column -- sorted by score descending (ties
+ * keep the draw order) into out [B, k, 2] int32 {score bits, j * V + token} (kmb_beam_step's layout); next_scores /
+ * next_tokens / next_beam_idx [B * num_beams]: the first num_beams of them whose token is not eos_token (-1: none), as
+ * kmb_beam_merge_select.  Needs k == 2 * num_beams <= 16, 1 <= V <= 65536, ld >= V, ld_noise >= num_beams * V,
+ * 0 < temperature, 0 < top_p <= 1 and scratch of kmb_beam_sample_scratch(B * num_beams) floats (device; each row's draws
+ * between the two launches, a per-row stage and a per-item merge); fails with a message and launches nothing otherwise.
+ * Deterministic: integer atomics only. */
+int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beams, const float* add, float temperature, int top_k,
+                         float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
+                         float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, float* scratch, int64_t scratch_floats,
+                         void* stream);
+int64_t kmb_beam_sample_scratch(int rows);
+/* The decode loop's form of kmb_beam_sample_step on the logits the last kmb_gen_step wrote (V and B are the handle's), with
+ * kmb_gen_beam_step's reorder_step contract: reorder_step >= 0 also reorders the caches by next_beam_idx in the same launch and
+ * usually embeds next_tokens for step reorder_step + 1 (kmb_gen_embedded_step tells; kmb_gen_step(h, NULL, ...) uses them). */
+int kmb_gen_beam_sample_step(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, float temperature, int top_k,
+                             float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
+                             float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, float* scratch, int64_t scratch_floats,
+                             int reorder_step, void* stream);
 int64_t kmb_gen_workspace_bytes(const kmb_handle* h, int B, int S, int num_beams, int max_length, int n_features);
 
 /* Data-parallel runs share the GPU between the GEMMs and RCCL's all-reduce kernel (reference: torch DDP's NCCL streams,

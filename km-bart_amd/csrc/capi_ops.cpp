@@ -6,6 +6,7 @@
 
 #include "kernels.h"
 #include "sample.h"
+#include "beam_sample.h"
 
 extern "C" const char* kmb_last_error(void);
 int kmb_set_error(const char* msg);  // engine.cpp
@@ -237,4 +238,43 @@ int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature
                  "sample_step");
 }
 
+int64_t kmb_beam_sample_scratch(int rows) { return (int64_t)kmb_beam_sample_scratch_floats(rows); }
+int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beams, const float* add, float temperature, int top_k,
+                         float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
+                         float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, float* scratch, int64_t scratch_floats,
+                         void* stream) {
+  if (kmb_beam_sample_validate("kmb_beam_sample_step", logits, ld, V, B, num_beams, temperature, top_k, top_p, ban_token, noise,
+                               ld_noise, k, out, eos_token, next_scores, next_tokens, next_beam_idx, scratch, scratch_floats) != 0)
+    return -1;
+  return hipfail(kmb_beam_sample_step_launch(logits, ld, V, B, num_beams, add, temperature, top_k, top_p, ban_token, noise, ld_noise,
+                                             k, out, eos_token, next_scores, next_tokens, next_beam_idx, scratch, (size_t)scratch_floats,
+                                             (hipStream_t)stream),
+                 "beam_sample_step");
+}
+
 }  // extern "C"
+
+// The argument checks of kmb_beam_sample_step and kmb_gen_beam_sample_step (`who` names the caller in the message).
+int kmb_beam_sample_validate(const char* who, const float* logits, int ld, int V, int B, int num_beams, float temperature, int top_k,
+                             float top_p, int ban_token, const float* noise, int ld_noise, int k, const int32_t* out, int eos_token,
+                             const float* next_scores, const int64_t* next_tokens, const int32_t* next_beam_idx, const float* scratch,
+                             int64_t scratch_floats) {
+  char buf[256];
+  auto bad = [&](const char* what) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return kmb_set_error(buf);
+  };
+  if (!logits || !noise || !out || !next_scores || !next_tokens || !next_beam_idx || !scratch)
+    return bad("logits, noise, out, next_scores, next_tokens, next_beam_idx and scratch are required");
+  if (num_beams < 1 || k != 2 * num_beams || k > KMB_BEAM_SAMPLE_MAX_K) return bad("need k == 2 * num_beams <= 16");
+  if (V < 1 || V > KMB_BEAM_SAMPLE_MAX_V || B < 0 || ld < V || ld_noise < num_beams * V)
+    return bad("need 1 <= V <= 65536, B >= 0, ld >= V, ld_noise >= num_beams * V");
+  if (scratch_floats < 0 || (size_t)scratch_floats < kmb_beam_sample_scratch_floats(B * num_beams))
+    return bad("scratch needs kmb_beam_sample_scratch(B * num_beams) floats");
+  if (!(temperature > 0.f) || std::isinf(temperature)) return bad("temperature must be finite and > 0");
+  if (top_k < 0) return bad("top_k must be >= 0");
+  if (!(top_p > 0.f && top_p <= 1.f)) return bad("top_p must lie in (0, 1]");
+  if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
+  if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
+  return 0;
+}

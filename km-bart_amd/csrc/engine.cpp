@@ -17,6 +17,7 @@
 
 #include <rccl/rccl.h>
 #include "kernels.h"
+#include "beam_sample.h"
 #include "diag.h"
 
 namespace {
@@ -2340,6 +2341,46 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
 
 int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream);
 
+// What a beam step of the decode loop folds into its launch (kmb_gen_beam_step, kmb_gen_beam_sample_step): the history-index reorder
+// (fold) and the next step's embedding (embed).
+static void gen_fold_plan(kmb_handle* h, int reorder_step, bool& fold, KmbHistGather& hg, bool& embed, KmbEmbedNext& en) {
+  auto& G = h->gen;
+  fold = reorder_step >= 0 && G.use_hist;
+  hg = KmbHistGather{G.hist[G.hcur], G.hist[G.hcur ^ 1], G.Tmax, reorder_step + 1};
+  // a reorder means another decode step follows, at position reorder_step + 1, on the tokens chosen here: the same launch embeds them
+  // (G.x0 is free: the step's layers have run).  KMB_GEN_FOLD_EMBED=0: kmb_gen_step's own embedding launch, as before round 6.
+  const char* fe_env = getenv("KMB_GEN_FOLD_EMBED");
+  const int d = h->d;
+  // ... not when x0 still holds the step's final decoder states (the launch-per-operation path swaps x0 / x1 once per layer, so an even
+  // number of layers ends there): kmb_gen_last_hidden must keep returning them; the next kmb_gen_step embeds then
+  embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && !(fe_env && fe_env[0] == '0') && (d & 7) == 0 && d > 512 && d <= 1024 &&
+                     G.last_x != G.x0;
+  en = KmbEmbedNext{};
+  if (embed) {
+    en.E = h->pf(h->shared); en.prow = h->pf(h->dec_pos) + (size_t)(h->cfg.extra_pos_embeddings + reorder_step + 1) * d;
+    en.gamma = h->pf(h->dec_lne_g); en.beta = h->pf(h->dec_lne_b); en.y = G.x0;
+    en.scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f; en.D = d; en.eps = h->cfg.layer_norm_eps; en.V = h->V;
+  }
+}
+
+// After the beam step's launch: the reorder's state, or the physical reorder (KMB_GEN_HIST=0).
+static int gen_fold_finish(kmb_handle* h, bool fold, bool embed, int reorder_step, const int32_t* next_beam_idx, void* stream) {
+  auto& G = h->gen;
+  hipStream_t s = (hipStream_t)stream;
+  if (embed) G.x0_step = reorder_step + 1;
+  if (fold) {
+    G.hcur ^= 1;
+    if (G.nb == 1) {   // independent rows: the row -> cross-attention item table follows (kmb_gen_reorder)
+      int32_t* other = G.kv_row == G.kv_row_base ? G.kv_row_base + G.R : G.kv_row_base;
+      HIPCHK(kmb_gather_i32_launch(G.kv_row, next_beam_idx, other, G.R, s));
+      G.kv_row = other;
+    }
+  } else if (reorder_step >= 0) {
+    return kmb_gen_reorder(h, next_beam_idx, reorder_step, stream);   // KMB_GEN_HIST=0: the physical reorder
+  }
+  return 0;
+}
+
 // The beam step of the decode loop on the logits of the last kmb_gen_step (mixins.py:386-417 via transformers 3.0.2
 // _generate_beam_search: log_softmax + beam score, the 2 * num_beams best per batch item, the next step's beams): kmb_beam_step's
 // arguments and outputs.  When that step's vocabulary projection left its per-block statistics (all-rows kernel, 257 .. 320 beam rows),
@@ -2355,22 +2396,10 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
   if (!logits || !out || !next_scores || !next_tokens || !next_beam_idx) return fail("kmb_gen_beam_step: missing tensor");
   if (num_beams != G.nb) return fail("kmb_gen_beam_step: num_beams %d, kmb_gen_begin had %d", num_beams, G.nb);
   if (reorder_step >= G.Tmax) return fail("kmb_gen_beam_step: reorder_step %d outside the cache (Tmax=%d)", reorder_step, G.Tmax);
-  const bool fold = reorder_step >= 0 && G.use_hist;
-  KmbHistGather hg{G.hist[G.hcur], G.hist[G.hcur ^ 1], G.Tmax, reorder_step + 1};
-  // a reorder means another decode step follows, at position reorder_step + 1, on the tokens chosen here: the same launch embeds them
-  // (G.x0 is free: the step's layers have run).  KMB_GEN_FOLD_EMBED=0: kmb_gen_step's own embedding launch, as before round 6.
-  const char* fe_env = getenv("KMB_GEN_FOLD_EMBED");
-  const int d = h->d;
-  // ... not when x0 still holds the step's final decoder states (the launch-per-operation path swaps x0 / x1 once per layer, so an even
-  // number of layers ends there): kmb_gen_last_hidden must keep returning them; the next kmb_gen_step embeds then
-  const bool embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && !(fe_env && fe_env[0] == '0') && (d & 7) == 0 && d > 512 && d <= 1024 &&
-                     G.last_x != G.x0;
+  bool fold, embed;
+  KmbHistGather hg;
   KmbEmbedNext en;
-  if (embed) {
-    en.E = h->pf(h->shared); en.prow = h->pf(h->dec_pos) + (size_t)(h->cfg.extra_pos_embeddings + reorder_step + 1) * d;
-    en.gamma = h->pf(h->dec_lne_g); en.beta = h->pf(h->dec_lne_b); en.y = G.x0;
-    en.scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f; en.D = d; en.eps = h->cfg.layer_norm_eps; en.V = h->V;
-  }
+  gen_fold_plan(h, reorder_step, fold, hg, embed, en);
   G.x0_step = -1;
   hipError_t e = hipErrorNotSupported;
   if (force_token < 0 && G.head_stats_blocks > 0 && G.head_stats_for == logits)
@@ -2383,18 +2412,32 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
                              embed ? &en : nullptr);
   if (e == hipErrorNotSupported) return fail("kmb_gen_beam_step: unsupported shape (k <= 16, num_beams <= 16, num_beams * k <= 256)");
   HIPCHK(e);
-  if (embed) G.x0_step = reorder_step + 1;
-  if (fold) {
-    G.hcur ^= 1;
-    if (G.nb == 1) {   // independent rows: the row -> cross-attention item table follows (kmb_gen_reorder)
-      int32_t* other = G.kv_row == G.kv_row_base ? G.kv_row_base + G.R : G.kv_row_base;
-      HIPCHK(kmb_gather_i32_launch(G.kv_row, next_beam_idx, other, G.R, s));
-      G.kv_row = other;
-    }
-  } else if (reorder_step >= 0) {
-    return kmb_gen_reorder(h, next_beam_idx, reorder_step, stream);   // KMB_GEN_HIST=0: the physical reorder
-  }
-  return 0;
+  return gen_fold_finish(h, fold, embed, reorder_step, next_beam_idx, stream);
+}
+
+// The beam-sampling step of the decode loop (kmb_beam_sample_step on the logits of the last kmb_gen_step), with kmb_gen_beam_step's
+// reorder / embedding contract.  The sampling filter needs every logit of the row: the projection's statistics are not used.
+int kmb_gen_beam_sample_step(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, float temperature, int top_k,
+                             float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
+                             float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, float* scratch, int64_t scratch_floats,
+                             int reorder_step, void* stream) {
+  auto& G = h->gen;
+  if (!G.active) return fail("kmb_gen_beam_sample_step: call kmb_gen_begin first");
+  if (num_beams != G.nb) return fail("kmb_gen_beam_sample_step: num_beams %d, kmb_gen_begin had %d", num_beams, G.nb);
+  if (reorder_step >= G.Tmax) return fail("kmb_gen_beam_sample_step: reorder_step %d outside the cache (Tmax=%d)", reorder_step, G.Tmax);
+  // the stateless form's argument checks, before anything is launched or the generation state changes
+  if (kmb_beam_sample_validate("kmb_gen_beam_sample_step", logits, ld, h->V, G.B, num_beams, temperature, top_k, top_p, ban_token,
+                               noise, ld_noise, k, out, eos_token, next_scores, next_tokens, next_beam_idx, scratch, scratch_floats) != 0)
+    return -1;
+  bool fold, embed;
+  KmbHistGather hg;
+  KmbEmbedNext en;
+  gen_fold_plan(h, reorder_step, fold, hg, embed, en);
+  G.x0_step = -1;
+  HIPCHK(kmb_beam_sample_step_launch(logits, ld, h->V, G.B, num_beams, add, temperature, top_k, top_p, ban_token, noise, ld_noise, k,
+                                     out, eos_token, next_scores, next_tokens, next_beam_idx, scratch, (size_t)scratch_floats,
+                                     (hipStream_t)stream, fold ? &hg : nullptr, embed ? &en : nullptr));
+  return gen_fold_finish(h, fold, embed, reorder_step, next_beam_idx, stream);
 }
 
 int kmb_gen_last_hidden(kmb_handle* h, kmb_bf16* out, void* stream) {

@@ -644,6 +644,43 @@ class Engine:
             self.gen_reorder(nidx, reorder_step)
         return cand, nscore, ntok, nidx
 
+    def beam_sample_step(self, logits, num_beams, noise, add=None, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, eos_token=-1,
+                         cand_out=None, reorder_step=-1):
+        """One beam-sampling step (kmb_beam_sample_step): per row log_softmax, EOS ban, + add (the beam scores), / temperature,
+        top-k / top-p; per batch item k = 2 * num_beams draws without replacement on `noise` (fp32 [B, >= num_beams * V] Exp(1)
+        draws), sorted by score, and the next beams (a per-row launch and a per-item merge).  Returns (cand int32 [B, k, 2], next_scores fp32 [R],
+        next_tokens int64 [R], next_beam_idx int32 [R]) like beam_step.  reorder_step >= 0: the call also reorders the
+        generation caches by next_beam_idx (in the same launch when `logits` are gen_step's, unedited)."""
+        R, V = logits.shape[0], int(self.config.vocab_size)
+        B, k = R // num_beams, 2 * num_beams
+        for x in (logits, noise, add):
+            assert x is None or (x.device == self.device and x.dtype == torch.float32 and x.stride(-1) == 1), "beam_sample_step: bad tensor"
+        assert R == B * num_beams and noise.shape[0] == B and (add is None or add.numel() == R)
+        self._folded = None
+        cand = cand_out if cand_out is not None else torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
+        nscore = torch.empty((R,), dtype=torch.float32, device=self.device)
+        ntok = torch.empty((R,), dtype=torch.int64, device=self.device)
+        nidx = torch.empty((R,), dtype=torch.int32, device=self.device)
+        nscr = int(self.lib.kmb_beam_sample_scratch(R))
+        scr = self.__dict__.get("_beam_sample_scratch")
+        if scr is None or scr.numel() < nscr:
+            scr = self._beam_sample_scratch = torch.empty(nscr, dtype=torch.float32, device=self.device)
+        args = (float(temperature), int(top_k), float(top_p), int(ban_token), ptr(noise), noise.stride(0), int(k), ptr(cand),
+                int(eos_token), ptr(nscore), ptr(ntok), ptr(nidx), ptr(scr), scr.numel())
+        if logits is self.__dict__.get("_gen_logits") and logits._version == self._gen_logits_version:
+            with torch.cuda.device(self.device):
+                check(self.lib.kmb_gen_beam_sample_step(self.h, ptr(logits), logits.stride(0), int(num_beams), ptr(add), *args,
+                                                        int(reorder_step), _stream()))
+                self._keep_idx = nidx
+                if reorder_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == reorder_step + 1:
+                    self._folded = (ntok, ntok._version, reorder_step + 1)
+            return cand, nscore, ntok, nidx
+        with torch.cuda.device(self.device):
+            check(self.lib.kmb_beam_sample_step(ptr(logits), logits.stride(0), V, B, int(num_beams), ptr(add), *args, _stream()))
+        if reorder_step >= 0:
+            self.gen_reorder(nidx, reorder_step)
+        return cand, nscore, ntok, nidx
+
     def sample_step(self, logits, noise, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, unfinished=None, pad_token=0,
                     eos_token=-1, next_tokens=None, ids=None, t=0, flag=None, info_out=None):
         """One decode step's sampling tail (kmb_sample_step): EOS ban, temperature, top-k, top-p and the exponential-race

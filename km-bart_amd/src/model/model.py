@@ -765,9 +765,14 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                 assert n_sent == num_beams, "Beam should always be full"
             return new_scores, new_tokens, new_idx
 
-        host_loop = do_sample or processors_on or fp32
+        # beam sampling on the device (kmb_beam_sample_step): the same pipelined loop; the noise of torch.multinomial's
+        # exponential race is drawn here, [B, num_beams * V] on the default generator as the torch path draws it
+        device_beam_sampling = (do_sample and not processors_on and not fp32 and getattr(self, "_sampler", None) is None
+                                and getattr(self, "_device_sampling", True) and 2 * num_beams <= 16 and V <= 65536)
+        host_loop = (do_sample and not device_beam_sampling) or processors_on or fp32
         if not host_loop:
-            # Greedy beam search, pipelined: the device picks the next step's beams itself (kmb_beam_merge_select: the
+            # Greedy beam search and beam sampling, pipelined: the device picks the next step's beams itself (kmb_beam_merge_select /
+            # kmb_beam_sample_step: the
             # first num_beams non-EOS candidates, exactly what the bookkeeping below sends on), so step t+1 is enqueued
             # before the host has seen step t.  The host replays the reference's bookkeeping one step behind from the
             # candidates (one small pinned copy per step): hypotheses, `done`, and the decision to stop -- a stop costs
@@ -777,6 +782,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             beam_scores_dev = torch.full((B, num_beams), -1e9, dtype=torch.float32, device=dev)   # = beam_scores, built on the device
             beam_scores_dev[:, 0] = 0.0
             beam_scores_dev = beam_scores_dev.view(-1)
+            if do_sample:
+                beam_scores_dev.zero_()
+                noise = torch.empty((B, num_beams * V), dtype=torch.float32, device=dev)
             pending = None
 
             def replay(item):
@@ -796,24 +804,32 @@ class MultiModalBartForConditionalGeneration(nn.Module):
 
             while cur_len < max_length:
                 ban = eos if (eos >= 0 and cur_len < min_length) else -1
-                force = -1
-                if cur_len == 1:
-                    force = cfg.bos_token_id          # adjust_logits_during_generation, mixins.py:400-405
                 last = cur_len == max_length - 1
-                if last and eos_token_id is not None:
-                    force = eos_token_id
-                # A forced step's scores are 0 at the forced token and -inf elsewhere whatever the model says
-                # (log_softmax of a row with one finite entry): the vocabulary projection is skipped, and on the LAST
-                # step, whose keys / values nobody will read, the decoder as well.
-                if force >= 0 and last:
-                    logits = eng._gen_logits
+                if do_sample:   # no forced tokens in the sampling branch; a stop found one step late has drawn that step's noise
+                    logits = eng.gen_step(last_tokens, cur_len - 1)
+                    noise.exponential_(1)
+                    cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_sample_step(
+                        logits, num_beams, noise, add=beam_scores_dev, temperature=temperature, top_k=top_k, top_p=top_p,
+                        ban_token=ban, eos_token=eos, cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
                 else:
-                    logits = eng.gen_step(last_tokens, cur_len - 1, want_logits=force < 0)
-                # the candidates land in the page-locked staging buffer straight from the kernel (no copy launch per step)
-                # ... and _reorder_cache (mixins.py:419-434) by the same call: the launch that picks the beams permutes the history index
-                cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step(
-                    logits, num_beams, k, beam_scores_dev, force_token=force, ban_token=ban, eos_token=eos,
-                    cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
+                    force = -1
+                    if cur_len == 1:
+                        force = cfg.bos_token_id          # adjust_logits_during_generation, mixins.py:400-405
+                    if last and eos_token_id is not None:
+                        force = eos_token_id
+                    # A forced step's scores are 0 at the forced token and -inf elsewhere whatever the model says
+                    # (log_softmax of a row with one finite entry): the vocabulary projection is skipped, and on the LAST
+                    # step, whose keys / values nobody will read, the decoder as well.
+                    if force >= 0 and last:
+                        logits = eng._gen_logits
+                    else:
+                        logits = eng.gen_step(last_tokens, cur_len - 1, want_logits=force < 0)
+                    # the candidates land in the page-locked staging buffer straight from the kernel (no copy launch per step)
+                    # ... and _reorder_cache (mixins.py:419-434) by the same call: the launch that picks the beams permutes the
+                    # history index
+                    cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step(
+                        logits, num_beams, k, beam_scores_dev, force_token=force, ban_token=ban, eos_token=eos,
+                        cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
                 ev = torch.cuda.Event()
                 ev.record()
                 if pending is not None and replay(pending):

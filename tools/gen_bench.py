@@ -3,10 +3,10 @@ cross-attention K/V computed once per batch item.  Prints one JSON line.
 
     python tools/gen_bench.py [--batch 64] [--beams 5] [--max-length 20] [--reps 5]
 
---do-sample with --beams 1 times sampled generation (the reference's nucleus sampling, batch x --num-gen rows): the device
-sampler (kmb_sample_step) and, unless --no-host, the torch path (model._device_sampling = False) alternated in one
-process, each generate timed to a device synchronise; one JSON line per path, the first row of each seeded output shared
-between them.  --host-sampling times the torch path alone.
+--do-sample times sampled generation (batch x --num-gen rows): with --beams 1 the reference's nucleus sampling on the device
+sampler (kmb_sample_step), with --beams N > 1 beam sampling on kmb_beam_sample_step; unless --no-host, the torch host loop
+(model._device_sampling = False) is alternated with it in one process, each generate timed to a device synchronise; one JSON
+line per path, the first row of each seeded output shared between them.  --host-sampling times the torch path alone.
 """
 import argparse
 import json
