@@ -270,7 +270,7 @@ int kmb_gen_encoder_states(kmb_handle* h, kmb_bf16* enc_out, void* stream);
  * embedded (no embedding launch); fails when no such embedding is pending for `step` (kmb_gen_embedded_step). */
 int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_out, void* stream);
 /* the step whose tokens the last kmb_gen_beam_step embedded for a kmb_gen_step(tokens = NULL), or -1: none pending (any
- * kmb_gen_step or kmb_gen_beam_step since, or that beam step did not embed -- KMB_GEN_FOLD_EMBED=0, no reorder, or the
+ * kmb_gen_step or kmb_gen_beam_step since, or that beam step did not embed -- no reorder, no next step inside max_length, or the
  * decoder states kmb_gen_last_hidden returns still lived where the embedding goes).  Host state only: no stream work. */
 int kmb_gen_embedded_step(const kmb_handle* h);
 /* the number of 256-column blocks of (maximum, sum-exp) statistics the last kmb_gen_step's vocabulary projection left for `logits` (the
@@ -278,7 +278,8 @@ int kmb_gen_embedded_step(const kmb_handle* h);
  * logits.  While it is > 0, kmb_gen_beam_step on those logits without a forced token selects from the statistics in one launch.  Host state
  * only: no stream work. */
 int kmb_gen_stats_blocks(const kmb_handle* h, const float* logits);
-/* _reorder_cache (src/model/mixins.py:419-434): self-attention caches follow beam_idx [B*num_beams] */
+/* _reorder_cache (src/model/mixins.py:419-434): self-attention caches follow beam_idx [B*num_beams] -- through their history
+ * index (KmbAttnDecode.hist), which one launch permutes; the caches themselves are never copied */
 int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream);
 /* The final decoder states of the last kmb_gen_step as bf16 [rows, d_model] (the `decoder_outputs[0]` of a cached bare-model
  * forward, reference src/model/model.py:87-103 with use_cache; transformers 3.0.2 BartDecoder returns the one new position). */

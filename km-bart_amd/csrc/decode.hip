@@ -49,18 +49,8 @@ extern "C" int kmb_debug_set_decode_stamps(void* p) {
     if (g_dec_stamps != nullptr && threadIdx.x == 0)                                                         \
       g_dec_stamps[((size_t)(type) * 4096 + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memrealtime();       \
   } while (0)
-// the resident decoder-layers kernel: 32 slots per workgroup, layer KMB_DL_STAMP_LAYER of the launch (tools/decode_resident_stamps.py)
-#ifndef KMB_DL_STAMP_LAYER
-#define KMB_DL_STAMP_LAYER 1
-#endif
-#define DLSTAMP(i)                                                                                           \
-  do {                                                                                                       \
-    if (g_dec_stamps != nullptr && threadIdx.x == 0 && l == KMB_DL_STAMP_LAYER)                              \
-      g_dec_stamps[(size_t)blockIdx.x * 32 + (i)] = __builtin_amdgcn_s_memrealtime();                        \
-  } while (0)
 #else
 #define DSTAMP(type, i)
-#define DLSTAMP(i)
 #endif
 
 #ifndef KMB_DEC_SELF_VU
@@ -755,12 +745,6 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const KmbDecodeBlock p
   DSTAMP(stype, 6);
 }
 
-// (The resident decoder-layers kernel of round 5 -- all layers of a decode step in one launch behind 12-workgroup counter barriers, bit-identical to
-//  the blocks above and 17 % slower -- lives in tools/experiments/decode_resident.hip since round 6: `python km-bart_amd/build.py --variant resident`
-//  builds a library with it, KMB_GEN_FUSED=2 selects it there.  That file includes this one for the device helpers above.)
-#ifdef KMB_DECODE_DEVICE_ONLY
-}  // namespace
-#else
 template <typename F>
 hipError_t set_lds(F* fn, size_t lds) {
   return hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -854,5 +838,3 @@ hipError_t kmb_decode_pack_launch(const bf16_t* const* W, const int* ld, const i
   hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
-
-#endif  // KMB_DECODE_DEVICE_ONLY

@@ -175,8 +175,7 @@ struct kmb_handle {
     bool active = false; int B = 0, S = 0, nb = 0, R = 0, Tmax = 0;
     kmb_batch bt{};
     std::vector<bf16_t*> ckv;              // per layer [B*S, 2d]
-    std::vector<bf16_t*> kc[2], vc[2];     // per layer self caches, double buffered [R, Tmax, d]
-    int cur = 0;
+    std::vector<bf16_t*> kc, vc;           // per layer self caches [R, Tmax, d], addressed through the history index below
     int32_t *kv_row = nullptr;             // [R] -> batch item (the current one of the two copies at kv_row_base)
     int32_t *kv_row_base = nullptr;
     bf16_t *x0, *x1, *qkv, *o, *z, *y, *cq, *u, *hh; float *mean, *rstd; float* slab;
@@ -184,12 +183,10 @@ struct kmb_handle {
     // the last kmb_gen_step's final decoder states: normalised rows at last_x, or (fused blocks, no vocabulary projection)
     // pre-LayerNorm sums at last_z with the last layer's LayerNorm (last_g, last_b) still to be applied
     const bf16_t* last_x = nullptr; const bf16_t* last_z = nullptr; const float *last_g = nullptr, *last_b = nullptr;
-    uint32_t* bars = nullptr;
     // History index of the self-attention caches (round 5): position t of beam row r lives in cache row hist[r][t].  A beam reorder
     // (mixins.py:419-434 _reorder_cache) permutes these [R, Tmax] int rows into the other copy instead of gathering every layer's
-    // K and V cache ([R, t, d] x 12 buffers: 5-40 us per decode step at batch 64 x 5 beams); the caches are never copied
-    // (kc[0] / vc[0] only).  KMB_GEN_HIST=0 restores the physical reorder.
-    int32_t* hist[2] = {nullptr, nullptr}; int hcur = 0; bool use_hist = true;
+    // K and V cache ([R, t, d] x 12 buffers: 5-40 us per decode step at batch 64 x 5 beams); the caches are never copied.
+    int32_t* hist[2] = {nullptr, nullptr}; int hcur = 0;
     // per-block (maximum, sum-exp) pairs the last kmb_gen_step's vocabulary projection left beside the logits at head_stats_for
     // (head_stats_blocks column blocks; 0: none -- the step ran another GEMM kernel, or no projection): kmb_gen_beam_step selects from them
     float* head_stats = nullptr; int head_stats_blocks = 0; const float* head_stats_for = nullptr;
@@ -1998,16 +1995,15 @@ int kmb_comm_gather_moments(kmb_handle* h, void* compute_stream) {
 // ================================================================================= generation
 namespace {
 
-struct GenLayout {   // (every pointer starts null: the product build leaves `bars` unset, and kmb_gen_begin copies it)
+struct GenLayout {   // (every pointer starts null)
   int32_t* status = nullptr; bf16_t* xf = nullptr; float* img_emb = nullptr; int32_t* img_src = nullptr;
   bf16_t* xe[2] = {nullptr, nullptr}; EncAct ea{};
-  std::vector<bf16_t*> ckv, kc[2], vc[2];
+  std::vector<bf16_t*> ckv, kc, vc;
   int32_t* kv_row = nullptr;
   bf16_t *x0 = nullptr, *x1 = nullptr, *qkv = nullptr, *o = nullptr, *z = nullptr, *y = nullptr, *cq = nullptr, *u = nullptr, *hh = nullptr;
   float *mean = nullptr, *rstd = nullptr;
   float* slab = nullptr;   // split-K partial sums of the residual projections of a decode step
   std::vector<bf16_t*> wp;   // per layer: self q|k|v, self out, cross q, cross out, fc1, fc2 in fragment order (decode.hip)
-  uint32_t* bars = nullptr;  // group-barrier counters of the resident decoder-layers kernel (decode.hip)
   int32_t* hist[2] = {nullptr, nullptr};   // history index of the self-attention caches [R, Tmax], ping-pong over beam reorders
   float* head_stats = nullptr;   // the all-rows vocabulary projection's per-block (maximum, sum-exp) pairs (kmb_gen_beam_step)
 };
@@ -2035,11 +2031,11 @@ size_t layout_gen(const kmb_handle* h, char* base, size_t cap, int B, int S, int
   a.z2 = bp.act(Me * d); a.lse = bp.take<float>((size_t)B * h->He * S);
   a.m1 = bp.take<float>(Me); a.r1 = bp.take<float>(Me); a.m2 = bp.take<float>(Me); a.r2 = bp.take<float>(Me);
   g.ckv.resize(Ld);
-  for (int i = 0; i < 2; ++i) { g.kc[i].resize(Ld); g.vc[i].resize(Ld); }
+  g.kc.resize(Ld); g.vc.resize(Ld);
   bf16_t* ckv_all = bp.act(Me * (size_t)Ld * 2 * d);   // [Me, Ld * 2d]: layer l's cross-attention k | v are columns [l * 2d, (l + 1) * 2d)
   for (int l = 0; l < Ld; ++l) {
     g.ckv[l] = ckv_all + (size_t)l * 2 * d;
-    for (int i = 0; i < 2; ++i) { g.kc[i][l] = bp.act(R * Tmax * d); g.vc[i][l] = bp.act(R * Tmax * d); }
+    g.kc[l] = bp.act(R * Tmax * d); g.vc[l] = bp.act(R * Tmax * d);
   }
   g.kv_row = bp.take<int32_t>(2 * R);   // two copies: a reorder of independent rows (num_beams == 1) gathers it into the other one
   g.x0 = bp.act(R * d); g.x1 = bp.act(R * d); g.qkv = bp.act(R * 3 * d);
@@ -2053,9 +2049,6 @@ size_t layout_gen(const kmb_handle* h, char* base, size_t cap, int B, int S, int
     for (int l = 0; l < Ld; ++l)
       for (int i = 0; i < 6; ++i) g.wp.push_back(bp.act(sizes[i]));
   }
-#ifdef KMB_WITH_RESIDENT_DECODE   // experiment build only (tools/experiments/decode_resident.hip): the group-barrier counters
-  g.bars = bp.take<uint32_t>(kmb_decode_layers_bar_words((int)R, Ld > 0 ? Ld : 1) + 64);
-#endif
   g.hist[0] = bp.take<int32_t>(R * Tmax); g.hist[1] = bp.take<int32_t>(R * Tmax);
   g.head_stats = bp.take<float>(kmb_gemm_allrows_stats_floats(h->V));
   if (out) *out = g;
@@ -2094,16 +2087,14 @@ int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_
   KCHK(encoder_forward(h, bt, false, s));
   const bf16_t* enc = h->xe[Le];
   auto& G = h->gen;
-  G.active = true; G.B = B; G.S = S; G.nb = num_beams; G.R = B * num_beams; G.Tmax = max_length; G.bt = bt; G.cur = 0;
-  G.ckv = g.ckv; G.kc[0] = g.kc[0]; G.kc[1] = g.kc[1]; G.vc[0] = g.vc[0]; G.vc[1] = g.vc[1];
+  G.active = true; G.B = B; G.S = S; G.nb = num_beams; G.R = B * num_beams; G.Tmax = max_length; G.bt = bt;
+  G.ckv = g.ckv; G.kc = g.kc; G.vc = g.vc;
   G.kv_row = g.kv_row; G.kv_row_base = g.kv_row; G.x0 = g.x0; G.x1 = g.x1; G.qkv = g.qkv; G.o = g.o; G.z = g.z; G.y = g.y; G.cq = g.cq;
   G.u = g.u; G.hh = g.hh; G.mean = g.mean; G.rstd = g.rstd; G.slab = g.slab; G.wp = g.wp;
   G.last_x = nullptr; G.last_z = nullptr; G.last_g = nullptr; G.last_b = nullptr;
-  G.bars = g.bars;
   G.hist[0] = g.hist[0]; G.hist[1] = g.hist[1]; G.hcur = 0;
   G.head_stats = g.head_stats; G.head_stats_blocks = 0; G.head_stats_for = nullptr;
   G.x0_step = -1;
-  { const char* he = getenv("KMB_GEN_HIST"); G.use_hist = !(he && he[0] == '0'); }
   // cross-attention K|V of every decoder layer, computed once per batch item (not per beam), all layers in ONE GEMM
   if (Ld > 0) {
     KmbGemm gm = lin_fwd(enc, d, h->wb(h->xkv_w), h->pf(h->xkv_b), Me, Ld * 2 * d, d);
@@ -2206,60 +2197,14 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
       HIPCHK(kmb_decode_block_launch(b, s));
       return 0;
     };
-#ifdef KMB_WITH_RESIDENT_DECODE
-    // Resident form (tools/experiments/decode_resident.hip, round 5; experiment build `build.py --variant resident`, KMB_GEN_FUSED=2): ALL the layers in one launch
-    // (KMB_GEN_LAYERS of them per launch), twelve co-resident workgroups per row tile behind counter barriers.  Bit-identical to the
-    // six-launches-per-layer blocks and MEASURED SLOWER than them (12.0 against 10.3 ms per generate at batch 64 x 5 beams: an
-    // in-kernel hand-off costs ~3.5 us where a kernel boundary costs ~1.7, and what a layer streams is bound by the CU's request
-    // rate either way -- DESIGN.md section 4 "Generation", round 5; profiles/r05_generation_resident_kernel_stamps.md), so it is
-    // opt-in; the blocks stay the default.
-    const int Ld = h->cfg.decoder_layers;
-    bool resident = fused_env && fused_env[0] == '2' && Ld > 0;
-    KmbDecodeLayers A;
-    if (resident) {
-      memset(&A, 0, sizeof(A));
-      A.n_layers = 1; A.x_in = G.x0; A.o = G.o; A.z = G.z; A.hh = G.hh; A.bars = G.bars; A.status = h->status;
-      A.R = R; A.F = F; A.H = h->Hd; A.Tmax = G.Tmax; A.Tk = step + 1; A.S = G.S; A.ldc = Ld * 2 * d; A.kv_group = G.nb;
-      A.key_mask = G.bt.attention_mask; A.mask_ld = G.S; A.eps = eps; A.q_scale = 0.125f;
-      A.hist = G.use_hist ? G.hist[G.hcur] : nullptr;
-      if (kmb_decode_layers_check(A) != nullptr) resident = false;
-    }
-    if (resident) {
-      const char* lenv = getenv("KMB_GEN_LAYERS");
-      int per = lenv && atoi(lenv) > 0 ? atoi(lenv) : Ld;
-      if (per > KMB_DL_MAX_LAYERS) per = KMB_DL_MAX_LAYERS;
-      for (int l0 = 0; l0 < Ld; l0 += per) {
-        const int n = std::min(per, Ld - l0);
-        A.n_layers = n;
-        A.x_in = l0 == 0 ? G.x0 : G.z;
-        for (int i = 0; i < n; ++i) {
-          const int l = l0 + i;
-          const LayerP& L = h->dec[l];
-          KmbDecodeLayerP& P = A.L[i];
-          P.Wqkv = G.wp[(size_t)l * 6 + 0]; P.Wo = G.wp[(size_t)l * 6 + 1]; P.Wcq = G.wp[(size_t)l * 6 + 2];
-          P.Wco = G.wp[(size_t)l * 6 + 3]; P.W1 = G.wp[(size_t)l * 6 + 4]; P.W2 = G.wp[(size_t)l * 6 + 5];
-          P.bqkv = h->pf(L.sa.qkv_b); P.bo = h->pf(L.sa.o_b); P.bcq = h->pf(L.ca.qkv_b); P.bco = h->pf(L.ca.o_b);
-          P.b1 = h->pf(L.fc1_b); P.b2 = h->pf(L.fc2_b);
-          P.lnin_g = l == 0 ? nullptr : h->pf(h->dec[l - 1].ln_g); P.lnin_b = l == 0 ? nullptr : h->pf(h->dec[l - 1].ln_b);
-          P.ln1_g = h->pf(L.sa.ln_g); P.ln1_b = h->pf(L.sa.ln_b); P.ln2_g = h->pf(L.ca.ln_g); P.ln2_b = h->pf(L.ca.ln_b);
-          P.Kc = G.kc[G.cur][l]; P.Vc = G.vc[G.cur][l]; P.cK = G.ckv[l]; P.cV = G.ckv[l] + d;
-        }
-        const hipError_t le = kmb_decode_layers_launch(A, s);
-        if (le != hipSuccess) return fail("kmb_gen_step: resident decoder-layers launch failed: %s", hipGetErrorString(le));
-      }
-      zin = G.z; lg = h->pf(h->dec[Ld - 1].ln_g); lb = h->pf(h->dec[Ld - 1].ln_b);
-    }
-#else
-    const bool resident = false;   // (the resident decoder-layers kernel is an experiment build since round 6: measured 17 % slower)
-#endif
-    for (int l = 0; !resident && l < h->cfg.decoder_layers; ++l) {
+    for (int l = 0; l < h->cfg.decoder_layers; ++l) {
       const LayerP& L = h->dec[l];
       KmbDecodeBlock b;
       memset(&b, 0, sizeof(b));
       b.kind = 1; b.in = zin; b.ld_in = d; b.gamma = lg; b.beta = lb; b.eps = eps; b.ln_out = lg ? G.x1 : nullptr;
       b.W = G.wp[(size_t)l * 6 + 0]; b.bias = h->pf(L.sa.qkv_b); b.R = R; b.K = d; b.N = 3 * d; b.out = G.o; b.ld_out = d;
-      b.H = h->Hd; b.q_scale = 0.125f; b.Kc = G.kc[G.cur][l]; b.Vc = G.vc[G.cur][l]; b.Tmax = G.Tmax; b.ldc = d; b.Tk = step + 1;
-      b.hist = G.use_hist ? G.hist[G.hcur] : nullptr;
+      b.H = h->Hd; b.q_scale = 0.125f; b.Kc = G.kc[l]; b.Vc = G.vc[l]; b.Tmax = G.Tmax; b.ldc = d; b.Tk = step + 1;
+      b.hist = G.hist[G.hcur];
       KCHK(block(b));
       const bf16_t* xres = lg ? G.x1 : zin;
       memset(&b, 0, sizeof(b));
@@ -2300,11 +2245,11 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
     g.col_scale = 0.125f; g.col_scale_n = d; g.out_bf16 = G.qkv; g.ld_out_bf16 = 3 * d;
     KCHK(run_gemm(g, s));
     KmbAttnDecode a; memset(&a, 0, sizeof(a));
-    a.Q = G.qkv; a.ldq = 3 * d; a.Kc = G.kc[G.cur][l]; a.Vc = G.vc[G.cur][l]; a.Tmax = G.Tmax; a.ldc = d;
+    a.Q = G.qkv; a.ldq = 3 * d; a.Kc = G.kc[l]; a.Vc = G.vc[l]; a.Tmax = G.Tmax; a.ldc = d;
     a.R = R; a.H = h->Hd; a.Tk = step + 1; a.O = G.o; a.ldo = d;
     // this step's key / value: attended to from the projection output and appended to the cache by the same launch
-    a.new_k = G.qkv + d; a.new_v = G.qkv + 2 * d; a.ld_new = 3 * d; a.Kw = G.kc[G.cur][l]; a.Vw = G.vc[G.cur][l];
-    a.hist = G.use_hist ? G.hist[G.hcur] : nullptr;
+    a.new_k = G.qkv + d; a.new_v = G.qkv + 2 * d; a.ld_new = 3 * d; a.Kw = G.kc[l]; a.Vw = G.vc[l];
+    a.hist = G.hist[G.hcur];
     HIPCHK(kmb_attn_decode_launch(a, s));
     KCHK(proj_ln(G.o, d, L.sa.o_w, L.sa.o_b, x, L.sa.ln_g, L.sa.ln_b, G.y));
     // cross attention over the cached encoder K|V of the row's batch item
@@ -2339,22 +2284,33 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
   return 0;
 }
 
-int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream);
+// The generation state after a beam reorder whose history gather is queued: the other history copy is current, and with independent
+// rows (num_beams == 1: the cached forward of src/model/model.py:384-397 with caller-expanded rows) the row -> cross-attention item
+// table follows into its other copy, as _reorder_cache (mixins.py:419-434) permutes the encoder side.  (With num_beams > 1 a beam
+// search only permutes rows inside a batch item and the table is unchanged.)
+static int gen_reordered(kmb_handle* h, const int32_t* beam_idx, hipStream_t s) {
+  auto& G = h->gen;
+  G.hcur ^= 1;
+  if (G.nb == 1) {
+    int32_t* other = G.kv_row == G.kv_row_base ? G.kv_row_base + G.R : G.kv_row_base;
+    HIPCHK(kmb_gather_i32_launch(G.kv_row, beam_idx, other, G.R, s));
+    G.kv_row = other;
+  }
+  return 0;
+}
 
 // What a beam step of the decode loop folds into its launch (kmb_gen_beam_step, kmb_gen_beam_sample_step): the history-index reorder
 // (fold) and the next step's embedding (embed).
 static void gen_fold_plan(kmb_handle* h, int reorder_step, bool& fold, KmbHistGather& hg, bool& embed, KmbEmbedNext& en) {
   auto& G = h->gen;
-  fold = reorder_step >= 0 && G.use_hist;
+  fold = reorder_step >= 0;
   hg = KmbHistGather{G.hist[G.hcur], G.hist[G.hcur ^ 1], G.Tmax, reorder_step + 1};
   // a reorder means another decode step follows, at position reorder_step + 1, on the tokens chosen here: the same launch embeds them
-  // (G.x0 is free: the step's layers have run).  KMB_GEN_FOLD_EMBED=0: kmb_gen_step's own embedding launch, as before round 6.
-  const char* fe_env = getenv("KMB_GEN_FOLD_EMBED");
+  // (G.x0 is free: the step's layers have run)
   const int d = h->d;
   // ... not when x0 still holds the step's final decoder states (the launch-per-operation path swaps x0 / x1 once per layer, so an even
   // number of layers ends there): kmb_gen_last_hidden must keep returning them; the next kmb_gen_step embeds then
-  embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && !(fe_env && fe_env[0] == '0') && (d & 7) == 0 && d > 512 && d <= 1024 &&
-                     G.last_x != G.x0;
+  embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && (d & 7) == 0 && d > 512 && d <= 1024 && G.last_x != G.x0;
   en = KmbEmbedNext{};
   if (embed) {
     en.E = h->pf(h->shared); en.prow = h->pf(h->dec_pos) + (size_t)(h->cfg.extra_pos_embeddings + reorder_step + 1) * d;
@@ -2363,30 +2319,18 @@ static void gen_fold_plan(kmb_handle* h, int reorder_step, bool& fold, KmbHistGa
   }
 }
 
-// After the beam step's launch: the reorder's state, or the physical reorder (KMB_GEN_HIST=0).
+// After the beam step's launch: the state of the reorder and of the embedding it folded in.
 static int gen_fold_finish(kmb_handle* h, bool fold, bool embed, int reorder_step, const int32_t* next_beam_idx, void* stream) {
-  auto& G = h->gen;
-  hipStream_t s = (hipStream_t)stream;
-  if (embed) G.x0_step = reorder_step + 1;
-  if (fold) {
-    G.hcur ^= 1;
-    if (G.nb == 1) {   // independent rows: the row -> cross-attention item table follows (kmb_gen_reorder)
-      int32_t* other = G.kv_row == G.kv_row_base ? G.kv_row_base + G.R : G.kv_row_base;
-      HIPCHK(kmb_gather_i32_launch(G.kv_row, next_beam_idx, other, G.R, s));
-      G.kv_row = other;
-    }
-  } else if (reorder_step >= 0) {
-    return kmb_gen_reorder(h, next_beam_idx, reorder_step, stream);   // KMB_GEN_HIST=0: the physical reorder
-  }
-  return 0;
+  if (embed) h->gen.x0_step = reorder_step + 1;
+  return fold ? gen_reordered(h, next_beam_idx, (hipStream_t)stream) : 0;
 }
 
 // The beam step of the decode loop on the logits of the last kmb_gen_step (mixins.py:386-417 via transformers 3.0.2
 // _generate_beam_search: log_softmax + beam score, the 2 * num_beams best per batch item, the next step's beams): kmb_beam_step's
 // arguments and outputs.  When that step's vocabulary projection left its per-block statistics (all-rows kernel, 257 .. 320 beam rows),
 // ONE launch selects from them; otherwise kmb_beam_step's two launches over the logits.
-// reorder_step >= 0: also kmb_gen_reorder(next_beam_idx, reorder_step) (_reorder_cache, mixins.py:419-434) -- with the history index
-// (the default) by the launch that has just chosen the beams, no launch of its own.
+// reorder_step >= 0: also kmb_gen_reorder(next_beam_idx, reorder_step) (_reorder_cache, mixins.py:419-434), by the launch that has just
+// chosen the beams, no launch of its own.
 int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, int force_token, int ban_token, int k,
                       int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, float* scratch,
                       int64_t scratch_floats, int reorder_step, void* stream) {
@@ -2463,48 +2407,12 @@ int kmb_gen_stats_blocks(const kmb_handle* h, const float* logits) {
   return h && h->gen.active && logits && h->gen.head_stats_for == logits ? h->gen.head_stats_blocks : 0;
 }
 
-int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream) {
+int kmb_gen_reorder(kmb_handle* h, const int32_t* beam_idx, int step, void* stream) {   // permutes the history index, not the caches
   hipStream_t s = (hipStream_t)stream;
   auto& G = h->gen;
   if (!G.active) return fail("kmb_gen_reorder: call kmb_gen_begin first");
-  const int d = h->d;
-  if (G.use_hist) {   // permute the history index, not the caches
-    HIPCHK(kmb_gather_hist_launch(G.hist[G.hcur], beam_idx, G.hist[G.hcur ^ 1], G.R, G.Tmax, step + 1, s));
-    G.hcur ^= 1;
-    if (G.nb == 1) {   // independent rows: the row -> cross-attention item table follows (see below)
-      int32_t* other = G.kv_row == G.kv_row_base ? G.kv_row_base + G.R : G.kv_row_base;
-      HIPCHK(kmb_gather_i32_launch(G.kv_row, beam_idx, other, G.R, s));
-      G.kv_row = other;
-    }
-    return 0;
-  }
-  const int row_bytes = (step + 1) * d * (int)sizeof(bf16_t);
-  const size_t stride = (size_t)G.Tmax * d * sizeof(bf16_t);
-  // every layer's K and V cache in one launch per 16 buffers (12 launches -> 1 for a 6-layer decoder)
-  const void* src[16];
-  void* dst[16];
-  int n = 0;
-  for (int l = 0; l < h->cfg.decoder_layers; ++l) {
-    for (int kv = 0; kv < 2; ++kv) {
-      src[n] = kv ? (const void*)G.vc[G.cur][l] : (const void*)G.kc[G.cur][l];
-      dst[n] = kv ? (void*)G.vc[G.cur ^ 1][l] : (void*)G.kc[G.cur ^ 1][l];
-      if (++n == 16) {
-        HIPCHK(kmb_gather_rows_multi_launch(src, dst, n, beam_idx, G.R, row_bytes, stride, s));
-        n = 0;
-      }
-    }
-  }
-  if (n) HIPCHK(kmb_gather_rows_multi_launch(src, dst, n, beam_idx, G.R, row_bytes, stride, s));
-  G.cur ^= 1;
-  if (G.nb == 1) {
-    // rows are independent sequences (the cached forward of src/model/model.py:384-397 with caller-expanded rows):
-    // _reorder_cache (mixins.py:419-434) also permutes the encoder side, here the row -> cross-attention item table.
-    // (With num_beams > 1 a beam search only permutes rows inside a batch item and the table is unchanged.)
-    int32_t* other = G.kv_row == G.kv_row_base ? G.kv_row_base + G.R : G.kv_row_base;
-    HIPCHK(kmb_gather_i32_launch(G.kv_row, beam_idx, other, G.R, s));
-    G.kv_row = other;
-  }
-  return 0;
+  HIPCHK(kmb_gather_hist_launch(G.hist[G.hcur], beam_idx, G.hist[G.hcur ^ 1], G.R, G.Tmax, step + 1, s));
+  return gen_reordered(h, beam_idx, s);
 }
 
 }  // extern "C"

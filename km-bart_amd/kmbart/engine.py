@@ -353,10 +353,6 @@ class Engine:
         if st & 2:
             raise RuntimeError("a label is neither -100 nor inside [0, number of classes) "
                                "(the reference's CrossEntropyLoss raises on such a target, src/model/model.py:400-402)")
-        if st & 8:
-            raise RuntimeError("a group barrier of the resident decoder-layers kernel gave up (csrc/decode.hip: its workgroups were "
-                               "not all co-resident -- another kernel held CUs?); the generated tokens of this call are invalid. "
-                               "KMB_GEN_FUSED=1 selects the six-launches-per-layer blocks")
 
     def read_status(self):
         """The device status word of the last forward / generation (syncs); bits: _raise_on_status."""
@@ -598,6 +594,36 @@ class Engine:
             cache[key] = torch.empty(shape, dtype=dtype, pin_memory=True)
         return cache[key]
 
+    def _beam_outputs(self, cand_out, B, k, R):
+        """The outputs of a beam step: (cand int32 [B, k, 2], next_scores fp32 [R], next_tokens int64 [R], next_beam_idx int32 [R]).
+        cand_out: a page-locked host tensor [B, k, 2] int32 the kernel writes directly (device-visible host memory: no copy launch
+        between two decode steps); the caller reads it after an event recorded behind the call."""
+        self._folded = None
+        cand = cand_out if cand_out is not None else torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
+        nscore = torch.empty((R,), dtype=torch.float32, device=self.device)
+        ntok = torch.empty((R,), dtype=torch.int64, device=self.device)
+        nidx = torch.empty((R,), dtype=torch.int32, device=self.device)
+        return cand, nscore, ntok, nidx
+
+    def _beam_call(self, logits, outs, reorder_step, gen_call, call, forced=False):
+        """Runs a beam step: gen_call (its kmb_gen_* form: the decode loop's, which may select from the statistics the step's
+        vocabulary projection left and folds the reorder and the next step's embedding into its launch) when `logits` are
+        gen_step's, unedited since (their _version unchanged; a forced step reads none), else `call` (the stateless form)
+        and then gen_reorder.  gen_call None: the stateless form only."""
+        nidx, ntok = outs[3], outs[2]
+        with torch.cuda.device(self.device):
+            if (gen_call is not None and logits is self.__dict__.get("_gen_logits")
+                    and (forced or logits._version == self._gen_logits_version)):
+                check(gen_call())
+                self._keep_idx = nidx
+                if reorder_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == reorder_step + 1:
+                    self._folded = (ntok, ntok._version, reorder_step + 1)
+                return outs
+            check(call())
+        if reorder_step >= 0:
+            self.gen_reorder(nidx, reorder_step)
+        return outs
+
     def beam_step(self, logits, num_beams, k, add, force_token=-1, ban_token=-1, eos_token=-1, cand_out=None, reorder_step=-1):
         """beam_candidates plus the next step's beams chosen on the device (kmb_beam_merge_select): returns
         (cand int32 [B, k, 2], next_scores fp32 [R], next_tokens int64 [R], next_beam_idx int32 [R]); nothing is
@@ -606,43 +632,24 @@ class Engine:
         reorder_step), folded into the beam step's launch when `logits` are gen_step's)."""
         R = logits.shape[0]
         B = R // num_beams
-        self._folded = None
-        # cand_out: a page-locked host tensor [B, k, 2] int32 the kernel writes directly (device-visible host memory: no copy
-        # launch between two decode steps); the caller reads it after an event recorded behind this call
-        cand = cand_out if cand_out is not None else torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
-        nscore = torch.empty((R,), dtype=torch.float32, device=self.device)
-        ntok = torch.empty((R,), dtype=torch.int64, device=self.device)
-        nidx = torch.empty((R,), dtype=torch.int32, device=self.device)
+        outs = cand, nscore, ntok, nidx = self._beam_outputs(cand_out, B, k, R)
         if k <= 16 and num_beams <= 16 and num_beams * k <= 256 and logits.stride(0) % 4 == 0:
             # kmb_beam_step: the rows' top-k lists never leave the workgroup that merges them (one launch less per decode step)
             scr = self._topk_scratch_for(R)
-            if logits is self.__dict__.get("_gen_logits") and (force_token >= 0 or logits._version == self._gen_logits_version):
-                # the decode loop: kmb_gen_beam_step selects from the statistics the step's vocabulary projection left (one launch,
-                # no second pass over the logits) when there are any, and is kmb_beam_step otherwise.  Those statistics describe the
-                # logits as gen_step wrote them: logits edited in place since (their _version moved) take kmb_beam_step below.
-                # (A forced step reads no logits.)
-                with torch.cuda.device(self.device):
-                    check(self.lib.kmb_gen_beam_step(self.h, ptr(logits), logits.stride(0), int(num_beams), ptr(add), int(force_token),
-                                                     int(ban_token), int(k), ptr(cand), int(eos_token), ptr(nscore), ptr(ntok),
-                                                     ptr(nidx), ptr(scr), scr.numel(), int(reorder_step), _stream()))
-                    self._keep_idx = nidx
-                    if reorder_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == reorder_step + 1:
-                        self._folded = (ntok, ntok._version, reorder_step + 1)
-                return cand, nscore, ntok, nidx
-            with torch.cuda.device(self.device):
-                check(self.lib.kmb_beam_step(ptr(logits), logits.stride(0), int(self.config.vocab_size), B, int(num_beams), ptr(add),
-                                             int(force_token), int(ban_token), int(k), ptr(cand), int(eos_token), ptr(nscore),
-                                             ptr(ntok), ptr(nidx), ptr(scr), scr.numel(), _stream()))
-            if reorder_step >= 0:
-                self.gen_reorder(nidx, reorder_step)
-            return cand, nscore, ntok, nidx
+            return self._beam_call(
+                logits, outs, reorder_step,
+                lambda: self.lib.kmb_gen_beam_step(self.h, ptr(logits), logits.stride(0), int(num_beams), ptr(add), int(force_token),
+                                                   int(ban_token), int(k), ptr(cand), int(eos_token), ptr(nscore), ptr(ntok),
+                                                   ptr(nidx), ptr(scr), scr.numel(), int(reorder_step), _stream()),
+                lambda: self.lib.kmb_beam_step(ptr(logits), logits.stride(0), int(self.config.vocab_size), B, int(num_beams), ptr(add),
+                                               int(force_token), int(ban_token), int(k), ptr(cand), int(eos_token), ptr(nscore),
+                                               ptr(ntok), ptr(nidx), ptr(scr), scr.numel(), _stream()),
+                forced=force_token >= 0)
         val, idx = self.logsoftmax_topk(logits, k, add=add, force_token=force_token, ban_token=ban_token)
-        with torch.cuda.device(self.device):
-            check(self.lib.kmb_beam_merge_select(ptr(val), ptr(idx), B, int(num_beams), int(k), int(self.config.vocab_size),
-                                                 ptr(cand), int(eos_token), ptr(nscore), ptr(ntok), ptr(nidx), _stream()))
-        if reorder_step >= 0:
-            self.gen_reorder(nidx, reorder_step)
-        return cand, nscore, ntok, nidx
+        return self._beam_call(
+            logits, outs, reorder_step, None,
+            lambda: self.lib.kmb_beam_merge_select(ptr(val), ptr(idx), B, int(num_beams), int(k), int(self.config.vocab_size),
+                                                   ptr(cand), int(eos_token), ptr(nscore), ptr(ntok), ptr(nidx), _stream()))
 
     def beam_sample_step(self, logits, num_beams, noise, add=None, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, eos_token=-1,
                          cand_out=None, reorder_step=-1):
@@ -656,30 +663,18 @@ class Engine:
         for x in (logits, noise, add):
             assert x is None or (x.device == self.device and x.dtype == torch.float32 and x.stride(-1) == 1), "beam_sample_step: bad tensor"
         assert R == B * num_beams and noise.shape[0] == B and (add is None or add.numel() == R)
-        self._folded = None
-        cand = cand_out if cand_out is not None else torch.empty((B, k, 2), dtype=torch.int32, device=self.device)
-        nscore = torch.empty((R,), dtype=torch.float32, device=self.device)
-        ntok = torch.empty((R,), dtype=torch.int64, device=self.device)
-        nidx = torch.empty((R,), dtype=torch.int32, device=self.device)
+        outs = cand, nscore, ntok, nidx = self._beam_outputs(cand_out, B, k, R)
         nscr = int(self.lib.kmb_beam_sample_scratch(R))
         scr = self.__dict__.get("_beam_sample_scratch")
         if scr is None or scr.numel() < nscr:
             scr = self._beam_sample_scratch = torch.empty(nscr, dtype=torch.float32, device=self.device)
         args = (float(temperature), int(top_k), float(top_p), int(ban_token), ptr(noise), noise.stride(0), int(k), ptr(cand),
                 int(eos_token), ptr(nscore), ptr(ntok), ptr(nidx), ptr(scr), scr.numel())
-        if logits is self.__dict__.get("_gen_logits") and logits._version == self._gen_logits_version:
-            with torch.cuda.device(self.device):
-                check(self.lib.kmb_gen_beam_sample_step(self.h, ptr(logits), logits.stride(0), int(num_beams), ptr(add), *args,
-                                                        int(reorder_step), _stream()))
-                self._keep_idx = nidx
-                if reorder_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == reorder_step + 1:
-                    self._folded = (ntok, ntok._version, reorder_step + 1)
-            return cand, nscore, ntok, nidx
-        with torch.cuda.device(self.device):
-            check(self.lib.kmb_beam_sample_step(ptr(logits), logits.stride(0), V, B, int(num_beams), ptr(add), *args, _stream()))
-        if reorder_step >= 0:
-            self.gen_reorder(nidx, reorder_step)
-        return cand, nscore, ntok, nidx
+        return self._beam_call(
+            logits, outs, reorder_step,
+            lambda: self.lib.kmb_gen_beam_sample_step(self.h, ptr(logits), logits.stride(0), int(num_beams), ptr(add), *args,
+                                                      int(reorder_step), _stream()),
+            lambda: self.lib.kmb_beam_sample_step(ptr(logits), logits.stride(0), V, B, int(num_beams), ptr(add), *args, _stream()))
 
     def sample_step(self, logits, noise, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, unfinished=None, pad_token=0,
                     eos_token=-1, next_tokens=None, ids=None, t=0, flag=None, info_out=None):

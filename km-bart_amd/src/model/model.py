@@ -8,6 +8,7 @@ been moved to a HIP device raises.
 """
 import math
 import os
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -172,6 +173,140 @@ class BeamHypotheses:
         if self.early_stopping:
             return True
         return self.worst_score >= best_sum_logprobs / cur_len ** self.length_penalty
+
+
+def _decode_route(num_beams, do_sample, processors_on, fp32, device_sampling, has_sampler, V):
+    """The decode loop generate() runs: "device_sampling" (_sample_on_device), "one_beam" (the torch loop without beams),
+    "pipelined_beams" (greedy beam search, or beam sampling on the device) or "host_beams" (the reference's step-by-step loop).
+    fp32 mode and the score post-processors need the host loops.  device_sampling is model._device_sampling (falsy: the torch
+    paths), has_sampler whether model._sampler is set (host beam sampling; one-beam sampling does not use it).  Beam sampling on
+    the device also needs 2 * num_beams <= 16 draws per batch item and V <= 65536."""
+    on_device = do_sample and not processors_on and not fp32 and bool(device_sampling)
+    if num_beams == 1:
+        return "device_sampling" if on_device else "one_beam"
+    if processors_on or fp32:
+        return "host_beams"
+    if not do_sample or (on_device and not has_sampler and 2 * num_beams <= 16 and V <= 65536):
+        return "pipelined_beams"
+    return "host_beams"
+
+
+def _forced_tokens(cur_len, max_length, bos_token_id, eos_token_id):
+    """adjust_logits_during_generation (mixins.py:400-405) of a greedy beam search: the tokens forced at decode step cur_len, in
+    the reference's order -- BOS on the first step, EOS on the last.  Both only when max_length == 2: the pipelined loop then
+    forces the last of them, the host loop the first."""
+    forced = []
+    if cur_len == 1:
+        forced.append(bos_token_id)
+    if cur_len == max_length - 1 and eos_token_id is not None:
+        forced.append(eos_token_id)
+    return forced
+
+
+def _inputs_end(eng, fp32):
+    """Raises if the device-side validation flagged the batch (Engine.check_inputs_begin); fp32 mode started none."""
+    if not fp32:
+        eng.check_inputs_end()
+
+
+class _LateStop:
+    """The "every row has finished" test of a one-beam decode loop, read one step late: the flag of step t is copied to
+    page-locked memory in stream order and looked at after step t + 1 is enqueued; a stop found then drops that step's
+    (all-pad) column."""
+
+    def __init__(self, eng, n, dtype):
+        self.flags = eng.pinned((n,), dtype)
+        self.pending = None
+
+    def after(self, cur_len, unfinished):
+        """Queues the copy of `unfinished` (device scalar, 0: every row has finished at length cur_len); returns the length
+        to keep when the previous step's flag was 0, else None."""
+        self.flags[cur_len].copy_(unfinished, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        if self.pending is not None:
+            prev, prev_ev = self.pending
+            prev_ev.synchronize()
+            if int(self.flags[prev]) == 0:   # finished one step ago: the reference stopped there
+                return prev
+        self.pending = (cur_len, ev)
+        return None
+
+
+class _BeamBook:
+    """The reference's host-side beam bookkeeping (transformers 3.0.2 _generate_beam_search) on plain Python lists: indexing
+    small CPU tensors element by element (as the reference does) costs ~10 us per access and made a beam step 6x longer
+    than its GPU work."""
+
+    def __init__(self, s):
+        self.s = s
+        self.hyps = [BeamHypotheses(s.num_beams, s.max_length, s.length_penalty, s.early_stopping) for _ in range(s.B)]
+        # greedy beam search starts from beam 0 only; beam sampling lets every beam draw (HF 3.0.2 _generate_beam_search)
+        self.beam_scores = [0.0 if ((i % s.num_beams) == 0 or s.do_sample) else -1e9 for i in range(s.R)]
+        self.seqs = [[int(s.decoder_start_token_id)] for _ in range(s.R)]   # decoder inputs of every beam row
+        self.done = [False] * s.B
+
+    def advance(self, next_scores, next_tokens, step_len):
+        """One step from the step's sorted candidates [B][2 * num_beams]: updates the hypotheses and `done`; returns None
+        when every batch item is done, else moves the beams on and returns their (tokens, source rows)."""
+        s, num_beams, V = self.s, self.s.num_beams, self.s.V
+        new_scores, new_tokens, new_idx = [], [], []
+        for b in range(s.B):
+            if self.done[b]:
+                new_scores += [0.0] * num_beams
+                new_tokens += [s.pad_token_id] * num_beams
+                new_idx += [0] * num_beams
+                continue
+            n_sent = 0
+            for rank in range(2 * num_beams):
+                tid, tscore = next_tokens[b][rank], next_scores[b][rank]
+                beam_id, token_id = tid // V, tid % V
+                eff = b * num_beams + beam_id
+                if s.eos_token_id is not None and token_id == s.eos_token_id:
+                    if rank >= num_beams:
+                        continue
+                    self.hyps[b].add(list(self.seqs[eff]), tscore)
+                else:
+                    new_scores.append(tscore)
+                    new_tokens.append(token_id)
+                    new_idx.append(eff)
+                    n_sent += 1
+                if n_sent == num_beams:
+                    break
+            self.done[b] = self.done[b] or self.hyps[b].is_done(max(next_scores[b]), step_len)
+            assert n_sent == num_beams, "Beam should always be full"
+        if all(self.done):
+            return None
+        self.beam_scores = new_scores
+        self.seqs = [self.seqs[j] + [t] for j, t in zip(new_idx, new_tokens)]
+        return new_tokens, new_idx
+
+    def best(self):
+        """The finished search: (best hypotheses as a CPU tensor, padded as the reference pads them, their scores)."""
+        s = self.s
+        for b in range(s.B):
+            if self.done[b]:
+                continue
+            for beam_id in range(s.num_beams):
+                eff = b * s.num_beams + beam_id
+                self.hyps[b].add(list(self.seqs[eff]), self.beam_scores[eff])
+        best, best_scores, lens = [], [], []
+        nret_each = 1 if s.do_sample else s.num_return_sequences   # sampling replicated the batch instead (mixins.py:259-262)
+        for h in self.hyps:
+            sh = sorted(h.beams, key=lambda x: x[0])
+            for _ in range(nret_each):
+                sc, hyp = sh.pop()
+                best.append(hyp)
+                best_scores.append(sc)
+                lens.append(len(hyp))
+        if min(lens) != max(lens):
+            L = min(max(lens) + 1, s.max_length)
+            rows = []
+            for hyp, n in zip(best, lens):   # hypothesis, EOS behind it if it stopped early, pads (one tensor build, not one per row)
+                row = list(hyp) + ([s.eos_token_id] if n < s.max_length else [])
+                rows.append(row + [s.pad_token_id] * (L - len(row)))
+            return torch.tensor(rows, dtype=torch.long), best_scores
+        return torch.tensor(best, dtype=torch.long), best_scores
 
 
 class DecoderCache:
@@ -661,7 +796,6 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             image_features = [image_features[i] for i in rep.tolist()]
             B = B * eff_mult
         V = cfg.vocab_size
-        R = B * num_beams
         # fp32 validation mode (Engine.set_precision(True)): parity evidence, not a product path -- no KV cache, no fused decode
         # blocks; every step is an eval forward on the exact-fp32 kernels over the rows' tokens so far (the encoder runs once,
         # its fp32 states are handed back in), and the host loops below do the reference's bookkeeping on those logits
@@ -673,195 +807,156 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             eng.gen_begin(input_ids, image_features, attention_mask, num_beams, max_length)
             # the device-side input validation is read back without waiting (the decode steps are enqueued while the encoder
             # still runs); a flagged batch raises at the first point where the host waits for the device anyway
-            if os.environ.get("KMB_GEN_SYNC_CHECK") == "1":   # A/B knob: wait for the encoder before the first decode step
-                eng.check_inputs()
-            else:
-                eng.check_inputs_begin()
-        cur_len = 1
-
-        if num_beams == 1 and do_sample and not processors_on and not fp32 and getattr(self, "_device_sampling", True):
+            eng.check_inputs_begin()
+        route = _decode_route(num_beams, do_sample, processors_on, fp32, getattr(self, "_device_sampling", True),
+                              getattr(self, "_sampler", None) is not None, V)
+        if route == "device_sampling":
             return self._sample_on_device(eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id,
                                           eos_token_id, decoder_start_token_id)
+        s = SimpleNamespace(B=B, V=V, R=B * num_beams, num_beams=num_beams, max_length=max_length, min_length=min_length,
+                            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, processors_on=processors_on,
+                            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                            bad_words_ids=bad_words_ids, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
+                            bos_token_id=cfg.bos_token_id, decoder_start_token_id=decoder_start_token_id, fp32=fp32,
+                            length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences)
+        if route == "one_beam":
+            return self._one_beam_loop(eng, s, step_logits)
+        book = _BeamBook(s)
+        if route == "pipelined_beams":
+            self._pipelined_beam_loop(eng, s, book)
+        else:
+            self._host_beam_loop(eng, s, book, step_logits)
+        out, best_scores = book.best()
+        _inputs_end(eng, fp32)
+        out = out.to(eng.device)
+        return (out, torch.tensor(best_scores)) if return_scores else out
 
-        if num_beams == 1:
-            # Greedy / sampling without beams (transformers 3.0.2 _generate_no_beam_search): everything stays on the
-            # device; the "every sentence has finished" test is read one step late from a pinned flag, so step t+1 is
-            # enqueued before step t's flag is looked at, and the extra (all-pad) column of a late stop is dropped.
-            unfinished = torch.ones(B, dtype=torch.long, device=dev)
-            cols = [torch.full((B,), decoder_start_token_id, dtype=torch.long, device=dev)]
-            flags = eng.pinned((max_length + 1,), torch.long)
-            pending, keep = None, None
-            while cur_len < max_length:
-                logits = step_logits(torch.stack(cols, dim=1)) if fp32 else eng.gen_step(cols[-1], cur_len - 1)[:, :V]
-                if processors_on:
-                    _postprocess_next_token_scores(logits, torch.stack(cols, dim=1).tolist(), cur_len, min_length,
-                                                   eos_token_id, repetition_penalty, no_repeat_ngram_size, bad_words_ids)
-                elif eos_token_id is not None and cur_len < min_length:
-                    logits[:, eos_token_id] = -float("inf")
-                if do_sample:
-                    lg = logits / temperature if temperature != 1.0 else logits
-                    lg = _top_k_top_p_filtering(lg.clone(), top_k=top_k, top_p=top_p)
-                    nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1).squeeze(1)
-                else:
-                    nxt = torch.argmax(logits, dim=-1)
-                tok = nxt * unfinished + pad_token_id * (1 - unfinished) if eos_token_id is not None else nxt
-                cols.append(tok)
-                cur_len += 1
-                if eos_token_id is not None:
-                    unfinished = unfinished * (tok != eos_token_id).long()
-                    flags[cur_len].copy_(unfinished.max(), non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    if pending is not None:
-                        pending[1].synchronize()
-                        if int(flags[pending[0]]) == 0:     # finished one step ago: the reference stopped there
-                            keep = pending[0]
-                            break
-                    pending = (cur_len, ev)
-            out = torch.stack(cols[:keep] if keep is not None else cols, dim=1)
-            if not fp32:
-                eng.check_inputs_end()
-            return out
-
-        # Host bookkeeping on plain Python lists: indexing small CPU tensors element by element (as the reference does)
-        # costs ~10 us per access and made a beam step 6x longer than its GPU work.
-        hyps = [BeamHypotheses(num_beams, max_length, length_penalty, early_stopping) for _ in range(B)]
-        # greedy beam search starts from beam 0 only; beam sampling lets every beam draw (HF 3.0.2 _generate_beam_search)
-        beam_scores = [0.0 if ((i % num_beams) == 0 or do_sample) else -1e9 for i in range(R)]
-        sampler = getattr(self, "_sampler", None) or (lambda probs, n: torch.multinomial(probs, num_samples=n))
-        seqs = [[int(decoder_start_token_id)] for _ in range(R)]   # decoder inputs of every beam row
-        done = [False] * B
-        k = 2 * num_beams
-        last_tokens = torch.full((R,), decoder_start_token_id, dtype=torch.long, device=dev)
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-
-        def bookkeeping(next_scores, next_tokens, step_len):
-            """One step of the reference's host-side beam bookkeeping (transformers 3.0.2 _generate_beam_search) from the
-            step's sorted candidates; returns (new_scores, new_tokens, new_idx) and updates hyps / done."""
-            new_scores, new_tokens, new_idx = [], [], []
-            for b in range(B):
-                if done[b]:
-                    new_scores += [0.0] * num_beams
-                    new_tokens += [pad_token_id] * num_beams
-                    new_idx += [0] * num_beams
-                    continue
-                n_sent = 0
-                for rank in range(k):
-                    tid, tscore = next_tokens[b][rank], next_scores[b][rank]
-                    beam_id, token_id = tid // V, tid % V
-                    eff = b * num_beams + beam_id
-                    if eos_token_id is not None and token_id == eos_token_id:
-                        if rank >= num_beams:
-                            continue
-                        hyps[b].add(list(seqs[eff]), tscore)
-                    else:
-                        new_scores.append(tscore)
-                        new_tokens.append(token_id)
-                        new_idx.append(eff)
-                        n_sent += 1
-                    if n_sent == num_beams:
-                        break
-                done[b] = done[b] or hyps[b].is_done(max(next_scores[b]), step_len)
-                assert n_sent == num_beams, "Beam should always be full"
-            return new_scores, new_tokens, new_idx
-
-        # beam sampling on the device (kmb_beam_sample_step, DESIGN.md 6e): the same pipelined loop; the noise of torch.multinomial's
-        # exponential race is drawn here, [B, num_beams * V] on the default generator as the torch path draws it
-        device_beam_sampling = (do_sample and not processors_on and not fp32 and getattr(self, "_sampler", None) is None
-                                and getattr(self, "_device_sampling", True) and 2 * num_beams <= 16 and V <= 65536)
-        host_loop = (do_sample and not device_beam_sampling) or processors_on or fp32
-        if not host_loop:
-            # Greedy beam search and beam sampling, pipelined: the device picks the next step's beams itself (kmb_beam_merge_select /
-            # kmb_beam_sample_step: the
-            # first num_beams non-EOS candidates, exactly what the bookkeeping below sends on), so step t+1 is enqueued
-            # before the host has seen step t.  The host replays the reference's bookkeeping one step behind from the
-            # candidates (one small pinned copy per step): hypotheses, `done`, and the decision to stop -- a stop costs
-            # one decode step that is thrown away.  A `done` batch item keeps decoding on the device (the reference feeds
-            # it pad tokens); its rows feed nothing that is read.
-            staging = eng.pinned((max_length, B, k, 2), torch.int32)
-            beam_scores_dev = torch.full((B, num_beams), -1e9, dtype=torch.float32, device=dev)   # = beam_scores, built on the device
-            beam_scores_dev[:, 0] = 0.0
-            beam_scores_dev = beam_scores_dev.view(-1)
-            if do_sample:
-                beam_scores_dev.zero_()
-                noise = torch.empty((B, num_beams * V), dtype=torch.float32, device=dev)
-            pending = None
-
-            def replay(item):
-                nonlocal beam_scores, seqs
-                slot, ev, step_len = item
-                ev.synchronize()
-                eng.check_inputs_end()
-                c = staging[slot]
-                ns = c[:, :, 0].contiguous().view(torch.float32).tolist()
-                nt = c[:, :, 1].tolist()
-                new_scores, new_tokens, new_idx = bookkeeping(ns, nt, step_len)
-                if all(done):
-                    return True
-                beam_scores = new_scores
-                seqs = [seqs[j] + [t] for j, t in zip(new_idx, new_tokens)]
-                return False
-
-            while cur_len < max_length:
-                ban = eos if (eos >= 0 and cur_len < min_length) else -1
-                last = cur_len == max_length - 1
-                if do_sample:   # no forced tokens in the sampling branch; a stop found one step late has drawn that step's noise
-                    logits = eng.gen_step(last_tokens, cur_len - 1)
-                    noise.exponential_(1)
-                    cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_sample_step(
-                        logits, num_beams, noise, add=beam_scores_dev, temperature=temperature, top_k=top_k, top_p=top_p,
-                        ban_token=ban, eos_token=eos, cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
-                else:
-                    force = -1
-                    if cur_len == 1:
-                        force = cfg.bos_token_id          # adjust_logits_during_generation, mixins.py:400-405
-                    if last and eos_token_id is not None:
-                        force = eos_token_id
-                    # A forced step's scores are 0 at the forced token and -inf elsewhere whatever the model says
-                    # (log_softmax of a row with one finite entry): the vocabulary projection is skipped, and on the LAST
-                    # step, whose keys / values nobody will read, the decoder as well.
-                    if force >= 0 and last:
-                        logits = eng._gen_logits
-                    else:
-                        logits = eng.gen_step(last_tokens, cur_len - 1, want_logits=force < 0)
-                    # the candidates land in the page-locked staging buffer straight from the kernel (no copy launch per step)
-                    # ... and _reorder_cache (mixins.py:419-434) by the same call: the launch that picks the beams permutes the
-                    # history index
-                    cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step(
-                        logits, num_beams, k, beam_scores_dev, force_token=force, ban_token=ban, eos_token=eos,
-                        cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
-                ev = torch.cuda.Event()
-                ev.record()
-                if pending is not None and replay(pending):
-                    pending = None
+    def _one_beam_loop(self, eng, s, step_logits):
+        """Greedy / sampling without beams (transformers 3.0.2 _generate_no_beam_search): everything stays on the device; the
+        "every sentence has finished" test is read one step late (_LateStop)."""
+        dev = eng.device
+        unfinished = torch.ones(s.B, dtype=torch.long, device=dev)
+        cols = [torch.full((s.B,), s.decoder_start_token_id, dtype=torch.long, device=dev)]
+        stop = _LateStop(eng, s.max_length + 1, torch.long)
+        cur_len, keep = 1, None
+        while cur_len < s.max_length:
+            logits = step_logits(torch.stack(cols, dim=1)) if s.fp32 else eng.gen_step(cols[-1], cur_len - 1)[:, :s.V]
+            if s.processors_on:
+                _postprocess_next_token_scores(logits, torch.stack(cols, dim=1).tolist(), cur_len, s.min_length, s.eos_token_id,
+                                               s.repetition_penalty, s.no_repeat_ngram_size, s.bad_words_ids)
+            elif s.eos_token_id is not None and cur_len < s.min_length:
+                logits[:, s.eos_token_id] = -float("inf")
+            if s.do_sample:
+                lg = logits / s.temperature if s.temperature != 1.0 else logits
+                lg = _top_k_top_p_filtering(lg.clone(), top_k=s.top_k, top_p=s.top_p)
+                nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1).squeeze(1)
+            else:
+                nxt = torch.argmax(logits, dim=-1)
+            tok = nxt * unfinished + s.pad_token_id * (1 - unfinished) if s.eos_token_id is not None else nxt
+            cols.append(tok)
+            cur_len += 1
+            if s.eos_token_id is not None:
+                unfinished = unfinished * (tok != s.eos_token_id).long()
+                keep = stop.after(cur_len, unfinished.max())
+                if keep is not None:
                     break
-                pending = (cur_len - 1, ev, cur_len)
-                cur_len += 1
-            if pending is not None:
-                replay(pending)
-        while host_loop and cur_len < max_length:
-            # The reference's step-by-step host loop (HF 3.0.2 _generate_beam_search), for the searches whose scores are
-            # post-processed on the host: beam-search multinomial sampling (do_sample branch, reached from mixins.py:336-361
-            # with generate_text's --do_sample/--top_p/--top_k and --num_beams: no forced BOS/EOS; 2*num_beams draws per batch
-            # item from softmax over the beams' filtered (log-prob + beam score) / T) and repetition_penalty /
-            # no_repeat_ngram_size / bad_words_ids (postprocess_next_token_scores on the log-probabilities).
-            logits = step_logits(torch.tensor(seqs, dtype=torch.long)) if fp32 else eng.gen_step(last_tokens, cur_len - 1)[:, :V].float()
-            if not do_sample:   # adjust_logits_during_generation (mixins.py:400-405): forced BOS / EOS, greedy beams only
-                force = cfg.bos_token_id if cur_len == 1 else (eos_token_id if (cur_len == max_length - 1 and eos_token_id is not None) else None)
+        out = torch.stack(cols[:keep] if keep is not None else cols, dim=1)
+        _inputs_end(eng, s.fp32)
+        return out
+
+    def _pipelined_beam_loop(self, eng, s, book):
+        """Greedy beam search and beam sampling on the device (kmb_beam_merge_select / kmb_beam_sample_step: the first num_beams
+        non-EOS candidates, exactly what the bookkeeping sends on), so step t+1 is enqueued before the host has seen step t.  The
+        host replays the reference's bookkeeping one step behind from the candidates (one small pinned copy per step):
+        hypotheses, `done`, and the decision to stop -- a stop costs one decode step that is thrown away.  A `done` batch item
+        keeps decoding on the device (the reference feeds it pad tokens); its rows feed nothing that is read.  Beam sampling
+         draws the noise of torch.multinomial's exponential race here, [B, num_beams * V] on the default
+        generator as the torch path draws it."""
+        dev = eng.device
+        B, num_beams, k = s.B, s.num_beams, 2 * s.num_beams
+        last_tokens = torch.full((s.R,), s.decoder_start_token_id, dtype=torch.long, device=dev)
+        eos = -1 if s.eos_token_id is None else int(s.eos_token_id)
+        staging = eng.pinned((s.max_length, B, k, 2), torch.int32)
+        beam_scores_dev = torch.full((B, num_beams), -1e9, dtype=torch.float32, device=dev)   # = book.beam_scores, built on the device
+        beam_scores_dev[:, 0] = 0.0
+        beam_scores_dev = beam_scores_dev.view(-1)
+        if s.do_sample:
+            beam_scores_dev.zero_()
+            noise = torch.empty((B, num_beams * s.V), dtype=torch.float32, device=dev)
+
+        def replay(item):   # True: every batch item is done
+            slot, ev, step_len = item
+            ev.synchronize()
+            eng.check_inputs_end()
+            c = staging[slot]
+            return book.advance(c[:, :, 0].contiguous().view(torch.float32).tolist(), c[:, :, 1].tolist(), step_len) is None
+
+        cur_len, pending = 1, None
+        while cur_len < s.max_length:
+            ban = eos if (eos >= 0 and cur_len < s.min_length) else -1
+            last = cur_len == s.max_length - 1
+            if s.do_sample:   # no forced tokens in the sampling branch; a stop found one step late has drawn that step's noise
+                logits = eng.gen_step(last_tokens, cur_len - 1)
+                noise.exponential_(1)
+                cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_sample_step(
+                    logits, num_beams, noise, add=beam_scores_dev, temperature=s.temperature, top_k=s.top_k, top_p=s.top_p,
+                    ban_token=ban, eos_token=eos, cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
+            else:
+                forced = _forced_tokens(cur_len, s.max_length, s.bos_token_id, s.eos_token_id)
+                force = forced[-1] if forced else -1
+                # A forced step's scores are 0 at the forced token and -inf elsewhere whatever the model says
+                # (log_softmax of a row with one finite entry): the vocabulary projection is skipped, and on the LAST
+                # step, whose keys / values nobody will read, the decoder as well.
+                if force >= 0 and last:
+                    logits = eng._gen_logits
+                else:
+                    logits = eng.gen_step(last_tokens, cur_len - 1, want_logits=force < 0)
+                # the candidates land in the page-locked staging buffer straight from the kernel (no copy launch per step)
+                # ... and _reorder_cache (mixins.py:419-434) by the same call: the launch that picks the beams permutes the
+                # history index
+                cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step(
+                    logits, num_beams, k, beam_scores_dev, force_token=force, ban_token=ban, eos_token=eos,
+                    cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
+            ev = torch.cuda.Event()
+            ev.record()
+            if pending is not None and replay(pending):
+                return
+            pending = (cur_len - 1, ev, cur_len)
+            cur_len += 1
+        if pending is not None:
+            replay(pending)
+
+    def _host_beam_loop(self, eng, s, book, step_logits):
+        """The reference's step-by-step host loop (HF 3.0.2 _generate_beam_search), for the searches whose scores are
+        post-processed on the host: beam-search multinomial sampling (do_sample branch, reached from mixins.py:336-361 with
+        generate_text's --do_sample/--top_p/--top_k and --num_beams: no forced BOS/EOS; 2*num_beams draws per batch item from
+        softmax over the beams' filtered (log-prob + beam score) / T) where the device path does not apply, repetition_penalty /
+        no_repeat_ngram_size / bad_words_ids (postprocess_next_token_scores on the log-probabilities), and fp32 mode."""
+        dev = eng.device
+        B, V, num_beams, k = s.B, s.V, s.num_beams, 2 * s.num_beams
+        last_tokens = torch.full((s.R,), s.decoder_start_token_id, dtype=torch.long, device=dev)
+        sampler = getattr(self, "_sampler", None) or (lambda probs, n: torch.multinomial(probs, num_samples=n))
+        cur_len = 1
+        while cur_len < s.max_length:
+            logits = (step_logits(torch.tensor(book.seqs, dtype=torch.long)) if s.fp32
+                      else eng.gen_step(last_tokens, cur_len - 1)[:, :V].float())
+            if not s.do_sample:   # adjust_logits_during_generation (mixins.py:400-405): forced BOS / EOS, greedy beams only
+                forced = _forced_tokens(cur_len, s.max_length, s.bos_token_id, s.eos_token_id)
+                force = forced[0] if forced else None
                 if force is not None:
                     kept = logits[:, force].clone()
                     logits.fill_(-float("inf"))
                     logits[:, force] = kept
-            add = torch.tensor(beam_scores, dtype=torch.float32).to(dev)
+            add = torch.tensor(book.beam_scores, dtype=torch.float32).to(dev)
             sc = torch.log_softmax(logits, dim=-1)
             # min_length (EOS -inf AFTER log_softmax) and the other post-processing of transformers 3.0.2
-            _postprocess_next_token_scores(sc, seqs if processors_on else None, cur_len, min_length, eos_token_id,
-                                           repetition_penalty, no_repeat_ngram_size, bad_words_ids)
+            _postprocess_next_token_scores(sc, book.seqs if s.processors_on else None, cur_len, s.min_length, s.eos_token_id,
+                                           s.repetition_penalty, s.no_repeat_ngram_size, s.bad_words_ids)
             sc = sc + add[:, None]
-            if do_sample:
-                if temperature != 1.0:
-                    sc = sc / temperature
-                sc = _top_k_top_p_filtering(sc, top_k=top_k, top_p=top_p, min_tokens_to_keep=2).view(B, num_beams * V)
+            if s.do_sample:
+                if s.temperature != 1.0:
+                    sc = sc / s.temperature
+                sc = _top_k_top_p_filtering(sc, top_k=s.top_k, top_p=s.top_p, min_tokens_to_keep=2).view(B, num_beams * V)
                 drawn = sampler(torch.softmax(sc, dim=-1), k)
                 ns = torch.gather(sc, -1, drawn)
                 ns, order = torch.sort(ns, descending=True, dim=1)
@@ -870,44 +965,14 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             else:
                 ns, nt_ = torch.topk(sc.view(B, num_beams * V), k, dim=1, largest=True, sorted=True)
                 next_scores, next_tokens = ns.cpu().tolist(), nt_.cpu().tolist()
-            new_scores, new_tokens, new_idx = bookkeeping(next_scores, next_tokens, cur_len)
-            if all(done):
-                break
-            beam_scores = new_scores
-            seqs = [seqs[j] + [t] for j, t in zip(new_idx, new_tokens)]
-            tok_idx = torch.tensor([new_tokens, new_idx], dtype=torch.long).to(dev)
+            moved = book.advance(next_scores, next_tokens, cur_len)
+            if moved is None:
+                return
+            tok_idx = torch.tensor(list(moved), dtype=torch.long).to(dev)   # [new tokens, their source rows]
             last_tokens = tok_idx[0].contiguous()
-            if not fp32:
+            if not s.fp32:
                 eng.gen_reorder(tok_idx[1], cur_len - 1)   # _reorder_cache, mixins.py:419-434
             cur_len += 1
-        for b in range(B):
-            if done[b]:
-                continue
-            for beam_id in range(num_beams):
-                eff = b * num_beams + beam_id
-                hyps[b].add(list(seqs[eff]), beam_scores[eff])
-        best, best_scores, lens = [], [], []
-        nret_each = 1 if do_sample else num_return_sequences   # sampling replicated the batch instead (mixins.py:259-262)
-        for h in hyps:
-            sh = sorted(h.beams, key=lambda x: x[0])
-            for _ in range(nret_each):
-                sc, hyp = sh.pop()
-                best.append(hyp)
-                best_scores.append(sc)
-                lens.append(len(hyp))
-        if min(lens) != max(lens):
-            L = min(max(lens) + 1, max_length)
-            rows = []
-            for hyp, n in zip(best, lens):   # hypothesis, EOS behind it if it stopped early, pads (one tensor build, not one per row)
-                row = list(hyp) + ([eos_token_id] if n < max_length else [])
-                rows.append(row + [pad_token_id] * (L - len(row)))
-            out = torch.tensor(rows, dtype=torch.long)
-        else:
-            out = torch.tensor(best, dtype=torch.long)
-        if not fp32:
-            eng.check_inputs_end()
-        out = out.to(dev)
-        return (out, torch.tensor(best_scores)) if return_scores else out
 
     def _sample_on_device(self, eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id, eos_token_id,
                           decoder_start_token_id):
@@ -924,8 +989,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         unfinished = torch.ones(B, dtype=torch.long, device=dev) if eos_token_id is not None else None
         noise = torch.empty((B, V), dtype=torch.float32, device=dev)
         dflags = torch.zeros(max_length + 1, dtype=torch.int32, device=dev)
-        flags = eng.pinned((max_length + 1,), torch.int32)
-        cur_len, pending, keep = 1, None, None
+        stop = _LateStop(eng, max_length + 1, torch.int32)
+        cur_len, keep = 1, None
         while cur_len < max_length:
             logits = eng.gen_step(toks[(cur_len - 1) % 2], cur_len - 1)
             ban = eos if (eos >= 0 and cur_len < min_length) else -1
@@ -935,15 +1000,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                             next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1])
             cur_len += 1
             if unfinished is not None:   # the finished flag, read one step late as in the torch path
-                flags[cur_len - 1].copy_(dflags[cur_len - 1], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                if pending is not None:
-                    pending[1].synchronize()
-                    if int(flags[pending[0] - 1]) == 0:
-                        keep = pending[0]
-                        break
-                pending = (cur_len, ev)
+                keep = stop.after(cur_len, dflags[cur_len - 1])
+                if keep is not None:
+                    break
         out = ids[:, :keep if keep is not None else cur_len].contiguous()
         eng.check_inputs_end()
         return out

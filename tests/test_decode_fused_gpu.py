@@ -272,31 +272,3 @@ def test_full_size_beam5_search_matches_the_oracle(fused, sublayer_scale):
             best = _oracle_sequence_score(sd, ocfg, b, r, ref_ids[r].tolist(), max_length=kw["max_length"])
             assert abs(best - float(ref_sc[r])) < 1e-3, "the test's scorer must reproduce the oracle's own score"
             assert alt >= best - 2e-2, "row %d: the product's hypothesis is not a tie for the oracle (%.4f vs %.4f)" % (r, alt, best)
-
-
-def test_physical_cache_reorder_fallback_equals_the_history_index():
-    """KMB_GEN_HIST=0 (the documented fallback: a beam reorder gathers every layer's self-attention K / V cache into the other copy instead
-    of permuting the history index, csrc/engine.cpp::kmb_gen_reorder) must keep returning what the default returns: same ids, same scores
-    (nothing exercised the old path any more).  The flag is read by kmb_gen_begin, i.e. per generate call."""
-    ocfg = O.OracleConfig.from_dict(BASE)
-    sd = G.golden_state_dict(ocfg, seed=11)      # re-scaled as in the full-size beam test above: searches that depend on item and position
-    sd["model.shared.weight"] = sd["model.shared.weight"] * 8.0
-    sd["model.decoder.embed_positions.weight"] = sd["model.decoder.embed_positions.weight"] * 40.0
-    for k_ in list(sd):
-        if k_.endswith("out_proj.weight") or k_.endswith("fc2.weight"):
-            sd[k_] = sd[k_] * 3.0
-    model = MultiModalBartForConditionalGeneration(MultiModalBartConfig.from_dict(BASE))
-    model.load_state_dict(sd, strict=False)
-    model.to(DEV).eval()
-    b = make_batch(5, seed=91, regions=(36, 20, 7, 36, 12), event_lens=(23, 7, 15, 9, 20), label_lens=(32,) * 5)
-    kw = dict(input_ids=b["input_ids"].to(DEV), image_features=[f.to(DEV) for f in b["image_features"]],
-              attention_mask=b["attention_mask"].to(DEV), num_beams=5, max_length=12, early_stopping=True)
-    want, want_sc = model.generate(return_scores=True, **kw)
-    os.environ["KMB_GEN_HIST"] = "0"
-    try:
-        got, got_sc = model.generate(return_scores=True, **kw)
-    finally:
-        os.environ.pop("KMB_GEN_HIST", None)
-    assert torch.equal(got, want)
-    assert torch.equal(got_sc, want_sc)
-    assert len({tuple(r) for r in want.tolist()}) > 1     # the searches differ by item: the reorders were not identities

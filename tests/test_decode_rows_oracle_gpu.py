@@ -327,22 +327,23 @@ def test_generate_at_the_benchmarked_shape_matches_the_oracle(setup, fused):
 # ---------------------------------------------------------------------------------------------------------- hand-offs
 def _drive_edited(eng, b, nb, steps, fold):
     """gen_step + beam_step(reorder_step = t) for `steps` steps; after each beam step every other row of the returned next_tokens is set
-    to pad IN PLACE and that same tensor is the next gen_step's input.  fold: KMB_GEN_FOLD_EMBED default (the beam step embeds the tokens
-    it chose), else 0 (gen_step embeds)."""
+    to pad IN PLACE and that same tensor is the next gen_step's input.  fold: the beam step reorders and embeds the tokens it chose, else
+    beam_step(reorder_step = -1) + gen_reorder, and gen_step embeds."""
     V = eng.config.vocab_size
     R = b["input_ids"].shape[0] * nb
     out = []
-    with _env(KMB_GEN_FOLD_EMBED="1" if fold else "0"):
-        _begin(eng, b, nb, steps + 2)
-        tok = torch.full((R,), EOS, dtype=torch.int64, device=DEV)
-        add = torch.zeros(R, device=DEV)
-        for t in range(steps):
-            lg = eng.gen_step(tok, t)
-            out.append(lg[:, :V].clone())
-            cand, add, ntok, nidx = eng.beam_step(lg, nb, 2 * nb, add, eos_token=-1, reorder_step=t)
-            out.append(ntok.clone())
-            ntok[::2] = PAD
-            tok = ntok
+    _begin(eng, b, nb, steps + 2)
+    tok = torch.full((R,), EOS, dtype=torch.int64, device=DEV)
+    add = torch.zeros(R, device=DEV)
+    for t in range(steps):
+        lg = eng.gen_step(tok, t)
+        out.append(lg[:, :V].clone())
+        cand, add, ntok, nidx = eng.beam_step(lg, nb, 2 * nb, add, eos_token=-1, reorder_step=t if fold else -1)
+        if not fold:
+            eng.gen_reorder(nidx, t)
+        out.append(ntok.clone())
+        ntok[::2] = PAD
+        tok = ntok
     torch.cuda.synchronize()
     return out
 

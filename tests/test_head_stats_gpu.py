@@ -146,12 +146,11 @@ def test_tied_logits_go_to_the_smaller_index():
     assert tok0[:2] == [0, 1] or b[0][0, 0, 1] // V != 0
 
 
-@pytest.mark.parametrize("knob,exact", [("KMB_GEN_HEAD_STATS", False), ("KMB_GEN_FOLD_EMBED", True), ("KMB_GEN_HIST", True)])
+@pytest.mark.parametrize("knob,exact", [("KMB_GEN_HEAD_STATS", False)])
 def test_generation_with_and_without_the_statistics_path_returns_the_same_ids(knob, exact):
     """model.generate at the benchmarked shape's row count (64 items x 5 beams = 320 rows: the all-rows kernel and its statistics run)
-    with KMB_GEN_HEAD_STATS=0 (two-launch beam step over the logits) and by default: same ids; sequence scores within 1e-5.
-    KMB_GEN_FOLD_EMBED=0 (the next step's embedding by kmb_gen_step's own launch instead of the beam step's) and KMB_GEN_HIST=0 (physical
-    cache reorder by kmb_gen_reorder instead of the history gather folded into the beam step): same ids AND bit-identical scores."""
+    with KMB_GEN_HEAD_STATS=0 (two-launch beam step over the logits) and by default: same ids; sequence scores within 1e-5.  (The
+    folded reorder and embedding: test_folded_reorder_and_embedding_equal_the_separate_calls.)"""
     from oracle import goldenlib as G
     from oracle import kmbart_oracle as O
     from src.data.synthetic import make_batch
