@@ -191,6 +191,25 @@ int kmb_stream_wait_bucket(kmb_handle* h, int i, void* stream);
 int kmb_logits_ld(const kmb_handle* h);
 int kmb_forward(kmb_handle* h, const kmb_batch* batch, int train, int need_grad, float* loss_out,
                 float* logits_out, kmb_bf16* enc_out, void* stream);
+/* Scores of a GIVEN target sequence: log p(label_t | image, event, labels_<t) per decoder position and per sample, without
+ * materialising the logits (reference scripts/filter_reason.py:24-52 -- forward without labels, log_softmax over outputs[0], the
+ * label's entry token by token, the mean over labels >= 0 against --pp_threshold).  An eval-mode forward (no dropout, need_grad = 0)
+ * that counts as a forward: it rewrites the workspace and invalidates a pending kmb_backward.  batch->labels is required.
+ *   token_logprob [B*T] fp32 : log_softmax(logits)[label]; 0 where the label is -100 or outside [0, vocab_size)
+ *   sample_nll    [B]   fp32 : the SUM of -token_logprob over the item's valid rows, in row order (no floating-point atomics)
+ *   sample_count  [B]   int32: the number of valid rows (0: the caller's mean / perplexity is 0 / 0 = NaN)
+ *   path_out (HOST, may be NULL): 1 = the store-free head ran, 0 = the fallback
+ * Store-free head: at least 256 decoder rows, padded vocabulary % 256 == 0, d_model % 64 == 0 and >= 320, bf16 product mode.  The
+ * label's logit comes from 2 * d_model values per row; one GEMM over the rows ROUNDED UP to whole 256-row tiles keeps, per row and
+ * 64-column block, the block's maximum and sum-exp only -- exact for any finite logits (nothing is shifted by the label's logit, no
+ * exponent is clamped), a non-finite logit makes its own row's score non-finite.  The TAIL ROWS [B*T, round_up(B*T, 256)) are whatever
+ * the bound workspace holds behind the decoder states (always inside it); rows of a GEMM are independent, their statistics go to rows
+ * of their own in the workspace and nothing reads them.  Fallback (anything else, and KMB_SCORE_FALLBACK=1 in the environment, read
+ * per call): fp32 logits in row chunks bounded by the workspace's existing head scratch + the row cross-entropy kernel; the fp32
+ * validation mode always takes it, through the fp32 head.  Out-of-range labels set bit 1 of the status word (kmb_read_status), as in
+ * kmb_forward.  Workspace: kmb_workspace_bytes, unchanged. */
+int kmb_score(kmb_handle* h, const kmb_batch* batch, float* token_logprob /* [B*T] */, float* sample_nll /* [B] */,
+              int32_t* sample_count /* [B] */, int32_t* path_out /* host, may be NULL */, void* stream);
 /* Optional inputs / outputs of the forward that the bare MultiModalBartModel and the `encoder_outputs` keyword need
  * (src/model/model.py:39-103): */
 typedef struct kmb_forward_opts {
@@ -455,6 +474,16 @@ int kmb_op_gemm_allrows(const KmbGemm* p, void* stream);
  * (stats_blocks = ceil(V / 256); what kmb_gen_step + kmb_gen_beam_step run) */
 int64_t kmb_op_gemm_allrows_stats_floats(int N);
 int kmb_op_gemm_allrows_stats(const KmbGemm* p, float* stats, void* stream);
+/* the vocabulary projection's SCORING class (what kmb_score's store-free head runs): C = A B^T + bias is never stored;
+ * stats[(row * (N / 64) + col / 64) * 2] = the maximum of the row's 64 values in that column block, [... + 1] = the sum of
+ * exp(v - maximum) over them (kmb_op_gemm_score_stats_floats(M, N) floats).  Forward layout (a_kc = b_kc = 1), M and N multiples of
+ * 256 with at least 128 tiles of 256 x 256, K a multiple of 64 and >= 320, bias required, every output / epilogue field of *p unset. */
+int64_t kmb_op_gemm_score_stats_floats(int M, int N);
+int kmb_op_gemm_score(const KmbGemm* p, float* stats, void* stream);
+/* ... and its finish: token_logprob[r] = label_logit[r] - logsumexp(row r's `blocks` pairs) (0 where labels[r] is -100 or outside
+ * [0, V)), then per batch item the sum of -token_logprob and the number of valid rows over its T rows, in row order */
+int kmb_op_score_rows_finish(const float* stats, int blocks, const float* label_logit, const int64_t* labels, int B, int T, int V,
+                             float* token_logprob, float* sample_nll, int32_t* sample_count, void* stream);
 int kmb_beam_step_stats(const float* logits, int ld, int V, int B, int num_beams, const float* add, int force_token, int ban_token,
                         int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
                         const float* stats, int stats_blocks, void* stream);

@@ -82,6 +82,23 @@ int kmb_op_gemm_allrows_stats(const KmbGemm* p, float* stats, void* stream) {
   if (!stats) return kmb_set_error("kmb_op_gemm_allrows_stats: stats is required");
   return hipfail(kmb_gemm_allrows_launch(*p, stats, (hipStream_t)stream), "gemm_allrows_stats");
 }
+// the scoring class of the vocabulary projection (gemm_lean.hip LN_SCORE) and its finish (loss.hip), without a model
+int64_t kmb_op_gemm_score_stats_floats(int M, int N) { return M > 0 && N > 0 ? (int64_t)M * (N / 64) * 2 : 0; }
+int kmb_op_gemm_score(const KmbGemm* p, float* stats, void* stream) {
+  if (!p) return kmb_set_error("kmb_op_gemm_score: null problem");
+  const char* why = kmb_gemm_score_check(*p, stats);
+  if (why) return kmb_set_error(why);
+  return hipfail(kmb_gemm_score_launch(*p, stats, (hipStream_t)stream), "gemm_score");
+}
+int kmb_op_score_rows_finish(const float* stats, int blocks, const float* label_logit, const int64_t* labels, int B, int T, int V,
+                             float* token_logprob, float* sample_nll, int32_t* sample_count, void* stream) {
+  if (!stats || !label_logit || !labels || !token_logprob || !sample_nll || !sample_count || blocks <= 0 || B <= 0 || T <= 0 || V <= 0)
+    return kmb_set_error("kmb_op_score_rows_finish: bad arguments");
+  int e = hipfail(kmb_score_rows_finish_launch(stats, blocks, label_logit, labels, B * T, V, token_logprob, (hipStream_t)stream), "score_rows_finish");
+  if (e) return e;
+  return hipfail(kmb_score_segments_launch(token_logprob, 0, labels, B, T, V, token_logprob, sample_nll, sample_count, (hipStream_t)stream),
+                 "score_segments");
+}
 int kmb_beam_step_stats(const float* logits, int ld, int V, int B, int num_beams, const float* add, int force_token, int ban_token,
                         int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
                         const float* stats, int stats_blocks, void* stream) {

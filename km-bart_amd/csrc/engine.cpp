@@ -1404,6 +1404,76 @@ int kmb_forward_ex(kmb_handle* h, const kmb_batch* batch, const kmb_forward_opts
   return forward_impl(h, batch, nullptr, opts, train, need_grad, loss_out, logits_out, enc_out, stream);
 }
 
+// Scores of a given target sequence (reference scripts/filter_reason.py:24-52: forward without labels, log_softmax over the [B, T, V]
+// logits, the label's entry per token, the mean per sample): an eval-mode forward up to the decoder states, then a head that leaves
+// no V-sized matrix.  Store-free path (1): the label's logit from 2 d values per row (ce_label_logit_kernel), ONE GEMM over the rows
+// rounded up to whole 256-row tiles whose epilogue keeps per row and 64-column block (maximum, sum-exp) only (gemm_lean.hip LN_SCORE;
+// the statistics live where the training head keeps its bf16 matrix), the row finish, the per-sample sums.  The tail rows [Md, Mpad) are
+// whatever the workspace holds behind the decoder states: they are multiplied like ignored rows, their statistics land in rows of their own
+// and nothing reads them.  Fallback (0; fewer than 256 rows, a vocabulary / width the persistent layout does not take, the fp32 validation
+// mode, KMB_SCORE_FALLBACK=1): fp32 logits in row chunks that fit the existing logits scratch + ce_kernel_reg, whose loss_rows are the
+// per-row values, then the same per-sample reduction.
+int kmb_score(kmb_handle* h, const kmb_batch* batch, float* token_logprob, float* sample_nll, int32_t* sample_count, int32_t* path_out,
+              void* stream) {
+  if (!h) return fail("kmb_score: null handle");
+  if (!batch || !batch->labels) return fail("kmb_score: labels are required (the sequence to score)");
+  if (!token_logprob || !sample_nll || !sample_count) return fail("kmb_score: token_logprob, sample_nll and sample_count are required");
+  kmb_forward_opts o{};
+  o.skip_head = 1;
+  KCHK(forward_impl(h, batch, nullptr, &o, 0, 0, nullptr, nullptr, nullptr, stream));
+  hipStream_t s = (hipStream_t)stream;
+  PrecisionScope scope(h);
+  if (!h->fp32 && h->small_floats > 1024) { g_small_slab = h->small_slab; g_small_floats = h->small_floats; }
+  const kmb_batch& bt = *batch;
+  const int d = h->d, B = bt.B, T = bt.T, Md = B * T;
+  const bf16_t* hdec = h->xd[h->cfg.decoder_layers];
+  const bf16_t* Eb = h->wb(h->shared);
+  HIPCHK(kmb_count_valid_launch(bt.labels, Md, h->V, h->count, h->status, s));
+  const char* fb = getenv("KMB_SCORE_FALLBACK");   // read per call: tests flip it inside one process
+  const bool forced = fb && fb[0] == '1';
+  const int Mpad = (Md + 255) & ~255, nparts = h->Vpad / 64;
+  const size_t head_bytes = (size_t)Md * h->Vpad * esz();   // the training head's matrix (dlogits_c): idle in an eval forward
+  const bool in_ws = (const char*)hdec + (size_t)Mpad * d * sizeof(bf16_t) <= h->ws + h->ws_bytes;
+  const bool store_free = !g_f32 && !forced && Md >= 256 && (h->Vpad % 256) == 0 && (d % 64) == 0 && d >= 320 &&
+                          (long)(Mpad / 256) * (h->Vpad / 256) >= 128 && in_ws && (size_t)Mpad * nparts * 2 * sizeof(float) <= head_bytes;
+  if (path_out) *path_out = store_free ? 1 : 0;
+  if (store_free) {
+    float* stats = reinterpret_cast<float*>(h->dlogits_c);
+    HIPCHK(kmb_ce_label_logit_launch(hdec, d, Eb, d, h->flb, bt.labels, Md, d, h->V, h->ce_shift, s));
+    HIPCHK(kmb_ce_pad_bias_launch(h->flb, h->V, h->Vpad, h->ce_bias, s));
+    const KmbGemm g = lin_fwd(hdec, d, Eb, h->ce_bias, Mpad, h->Vpad, d);
+    if (const char* why = kmb_gemm_score_check(g, stats)) return fail("kmb_score: %s", why);
+    HIPCHK(kmb_gemm_score_launch(g, stats, s));
+    HIPCHK(kmb_score_rows_finish_launch(stats, nparts, h->ce_shift, bt.labels, Md, h->V, token_logprob, s));
+    HIPCHK(kmb_score_segments_launch(token_logprob, 0, bt.labels, B, T, h->V, token_logprob, sample_nll, sample_count, s));
+    return 0;
+  }
+  // fallback: the larger of the two head scratch buffers holds the fp32 logits of a row chunk
+  float* buf = h->logits_c;
+  size_t cap = h->logits_c_floats;
+  if (head_bytes / sizeof(float) > cap) { buf = reinterpret_cast<float*>(h->dlogits_c); cap = head_bytes / sizeof(float); }
+  const size_t fit = cap / (size_t)h->Vpad;
+  if (fit >= 1) {
+    int CH = Md < h->lm_chunk ? Md : h->lm_chunk;
+    if ((size_t)CH > fit) CH = (int)fit;
+    for (int r0 = 0; r0 < Md; r0 += CH) {
+      const int rows = (Md - r0) < CH ? (Md - r0) : CH;
+      KmbGemm g = lin_fwd(EP(hdec, (size_t)r0 * d), d, Eb, h->flb, rows, h->V, d);
+      g.out_f32 = buf; g.ld_out_f32 = h->Vpad;
+      KCHK(run_vocab_gemm(g, s));
+      HIPCHK(kmb_ce_launch(buf, h->Vpad, h->V, bt.labels + r0, rows, h->count, 1.f, h->loss_rows + r0, nullptr, s));
+    }
+  } else {   // (a single decoder row of a wide vocabulary: the bf16 head's matrix is all there is room for)
+    if (g_f32) return fail("kmb_score: the logits scratch does not hold one fp32 row");
+    KmbGemm g = lin_fwd(hdec, d, Eb, h->flb, Md, h->V, d);
+    g.out_bf16 = h->dlogits_c; g.ld_out_bf16 = h->Vpad;
+    KCHK(run_gemm(g, s));
+    HIPCHK(kmb_ce_bf16_launch(h->dlogits_c, h->Vpad, h->V, bt.labels, Md, h->count, 1.f, h->loss_rows, nullptr, s));
+  }
+  HIPCHK(kmb_score_segments_launch(h->loss_rows, 1, bt.labels, B, T, h->V, token_logprob, sample_nll, sample_count, s));
+  return 0;
+}
+
 int kmb_hidden_state(kmb_handle* h, int which, int index, kmb_bf16* out, void* stream) {
   if (!h->have_hdec) return fail("kmb_hidden_state: no forward whose activations are still in the workspace");
   if (h->fp32) return fail("kmb_hidden_state: not available in the fp32 validation mode");

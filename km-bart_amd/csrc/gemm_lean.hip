@@ -26,13 +26,55 @@ constexpr int LN_A = 256 * BK * 2;                    // 32 KB
 constexpr int LN_EPW = 16 * 64 * 4;                   // fp32 staging image of a wave (16 rows x 64 columns)
 constexpr int LN_LDS = 2 * LN_STG + 8 * LN_EPW;       // 160 KB
 
-enum { LN_BIAS = 0, LN_BIAS_RES = 1, LN_PLAIN = 2, LN_GELU = 3, LN_DGELU_CS = 4, LN_CE = 5 };
+enum { LN_BIAS = 0, LN_BIAS_RES = 1, LN_PLAIN = 2, LN_GELU = 3, LN_DGELU_CS = 4, LN_CE = 5, LN_SCORE = 6 };
 
 __device__ __forceinline__ const char* ln_uniform(const char* ptr) {
   const uint64_t a = reinterpret_cast<uint64_t>(ptr);
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
   return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
+}
+
+// LN_SCORE: the tied head's projection for SCORING a given sequence (kmb_score; reference scripts/filter_reason.py:24-52 takes the [B, T, V]
+// logits and runs log_softmax + a per-token pick over them).  The class stores NOTHING V-sized: per row and per 64-column wave block only the
+// block's maximum and its sum of exp(v - maximum), to p.row_sums[(row * p.row_sums_ld + col / 64) * 2 + {0, 1}]; score_rows_finish_kernel
+// (loss.hip) merges a row's blocks into its log-sum-exp.  Unlike LN_CE nothing is shifted by the label's logit and no exponent is clamped: the
+// pair is exact for any finite logits (a row whose loss exceeds 80 nats is what a perplexity filter looks for), and a non-finite logit makes
+// its own row's pair non-finite and no other's.
+// No staging pass either: lane (r, g) holds C[16 i + r][16 j + 4 g .. + 3], so the 64 columns of row 16 i + r inside this wave block are
+// the 4 x NJ accumulator values of the four lanes r, r + 16, r + 32, r + 48 -- an in-lane tree and two cross-lane steps per reduction, in a
+// fixed order (same inputs, same bits), and one 8-byte store per row from the lanes g == 0.
+template <int NJ>
+__device__ __forceinline__ void ln_epilogue_score(const KmbGemm& p, const f32x4 (&acc)[8][NJ], int r, int g, int row0w, int col0w) {
+  static_assert(NJ == 4, "64-column wave blocks");
+  f32x4 b4[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) b4[j] = *reinterpret_cast<const f32x4*>(p.bias + col0w + 16 * j + 4 * g);
+  float* slot = p.row_sums + ((size_t)(row0w + r) * p.row_sums_ld + (col0w >> 6)) * 2;
+  const size_t chunk = (size_t)16 * p.row_sums_ld * 2;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {   // static accumulator indices (a run-time index would put acc in scratch)
+    f32x4 v[NJ];
+    float mj[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      v[j] = acc[i][j] + b4[j];
+      mj[j] = fmaxf(fmaxf(v[j][0], v[j][1]), fmaxf(v[j][2], v[j][3]));
+    }
+    float m = fmaxf(fmaxf(mj[0], mj[1]), fmaxf(mj[2], mj[3]));
+    m = fmaxf(m, __shfl_xor(m, 16));
+    m = fmaxf(m, __shfl_xor(m, 32));
+    float sj[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const f32x4 t = (v[j] - m) * 1.4426950408889634f;
+      sj[j] = (__builtin_amdgcn_exp2f(t[0]) + __builtin_amdgcn_exp2f(t[1])) + (__builtin_amdgcn_exp2f(t[2]) + __builtin_amdgcn_exp2f(t[3]));
+    }
+    float s = (sj[0] + sj[1]) + (sj[2] + sj[3]);
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (g == 0) *reinterpret_cast<kmb_f32x2*>(slot + i * chunk) = kmb_f32x2{m, s};
+  }
 }
 
 template <bool B_KC, int EC>
@@ -332,6 +374,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if constexpr (EC == LN_GELU) KMB_LN_LEAN(true, false, 1, false, false, false);
       if constexpr (EC == LN_DGELU_CS) KMB_LN_LEAN(false, false, 2, false, false, true);
       if constexpr (EC == LN_CE) KMB_LN_LEAN(true, false, 5, false, false, false);
+      if constexpr (EC == LN_SCORE) ln_epilogue_score<NJ>(p, acc, r, g, row0w, col0w);
 #undef KMB_LN_LEAN
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -404,4 +447,38 @@ hipError_t kmb_gemm_lean_launch(const KmbGemm& p, hipStream_t stream, uint32_t* 
   const dim3 grid(tiles >= 256 ? 256u : (unsigned)(tiles & ~7L));
   const int ec = ln_class(p);
   return p.b_kc ? ln_launch_layout<true>(ec, p, grid, stream, sched, dyn_first) : ln_launch_layout<false>(ec, p, grid, stream, sched, dyn_first);
+}
+
+// The scoring class (LN_SCORE) has its own entry: it has no output matrix, so it is not one of kmb_op_gemm's epilogues and the tuner never
+// sees it.  Forward layout only (X W^T, both operands K-contiguous), whole 256 x 256 tiles, at least 128 of them (the per-XCD ranges of the
+// persistent grid), bias required (the padded vocabulary columns carry -1e30 there).  stats: [M][N / 64][2] floats.
+const char* kmb_gemm_score_check(const KmbGemm& p, const float* stats) {
+  if (!p.A || !p.B || !p.bias || !stats) return "gemm score: A, B, bias and stats are required";
+  if (!p.a_kc || !p.b_kc) return "gemm score: forward layout only (both operands K-contiguous)";
+  if (p.M <= 0 || (p.M % 256) != 0 || (p.N % 256) != 0 || (p.K % BK) != 0 || p.K / BK < 5)
+    return "gemm score: M and N must be multiples of 256, K a multiple of 64 and at least 320";
+  if ((long)(p.M / 256) * (p.N / 256) < 128) return "gemm score: fewer than 128 tiles of 256 x 256";
+  if (p.act != 0 || p.out_bf16 || p.out_f32 || p.residual || p.drop_thr16 || p.colsum || p.col_scale_n > 0 || p.split_k > 1 || p.preact || p.aux)
+    return "gemm score: the class has no output matrix and no other epilogue option";
+  if (p.lda < p.K || p.ldb < p.K || (p.lda & 7) || (p.ldb & 7)) return "gemm score: lda / ldb must be multiples of 8 and at least K";
+  if ((long)p.lda * 2 * 256 >= (1L << 31) || (long)p.ldb * 2 * 256 >= (1L << 31)) return "gemm score: row stride too large";
+  if (((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15) || ((uintptr_t)p.bias & 15) || ((uintptr_t)stats & 7)) return "gemm score: misaligned operand";
+  return nullptr;
+}
+
+hipError_t kmb_gemm_score_launch(const KmbGemm& p, float* stats, hipStream_t stream) {
+  if (kmb_gemm_score_check(p, stats) != nullptr) return hipErrorInvalidValue;
+  KmbGemm q = p;
+  q.row_sums = stats; q.row_sums_ld = p.N / 64;
+  q.tile_order = p.N >= 32 * 256 ? 8 : 0;   // column blocks for wide outputs, as launch_config sets them for the other classes
+  const long tiles = (long)(p.M / 256) * (p.N / 256);
+  const dim3 grid(tiles >= 256 ? 256u : (unsigned)(tiles & ~7L));
+  static bool attr = false;
+  if (!attr) {
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel_lean<true, LN_SCORE>, hipFuncAttributeMaxDynamicSharedMemorySize, LN_LDS);
+    if (e != hipSuccess) return e;
+    attr = true;
+  }
+  hipLaunchKernelGGL((gemm_kernel_lean<true, LN_SCORE>), grid, dim3(512), LN_LDS, stream, q, (uint32_t*)nullptr, 0);
+  return hipGetLastError();
 }

@@ -23,6 +23,9 @@ void kmb_gemm_set_shared_device(int on);   // persistent variants: hand out ever
 // variant 6 (gemm_lean.hip): the eight-wave persistent 256 x 256 kernel rebuilt around the bare K loop of tools/mfma_loop.hip
 bool kmb_gemm_lean_ok(const KmbGemm& p);
 hipError_t kmb_gemm_lean_launch(const KmbGemm& p, hipStream_t stream, uint32_t* sched, int dyn_first);
+// ... and its scoring class (LN_SCORE): no output matrix, stats [M][N / 64][2] = per row and 64-column block (maximum, sum of exp(v - maximum))
+const char* kmb_gemm_score_check(const KmbGemm& p, const float* stats);
+hipError_t kmb_gemm_score_launch(const KmbGemm& p, float* stats, hipStream_t stream);
 // variant 9 (gemm_pair.hip): two persistent 256 x 128 workgroups per CU, 32-deep stages (forward layout)
 bool kmb_gemm_pair_ok(const KmbGemm& p);
 hipError_t kmb_gemm_pair_launch(const KmbGemm& p, hipStream_t stream);
@@ -114,6 +117,12 @@ hipError_t kmb_ce_pad_bias_launch(const float* bias, int V, int Vpad, float* out
 hipError_t kmb_ce_rows_finish_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const int64_t* labels,
                                      const int32_t* count, float lm_factor, int rows, int d, int V, const bf16_t* H, int ldh,
                                      float* loss_rows, float* srow, float* alpha, bf16_t* ah, bf16_t* P, int ldp, hipStream_t stream);
+// scoring (kmb_score): logp[r] = label_logit[r] - lse(stats row r), 0 in rows whose label is -100 / out of range; stats as kmb_gemm_score_launch leaves them
+hipError_t kmb_score_rows_finish_launch(const float* stats, int nblk, const float* label_logit, const int64_t* labels, int rows, int V,
+                                        float* logp, hipStream_t stream);
+// per batch item the sum of -logp and the number of valid rows over its T rows, in row order; src holds log-probabilities or (src_is_nll) row losses
+hipError_t kmb_score_segments_launch(const float* src, int src_is_nll, const int64_t* labels, int B, int T, int V, float* logp_out,
+                                     float* nll, int32_t* count, hipStream_t stream);
 // out[r] = bf16(alpha[r] * sum_s slab[s][r])
 hipError_t kmb_ce_dgrad_finish_launch(const float* slab, int nslabs, size_t stride, const float* alpha, bf16_t* out, int rows, int d,
                                       hipStream_t stream);

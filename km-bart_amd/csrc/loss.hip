@@ -1151,6 +1151,58 @@ __global__ __launch_bounds__(256) void ce_dgrad_finish_kernel(const float* __res
   *reinterpret_cast<u32x4*>(out + (size_t)r * d + c) = pack8(v);
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// Scoring a given target sequence (kmb_score; reference scripts/filter_reason.py:24-52: log_softmax over the [B, T, V] logits,
+// the label's entry token by token, the mean over labels >= 0 per sample).  The head GEMM's scoring class (gemm_lean.hip
+// LN_SCORE) leaves per row and 64-column block (maximum, sum of exp(v - maximum)); this is the row finish:
+//   logp_r = v_r[label_r] - lse_r,   lse_r = M + log sum_b s_b exp(m_b - M),  M = max_b m_b
+// with the label's logit from ce_label_logit_kernel.  Rows whose label is -100 or out of range get 0.  One wave per row; the
+// blocks are walked lane-strided and folded by a butterfly: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void score_rows_finish_kernel(const float* __restrict__ stats, int nblk, const float* __restrict__ label_logit,
+                                                                const int64_t* __restrict__ labels, int rows, int V, float* __restrict__ logp) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (r >= rows) return;
+  const long long lab = labels[r];
+  if (lab < 0 || lab >= V) {
+    if (lane == 0) logp[r] = 0.f;
+    return;
+  }
+  const kmb_f32x2* st = reinterpret_cast<const kmb_f32x2*>(stats) + (size_t)r * nblk;
+  float m = -INFINITY;
+  for (int i = lane; i < nblk; i += 64) m = fmaxf(m, st[i][0]);
+  m = wave_max(m);
+  float s = 0.f;
+  for (int i = lane; i < nblk; i += 64) {
+    const kmb_f32x2 b = st[i];
+    s += b[1] * expf(b[0] - m);
+  }
+  s = wave_sum(s);
+  if (lane == 0) logp[r] = label_logit[r] - (m + logf(s));
+}
+
+// Per batch item: nll[b] = sum over its T rows, in row order, of -logp of the rows with a valid label, count[b] = their number.
+// src_is_nll: src holds the rows' losses (loss_rows of ce_kernel_reg / ce_kernel_reg_bf16, the fallback head paths) instead of
+// log-probabilities; either way logp_out (may alias src) receives the log-probabilities, 0 in ignored rows.  One thread per item.
+__global__ __launch_bounds__(256) void score_segments_kernel(const float* src, int src_is_nll, const int64_t* __restrict__ labels, int B, int T,
+                                                             int V, float* logp_out, float* __restrict__ nll, int32_t* __restrict__ count) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float a = 0.f;
+  int n = 0;
+  for (int t = 0; t < T; ++t) {
+    const size_t r = (size_t)b * T + t;
+    const long long lab = labels[r];
+    const bool valid = lab >= 0 && lab < V;
+    const float x = src[r];
+    const float lp = valid ? (src_is_nll ? -x : x) : 0.f;
+    logp_out[r] = lp;
+    if (valid) { a -= lp; ++n; }
+  }
+  nll[b] = a;
+  count[b] = n;
+}
+
 }  // namespace
 
 hipError_t kmb_ce_label_logit_launch(const bf16_t* H, int ldh, const bf16_t* E, int lde, const float* bias, const int64_t* labels,
@@ -1180,6 +1232,20 @@ hipError_t kmb_ce_dgrad_finish_launch(const float* slab, int nslabs, size_t stri
   const size_t chunks = (size_t)rows * (d >> 3);
   hipLaunchKernelGGL(ce_dgrad_finish_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, slab, nslabs, stride, alpha,
                      out, rows, d);
+  return hipGetLastError();
+}
+
+hipError_t kmb_score_rows_finish_launch(const float* stats, int nblk, const float* label_logit, const int64_t* labels, int rows, int V,
+                                        float* logp, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
+  if (nblk <= 0 || ((uintptr_t)stats & 7)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(score_rows_finish_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, stats, nblk, label_logit, labels, rows, V, logp);
+  return hipGetLastError();
+}
+hipError_t kmb_score_segments_launch(const float* src, int src_is_nll, const int64_t* labels, int B, int T, int V, float* logp_out,
+                                     float* nll, int32_t* count, hipStream_t stream) {
+  if (B <= 0 || T <= 0) return hipSuccess;
+  hipLaunchKernelGGL(score_segments_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, src, src_is_nll, labels, B, T, V, logp_out, nll, count);
   return hipGetLastError();
 }
 

@@ -111,6 +111,7 @@ PROTOTYPES = {
     "kmb_logits_ld": (C.c_int, [c_p]),
     "kmb_forward": (C.c_int, [c_p, C.POINTER(KmbBatch), C.c_int, C.c_int, c_p, c_p, c_p, c_p]),
     "kmb_forward_ex": (C.c_int, [c_p, C.POINTER(KmbBatch), C.POINTER(KmbForwardOpts), C.c_int, C.c_int, c_p, c_p, c_p, c_p]),
+    "kmb_score": (C.c_int, [c_p, C.POINTER(KmbBatch), c_p, c_p, c_p, C.POINTER(i32), c_p]),
     "kmb_last_logits": (C.c_int, [c_p, c_p, c_p]),
     "kmb_hidden_state": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p]),
     "kmb_attention_probs": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p]),
@@ -177,6 +178,9 @@ PROTOTYPES = {
     "kmb_op_gemm_allrows": (C.c_int, [C.POINTER(KmbGemm), c_p]),
     "kmb_op_gemm_allrows_stats_floats": (C.c_int64, [C.c_int]),
     "kmb_op_gemm_allrows_stats": (C.c_int, [C.POINTER(KmbGemm), c_p, c_p]),
+    "kmb_op_gemm_score_stats_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "kmb_op_gemm_score": (C.c_int, [C.POINTER(KmbGemm), c_p, c_p]),
+    "kmb_op_score_rows_finish": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p, c_p]),
     "kmb_op_gemm_group": (C.c_int, [C.POINTER(KmbGemm), C.c_int32, c_p]),
     "kmb_op_attn_fwd": (C.c_int, [C.POINTER(KmbAttn), c_p]),
     "kmb_op_attn_bwd": (C.c_int, [C.POINTER(KmbAttn), c_p]),

@@ -227,6 +227,31 @@ class Engine:
             self._last_S = S
             return (loss, logits, enc, dec) if want_decoder_states else (loss, logits, enc)
 
+    def score(self, input_ids, image_features, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None,
+              labels=None):
+        """log p(label | image, event, earlier labels) of a GIVEN target sequence (kmb_score; reference
+        scripts/filter_reason.py:24-52 without the [B, T, V] logits).  Returns device tensors (token_logprobs fp32 [B, T], nll fp32 [B]
+        -- a sum --, count int32 [B]); no host synchronisation.  `last_score_path` is 1 when the store-free head ran, 0 for the
+        fallback (KMB_SCORE_FALLBACK=1 forces it)."""
+        if labels is None:
+            raise ValueError("score() needs labels: the sequence to score")
+        with torch.cuda.device(self.device):
+            b, keep, (B, S, T, ntot) = self._batch(input_ids, image_features, attention_mask, decoder_input_ids,
+                                                   decoder_attention_mask, labels)
+            self._ensure_ws(self.lib.kmb_workspace_bytes(self.h, B, S, T, ntot))
+            self._poison()
+            logp = torch.empty((B, T), dtype=torch.float32, device=self.device)
+            nll = torch.empty(B, dtype=torch.float32, device=self.device)
+            count = torch.empty(B, dtype=torch.int32, device=self.device)
+            path = C.c_int32(-1)
+            self.fwd_serial += 1
+            check(self.lib.kmb_score(self.h, C.byref(b), ptr(logp), ptr(nll), ptr(count), C.byref(path), _stream()))
+            self._keep = keep
+            self._last_bt = (B, T)
+            self._last_S = S
+            self.last_score_path = int(path.value)
+            return logp, nll, count
+
     def hidden_states(self, which):
         """`output_hidden_states` of the forward still in the workspace: tuple of [B, T, d] activations of the encoder
         (which = 0: embedding output + every layer's output) or decoder (which = 1) stack."""

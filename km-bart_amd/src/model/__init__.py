@@ -1,6 +1,6 @@
 from src.model.config import MultiModalBartConfig
 from src.model.model import (LazyLogits, MultiModalBartForConditionalGeneration, MultiModalBartForPreTraining,
-                             MultiModalBartModel)
+                             MultiModalBartModel, SequenceScore)
 
 __all__ = ["MultiModalBartConfig", "MultiModalBartForConditionalGeneration", "MultiModalBartForPreTraining",
-           "MultiModalBartModel", "LazyLogits"]
+           "MultiModalBartModel", "LazyLogits", "SequenceScore"]

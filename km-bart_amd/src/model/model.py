@@ -6,6 +6,7 @@ libkmbart_hip.so: this module only marshals tensors, keeps the reference's retur
 does the beam bookkeeping on the host.  There is no CPU forward: calling the model before it has
 been moved to a HIP device raises.
 """
+import collections
 import math
 import os
 from types import SimpleNamespace
@@ -101,6 +102,18 @@ class _LossFn(torch.autograd.Function):
             dtype, device, shape = ctx.enc_meta
             g_enc = ctx.model._engine.encoder_states_grad().to(device=device, dtype=dtype).reshape(shape)
         return None, None, None, g_enc
+
+
+class SequenceScore(collections.namedtuple("SequenceScore", ("token_logprobs", "nll", "count"))):
+    """What `score()` returns, all on the device: token_logprobs fp32 [B, T] (0 where the label is ignored), nll fp32 [B] (the SUM of
+    -token_logprobs over a sample's valid labels), count int32 [B] (their number)."""
+    __slots__ = ()
+
+    @property
+    def perplexity(self):
+        """exp(nll / count) per sample; a sample without a valid label gives NaN (0 / 0), as the reference's mean() of an empty tensor
+        does (scripts/filter_reason.py:17-21)."""
+        return torch.exp(self.nll / self.count.to(torch.float32))
 
 
 class LazyLogits:
@@ -549,6 +562,28 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         if logits is None:
             logits = LazyLogits(eng)
         return (loss, logits) + dec_extra + (enc,) + enc_extra
+
+    def score(self, input_ids, image_features, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None, labels=None):
+        """Scores a GIVEN target sequence: `SequenceScore(token_logprobs, nll, count)` with token_logprobs[b, t] =
+        log_softmax(logits[b, t])[labels[b, t]] -- what the reference's perplexity filter computes from `forward(...)[0]` token by token
+        (scripts/filter_reason.py:17-44) -- without the [B, T, V] logits: the head keeps per-row softmax statistics only.  Eval-mode
+        arithmetic whatever `self.training` is (no dropout, no gradient state); everything stays on the device, nothing synchronises.
+        `decoder_input_ids` / `decoder_attention_mask` default as in `forward`.  Out-of-range labels are flagged like `forward`'s
+        (`_engine.check_inputs()`)."""
+        eng = self._need_engine()
+        if labels is None:
+            raise ValueError("score() needs labels: the sequence to score")
+        if decoder_input_ids is None:   # as forward: transformers shift_tokens_right(input_ids, pad)
+            pad = self.config.pad_token_id
+            prev = input_ids.clone()
+            idx_eos = (input_ids.ne(pad).sum(dim=1) - 1).unsqueeze(-1)
+            prev[:, 0] = input_ids.gather(1, idx_eos).squeeze()
+            prev[:, 1:] = input_ids[:, :-1]
+            decoder_input_ids = prev
+        if decoder_attention_mask is None and bool((decoder_input_ids == self.config.pad_token_id).any()):
+            decoder_attention_mask = decoder_input_ids.ne(self.config.pad_token_id).long()
+        logp, nll, count = eng.score(input_ids, image_features, attention_mask, decoder_input_ids, decoder_attention_mask, labels)
+        return SequenceScore(logp, nll, count)
 
     def _resolve_use_cache(self, use_cache, has_labels, decoder_input_ids, decoder_cached_states, output_attentions,
                            output_hidden_states):
