@@ -397,6 +397,14 @@ int64_t kmb_gen_workspace_bytes(const kmb_handle* h, int B, int S, int num_beams
  * Process-wide; results do not depend on it. */
 int kmb_gemm_shared_device(int on);
 
+/* Diagnostic: what kmb_op_gemm would do with *p, decided exactly as the launch decides it -- no GPU call, the operands
+ * are never dereferenced (any aligned non-null addresses do).  forced_variant > 0: as under KMB_GEMM_VARIANT=forced_variant;
+ * 0: the library's own choice.  out[0] = 0: one triple follows, the launch itself; out[0] = 1: the first launch of this
+ * shape times candidates, one triple each in the tuner's order.  A triple is (configuration = variant | tile order << 4
+ * (variant 0: the narrow kernel), kernel variant that runs it (honours kmb_gemm_shared_device), tile_order it is launched
+ * with).  Returns the number of int32 words written, -1 for a problem kmb_op_gemm refuses or a cap too small. */
+int kmb_debug_gemm_route(const KmbGemm* p, int forced_variant, int32_t* out, int32_t cap);
+
 /* ================= data parallelism: native RCCL (vcg_train.py:98 DDP, src/utils.py:9-17 init_process_group) =================
  * One process per GPU; the library owns the communicator and a communication stream, and a step's whole gradient
  * exchange is ONE call: every gradient bucket (kmb_bucket_range, backward completion order) is reduced on the

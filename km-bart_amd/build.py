@@ -41,7 +41,7 @@ def build(force=False, verbose=True):
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src + ".o")
-        deps = [s] + headers + ([os.path.join(CSRC, "gemm.hip")] if src in ("gemm_pair.hip", "gemm_lean.hip") else [])   # they #include gemm.hip
+        deps = [s] + headers
         if force or _stale(o, deps):
             jobs.append((s, o))
 

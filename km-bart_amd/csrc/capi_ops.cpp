@@ -204,6 +204,11 @@ int kmb_gemm_shared_device(int on) {
   kmb_gemm_set_shared_device(on);
   return 0;
 }
+int kmb_debug_gemm_route(const KmbGemm* p, int forced_variant, int32_t* out, int32_t cap) {
+  if (!p || !out || cap < 1 || forced_variant < 0) return -1;
+  if (kmb_gemm_check(*p) != nullptr) return -1;
+  return kmb_gemm_route(*p, forced_variant, out, cap);
+}
 int kmb_beam_merge(const float* val, const int32_t* idx, int B, int num_beams, int k, int V, int32_t* out, void* stream) {
   return hipfail(kmb_beam_merge_launch(val, idx, B, num_beams, k, V, out, -1, nullptr, nullptr, nullptr, (hipStream_t)stream), "beam_merge");
 }

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "diag.h"
 #include "kernels.h"
+#include "gemm_device.h"
 
 // ---- diagnostic build only (tools/gemm_stamps.py compiles this file with -DKMB_GEMM_STAMP into a separate library):
 // per-workgroup s_memrealtime stamps (100 MHz) + HW_ID / XCC_ID, to read prologue / loop / epilogue / dispatch-gap
@@ -65,40 +66,10 @@ extern "C" int kmb_debug_set_stamps(void* p) {
 #define KMB_STAMP_VALUE(i, v)
 #endif
 
-// KMB_PLAIN_STORES (experiment builds, build.py --variant): default-policy stores in the persistent kernels' epilogues
-// instead of non-temporal ones
-#ifdef KMB_PLAIN_STORES
-#define KMB_NT_STORE(v, p) (*(p) = (v))
-#else
-#define KMB_NT_STORE(v, p) __builtin_nontemporal_store(v, p)
-#endif
-
-// The L2 touch of the persistent kernels: a load whose result nobody reads.  Round 5: it is a 4-byte LDS-DMA into a dummy LDS word
-// of the issuing wave (`lds`: 256 bytes that nothing reads while a touch can be in flight -- the wave's epilogue staging image,
-// idle during the K loop) -- NO register destination.  Rounds 2-4 gave it a register: "=v" (a fresh value per touch: the allocator
-// reused the register while the load was in flight -- wrong bits), one "+v" web (split under pressure: memory fault), then v255 with
-// __attribute__((amdgpu_num_vgpr(255))), on the belief that the allocator then never hands out v255.  It does (found by grepping the ISA of every kernel with a touch for other uses of v255,
-// round 5: the eight-wave and the two-workgroup kernels are compiled with all 256 registers, v255 among them -- the attribute does not
-// cap a kernel whose budget waves_per_eu fixes); what kept the results right was the ORDER of the counted waits (a touch is older
-// than the pieces the next wait leaves outstanding), not the register.  A touch still counts as one vector-memory operation, so the
-// kernels' counted waits are unchanged; results are bit-identical (tests/test_gemm_variants_gpu.py).
-// (inline asm, not __builtin_amdgcn_global_load_lds: the builtin spends eight scalar instructions per touch on turning the generic
-//  LDS pointer into M0 -- measured -0.5...-1 % of a step; here M0 is saved, set from a 32-bit LDS address kept in a scalar
-//  register and restored inside ONE statement, as the guide's glds16_asm recipe does.  `lds_u32`: kmb_lds_addr(ptr), wave-uniform.)
-#define KMB_L2_TOUCH(voff, sbase, lds_u32)                                                                                    \
-  do {                                                                                                                        \
-    unsigned kmb_m0_keep_;                                                                                                    \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"       \
-                 : "=&s"(kmb_m0_keep_) : "v"(voff), "s"(sbase), "s"(lds_u32) : "memory");                                     \
-  } while (0)
-__device__ __forceinline__ unsigned kmb_lds_addr(const void* p) {   // the 32-bit LDS address of a (generic) pointer into shared memory, in a scalar register
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) const void*)p);
-}
 namespace {
 
 int g_shared_device = 0;   // kmb_gemm_shared_device(): other kernels (RCCL) hold CUs while the GEMMs run
 
-constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int STAGE_BYTES = (BM * BK + BN * BK) * 2;  // 32 KB
 constexpr int EPI_LD = BN + 4;                        // fp32 staging row stride
 constexpr int CS256 = 16 * 128 * 4, CS512 = 32 * 128 * 4;  // column-sum scratch behind the fp32 staging (bias gradients)
@@ -120,7 +91,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
 }
 
-__device__ __forceinline__ int swz_nkc(int krow) { return (krow & 3) | (((krow >> 3) & 1) << 2); }
 
 // ---- global -> register staging of one 128x64 (KC) or 64x128 (non-KC) tile: 4 chunks / thread ----
 template <bool KC>
@@ -163,55 +133,6 @@ __device__ __forceinline__ void store_tile(char* lds, int tid, const u32x4 (&reg
   }
 }
 
-// fragment for MFMA 16x16x32: 16 rows (r = lane&15) x 32 k (8 per lane group g = lane>>4)
-// The transposing LDS reads (`ds_read_b64_tr_b16`, the token-major operand of the data- and weight-gradient layouts) as INLINE ASM (late round 5).
-// hipcc puts `s_waitcnt vmcnt(0)` in front of the first __builtin_amdgcn_ds_read_tr16_b64 behind an LDS-DMA issue: the intrinsic carries no memory
-// operand, so the wait-count pass assumes it may read what the DMA is writing.  The K loops issue the NEXT stage's DMA pieces and then read fragments
-// of the CURRENT one -- so in every kernel with a token-major operand the stage requested a moment ago was waited for at once: prefetch distance
-// zero, two such stalls per K step in the weight-gradient kernel (found on the ISA: one counted wait per step in the K-contiguous kernels, two or
-// three vmcnt(0) in the others; their matrix pipes were busy 29-40 % against 42 %).  As asm the compiler sees neither an LDS read (no wait in
-// front) nor its result's latency (no wait before the use): the consumers' wait is an explicit `s_waitcnt lgkmcnt(0)` at the top of every
-// sub-phase (KMB_TR_SYNC, fenced by sched_barriers: fragments are always consumed one sub-phase after they are requested) and behind the K loop of
-// the persistent kernels (the next tile's first fragments live across the epilogue).  Sound only if no instruction names such a register between
-// the read and the wait -- a property of the compiled code: tools/gemm_tr_asm_hazards.py walks the ISA's control-flow graph, and
-// tests/test_cabi_cpu.py::test_gemm_asm_transposing_reads_are_waited_for runs it on every build.  Same arithmetic in the same order: outputs
-// bit-identical to the intrinsic's (tools/gemm_tr_asm_ab.py: md5 per shape).  Kernels: v7 (+ the grouped weight gradients), v8, v11 with 256-wide
-// tiles (four and eight waves) -- the ones compared on the GPU when this went in (round 5); v7d, the 128- / 192-wide v11 tiles and gemm_lean.hip:
-// KMB_TR_ALL (round 6; gemm_lean.hip's L2 touch moved off v255 first -- with asm reads the allocator hands that register out).
-// -DKMB_TR_BUILTIN: the intrinsic everywhere (A/B builds).  profiles/r05_gemm_transposing_reads_asm.md.
-// Round 6: EVERY kernel (KMB_TR_ALL: also the four-stage kernel, the 128- / 192-wide persistent tiles and gemm_lean.hip) -- one GPU call compared
-// the md5 of seven shapes x nine launch variants between the intrinsic build, round 5's partial build and this one: all identical and stable
-// (profiles/r06_gemm_transposing_reads_all_variants.txt; the four-stage kernel's lone workgroups -33 %, the 128- / 192-wide weight gradients -12...-21 %).
-#ifndef KMB_TR_BUILTIN
-constexpr bool KMB_TR_ALL = true;
-#else
-constexpr bool KMB_TR_ALL = false;
-#endif
-#ifndef KMB_TR_BUILTIN
-__device__ __forceinline__ s16x4 kmb_tr_read_asm(const char* ptr) {
-  s16x4 t;
-  const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)ptr;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(t) : "v"(a));
-  return t;
-}
-// the same read at `addr` (32-bit LDS address in a register) + a compile-time byte offset in the instruction's offset field: one address
-// register serves every (kk, hh) of a fragment column (gemm_lean.hip: without it each of the 16 reads of a stage kept its own hoisted address)
-template <int OFF>
-__device__ __forceinline__ s16x4 kmb_tr_read_asm_off(uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
-  s16x4 t;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(t) : "v"(addr), "n"(OFF));
-  return t;
-}
-#define KMB_TR_SYNC()                                   \
-  do {                                                  \
-    __builtin_amdgcn_sched_barrier(0);                  \
-    __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0); the builtin, not asm: hipcc's own wait tracking then knows the LDS queue is empty (as asm it re-waited, lgkmcnt(0), in front of the next use of a plain fragment read -- right behind the asm reads just issued) */ \
-    __builtin_amdgcn_sched_barrier(0);                  \
-  } while (0)
-#else
-#define KMB_TR_SYNC() do { } while (0)
-#endif
 template <bool KC, bool ASM = false>
 __device__ __forceinline__ bf16x8 read_frag(const char* lds, int rowtile16, int kk, int r, int g) {
   if (KC) {
@@ -606,10 +527,6 @@ __device__ __forceinline__ void dma_offsets(uint32_t (&off)[4], int ld, int r0, 
   }
 }
 
-__device__ __forceinline__ void dma_piece(const char* gbase, uint32_t off, char* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + off),
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
 // the same with the non-temporal cache policy (aux bit 1 = nt on gfx950): the line is allocated in L2 as the first to leave.  For
 // the STREAMED operand of a persistent launch (the activation panel: read by the column tiles of one round, never again) so
 // that it does not push the REUSED one (the weight panels, re-read every round) out of a 4 MB L2.  Experiment: -DKMB_A_NT.
@@ -949,7 +866,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_v7d(const KmbGemm p) {   /
   v7d_tile<A_KC, B_KC>(p, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
-#ifndef KMB_GEMM_DEVICE_ONLY
 // Grouped weight gradients (round 5): ONE launch walks the 128x128 tiles of up to KMB_GEMM_GROUP_MAX independent problems of the
 // weight-gradient layout (dW = dY^T X: both operands token-major), each tile over the WHOLE token reduction -- no K slices,
 // no fp32 slabs, no reduction pass.  For the small batches of the reference's default (64 samples: 2048-4096 tokens) a layer's
@@ -979,34 +895,10 @@ __global__ __launch_bounds__(256, 2) void gemm_group_wgrad_kernel(const KmbGemmG
   if (local >= grp.blocks[k]) return;   // padding up to the next multiple of 8
   v7_tile<false, false>(grp.p[k], smem, local, grp.blocks[k]);
 }
-#endif
 
 // ------------------------------------------------------------------------------------------
 // fragment reads for tiles that are 256 rows (columns) tall (v8)
 
-template <bool KC, int ROWS, bool ASM = false>
-__device__ __forceinline__ bf16x8 read_frag3(const char* lds, int rowtile16, int kk, int r, int g) {
-  if (KC) {
-    const int row = rowtile16 * 16 + r;
-    const int c = kk * 4 + g;
-    return *reinterpret_cast<const bf16x8*>(lds + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-  } else {
-    bf16x8 out;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int krow = kk * 32 + g * 8 + hh * 4 + (r >> 2);
-      const int off = krow * (ROWS * 2) + ((rowtile16 ^ swz_nkc(krow)) << 5) + ((r & 3) << 3);
-#ifndef KMB_TR_BUILTIN
-      const s16x4 t = ASM ? kmb_tr_read_asm(lds + off) : __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(lds + off));
-#else
-      const s16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s16x4*)(lds + off));
-#endif
-      out[hh * 4 + 0] = t[0]; out[hh * 4 + 1] = t[1]; out[hh * 4 + 2] = t[2]; out[hh * 4 + 3] = t[3];
-    }
-    return out;
-  }
-}
 
 // 256x256x64 tile, 512 threads = 8 waves (2x4), each wave 128x64 (8x4 MFMA tiles); two 64 KB stages filled by
 // LDS-DMA; epilogue in two column halves (the fp32 staging image does not fit otherwise).
@@ -1252,7 +1144,6 @@ __global__ __launch_bounds__(512) void gemm_kernel_v8(const KmbGemm p) {
 }
 
 
-#ifndef KMB_GEMM_DEVICE_ONLY   // (gemm_rolesplit.hip includes this file for the device helpers above and below only)
 // ------------------------------------------------------------------------------------------
 // "All rows" kernel: the vocabulary projection of a generation decode step (R = batch x beams <= 320 rows, N = 50320, K = 768,
 // forward layout, fp32 logits).  The 128x128 kernel re-reads the R activation rows for each of 394 column tiles and the tied
@@ -1472,7 +1363,6 @@ __global__ __launch_bounds__(512) void gemm_kernel_allrows(const KmbGemm p, floa
   KMB_STAMP(4);
 }
 
-#endif  // KMB_GEMM_DEVICE_ONLY
 
 // ------------------------------------------------------------------------------------------
 // v11: persistent 256x256 tile.  One workgroup per CU (grid = 256), four waves (2x2), each wave a 128x128 block of C
@@ -1496,28 +1386,6 @@ __global__ __launch_bounds__(512) void gemm_kernel_allrows(const KmbGemm p, floa
 // workgroups of an XCD up to 12 us apart (no HBM burst limit at this size).  Whole kernel 76-77 us against 90 us for
 // v8; the vendor library's stream-K kernel (256 workgroups x 256 threads, 256x256x64, tools/gemm_yardstick.py) takes
 // 70.5 us per call in a back-to-back loop on this shape.
-template <bool KC, int NP = 8>
-__device__ __forceinline__ void dma_offsets256w4(uint32_t (&off)[NP], int ld, int r0, int R, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const int piece = wave * NP + i;  // 4 * NP pieces of 1 KiB per tile (32 for 256 rows, 24 for a 192-row KC image)
-    if (KC) {
-      const int row = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ ((row >> 1) & 7);
-      int grow = r0 + row;
-      grow = grow < R ? grow : R - 1;
-      off[i] = (uint32_t)(((grow - r0) * ld + c * 8) * 2);
-    } else {
-      const int krow = piece * 2 + (lane >> 5);
-      const int ps = lane & 31;
-      const int c32 = (ps >> 1) ^ swz_nkc(krow);
-      int m = r0 + c32 * 16 + (ps & 1) * 8;
-      const int mlast = ((R - 1) >> 3) << 3;
-      m = m < R ? m : mlast;
-      off[i] = (uint32_t)((krow * ld + (m - r0)) * 2);
-    }
-  }
-}
 
 constexpr int EPW_BYTES = 16 * 128 * 4;            // wave-private fp32 staging: 16 rows x 128 columns, XOR-swizzled
 constexpr int LDS11 = 2 * ST4 + 4 * EPW_BYTES;     // 160 KB: the whole CU
@@ -1577,268 +1445,6 @@ __device__ __forceinline__ void v11_epilogue(const KmbGemm& p, f32x4 (&acc)[8][N
   }
 }
 
-// The hot epilogue classes of v11, everything decided at compile time.  With ONE wave per SIMD nothing hides an
-// instruction: the general body (run-time option tests, edge handling, spilled-SGPR reloads) costs ~450 instructions
-// per 16-row chunk = 7 us per 256x256 tile (in-kernel stamps), as long as the tile's MFMAs at K = 256.  Interior wave
-// blocks with a bf16 output only; same operation order as gemm_epilogue_body (bit-identical results).
-//   BIAS: + bias[col];  SCALE: * col_scale (the whole wave block lies in the scaled columns);  ACT 1: GeLU (+ optional
-//   pre-activation store), 2: * GeLU'(aux);  DROP: dropout mask;  RES: + residual;  CS: column sums.
-template <bool BIAS, bool SCALE, int ACT, bool RES, bool DROP, bool CS, int WROWS, bool F32 = false, int NJ = 8>
-__device__ __forceinline__ void v11_epilogue_lean(const KmbGemm& p, f32x4 (&acc)[8][NJ], float* ef, int lane, int r, int g,
-                                                  int row0w, int col0w) {
-  constexpr int WCOLS = NJ * 16;
-  // lane map of the row-major pass: CL column-lanes of 8 columns x RPI rows per iteration, NIT iterations per 16-row chunk
-  // (128- and 96-column blocks: 16 x 4, four iterations; the 8-wave kernel's 64-column blocks: 8 x 8, two iterations)
-  constexpr int CL = WCOLS > 64 ? 16 : 8, RPI = 64 / CL, NIT = 16 / RPI, LDE = WCOLS > 64 ? 128 : 64;
-  const int lr = lane / CL;
-  // a 96-column wave block (256x192 tile) keeps the 128-column lane map: the last four column-lanes of every row group
-  // redo column-lane 11's work on the same addresses (same values: harmless duplicate stores) instead of branching
-  // a 96- / 48-column wave block keeps the 128- / 64-column lane map: the column-lanes past the block redo the last
-  // column-lane's work on the same addresses (same values: harmless duplicate stores) instead of branching
-  const int c8 = ((lane % CL) * 8 < WCOLS) ? (lane % CL) * 8 : WCOLS - 8;
-  const int gcol = col0w + c8;
-  kmb_f32x2 bias2[4], csum2[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    bias2[e] = BIAS ? kmb_f32x2{p.bias[gcol + 2 * e], p.bias[gcol + 2 * e + 1]} : kmb_f32x2{0.f, 0.f};
-    csum2[e] = kmb_f32x2{0.f, 0.f};
-  }
-  const kmb_f32x2 scale2 = {p.col_scale, p.col_scale};
-  const kmb_f32x2 dscale2 = {p.drop_scale, p.drop_scale};
-  // staging write (transposed accumulators: lane (r, g) holds C[16 i + r][16 j + 4 g .. +3]) and read addresses
-  // Swizzle of a staged row: its 16-byte groups XORed with the row's low three bits.  Writes: the 8 lanes of a ds_write_b128
-  // group (8 rows, one column group) spread over all 32 banks.  Reads: a lane of the row-major pass reads its eight floats as
-  // two ds_read_b128, and the 16 lanes of a read group (two rows of different parity) then cover all 64 banks.  (Rounds 1-3
-  // XORed at 32-byte granularity: every read asked for the even 16-byte groups only and the writes for every other one --
-  // two-way conflicts on both, 15-25 % of the LDS cycles of the forward kernels: tools/pmc_stalls.sh.)
-  float* const wbase = ef + r * LDE;
-  const int sw = (r & 7) << 2;
-  auto stage = [&](const f32x4 (&a)[NJ]) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) *reinterpret_cast<f32x4*>(wbase + ((j * 16 + g * 4) ^ sw)) = a[j];
-    asm volatile("" ::: "memory");
-  };
-  const float* rd[NIT];   // this lane's floats 0-3 of row-iteration it; floats 4-7 are rd_hi floats further (RPI is even: the row parity is lr's)
-#pragma unroll
-  for (int it = 0; it < NIT; ++it)
-    rd[it] = ef + (lr + RPI * it) * LDE + (c8 ^ (((lr + RPI * it) & 7) << 2));
-  const int rd_hi = (lr & 1) ? -4 : 4;
-  // row pointers of this lane's first row; a row-iteration is 4 rows further, a chunk 16
-  bf16_t* out = F32 ? nullptr : p.out_bf16 + (size_t)(row0w + lr) * p.ld_out_bf16 + gcol;
-  float* out32 = F32 ? p.out_f32 + (size_t)(row0w + lr) * p.ld_out_f32 + gcol : nullptr;   // fp32 logits (ld % 4 == 0)
-  bf16_t* pre = (ACT == 1 && p.preact != nullptr) ? p.preact + (size_t)(row0w + lr) * p.ld_preact + gcol : nullptr;
-  const bf16_t* side = nullptr;   // residual (RES) or GeLU' argument (ACT 2): one 16-byte load per row
-  size_t ld_side = 0;
-  if (RES) { side = p.residual + (size_t)(row0w + lr) * p.ld_res + gcol; ld_side = (size_t)p.ld_res; }
-  if (ACT == 2) { side = p.aux + (size_t)(row0w + lr) * p.ld_aux + gcol; ld_side = (size_t)p.ld_aux; }
-  constexpr bool SIDE = RES || ACT == 2;
-  static_assert(!(RES && ACT == 2), "one side stream");
-  // Side loads run two chunks ahead of their use (a chunk is ~0.3 us, an HBM miss longer).  The chunks are walked in pairs:
-  // even chunks keep their side values in sE / hE, odd ones in sO / hO; a chunk first consumes its registers (unpacks them)
-  // and then requests chunk i + 2 into the SAME registers, so the loop-carried value is defined by the load itself.  (Rounds
-  // 1-3 rotated three register sets, s0 <- s1 <- s2, at the bottom of a one-chunk loop: the copy s1 <- s2 is a USE of the load
-  // issued in that same iteration, so hipcc put `s_waitcnt vmcnt(0)` into every chunk -- the prefetch distance was zero and
-  // each chunk also waited for its own stores: 10 us of the fc2 data-gradient tile's epilogue, tools/epilogue_burst.py.)
-  // The eight-wave kernels (NIT = 2: 128 registers in all; with the pair loop they spilled, and a scratch access in the K
-  // loop breaks its counted vmcnt waits) use ONE register set and a one-chunk distance: consume, request chunk i + 1, compute
-  // chunk i -- their second wave per SIMD covers the rest.
-  constexpr bool PAIRS = NIT == 4;
-  constexpr int AHEAD = PAIRS ? 2 : 1;
-  u32x4 sE[NIT];
-  [[maybe_unused]] u32x4 sO[NIT];
-  if (SIDE) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      sE[it] = *reinterpret_cast<const u32x4*>(side + (size_t)(RPI * it) * ld_side);
-      if constexpr (PAIRS) sO[it] = *reinterpret_cast<const u32x4*>(side + (size_t)(16 + RPI * it) * ld_side);
-    }
-  }
-  // act 5: the rows' shifts, loaded like the side operand two chunks ahead of their use (a load at the point of use exposed
-  // its latency in every row-iteration: the head's forward GEMM 2.24 -> 3.19 ms)
-  float hE[NIT];
-  [[maybe_unused]] float hO[NIT];
-  const float* shift_base = ACT == 5 ? p.row_shift + row0w + lr : nullptr;
-  if constexpr (ACT == 5) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      hE[it] = shift_base[RPI * it];
-      if constexpr (PAIRS) hO[it] = shift_base[16 + RPI * it];
-    }
-  }
-  auto stage_chunk = [&](int i) {
-    switch (i) {   // static accumulator indices in every arm (a run-time index would put acc in scratch)
-      case 0: stage(acc[0]); break;
-      case 1: stage(acc[1]); break;
-      case 2: stage(acc[2]); break;
-      case 3: stage(acc[3]); break;
-      case 4: stage(acc[4]); break;
-      case 5: stage(acc[5]); break;
-      case 6: stage(acc[6]); break;
-      default: stage(acc[7]); break;
-    }
-  };
-  static_assert((WROWS / 16) % 2 == 0, "chunks are walked in pairs");
-  auto chunk = [&](const int i, u32x4 (&sv)[NIT], float (&hv)[NIT]) {
-    // this chunk's side values out of their registers, then chunk i + 2's requested into them (the last two chunks re-read
-    // rows that are in cache; never used)
-    [[maybe_unused]] float su[SIDE ? NIT : 1][8];
-    [[maybe_unused]] float hc[ACT == 5 ? NIT : 1];
-    const int ahead = i + AHEAD < WROWS / 16 ? i + AHEAD : WROWS / 16 - 1;
-    if (SIDE) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) unpack8(sv[it], su[it]);
-      __builtin_amdgcn_sched_barrier(0);   // the unpacks stay in front of the reload of their source registers
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) sv[it] = *reinterpret_cast<const u32x4*>(side + (size_t)(16 * ahead + RPI * it) * ld_side);
-    }
-    if constexpr (ACT == 5) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) hc[it] = hv[it];
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(hc[it]));   // a value of its own, not an alias of the register being reloaded
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) hv[it] = shift_base[16 * ahead + RPI * it];
-    }
-    // this chunk's rows out of LDS first, then the next chunk's accumulators into the same image: the LDS executes
-    // a wave's accesses in order, so the writes queue behind the reads and their latency hides under this chunk's math
-    f32x4 lo4[NIT], hi4[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      lo4[it] = *reinterpret_cast<const f32x4*>(rd[it]);
-      hi4[it] = *reinterpret_cast<const f32x4*>(rd[it] + rd_hi);
-    }
-    asm volatile("" ::: "memory");
-    if (i + 1 < WROWS / 16) stage_chunk(i + 1);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const f32x4 lo = lo4[it];
-      const f32x4 hi = hi4[it];
-      kmb_f32x2 v[4] = {{lo[0], lo[1]}, {lo[2], lo[3]}, {hi[0], hi[1]}, {hi[2], hi[3]}};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (BIAS) v[e] = v[e] + bias2[e];
-        if (SCALE) v[e] = v[e] * scale2;
-      }
-      const size_t roff = (size_t)(16 * i + RPI * it);
-      if constexpr (ACT == 5) {
-        // tied-head cross-entropy: exp(v - shift[row]) is what is stored; the row's fp32 sum over this wave block and the
-        // shifted value at the label's column go to the side buffers (see KmbGemm)
-        static_assert(ACT != 5 || WCOLS == 64 || WCOLS == 128, "act 5: 64- or 128-column wave blocks");
-        const int grow = row0w + lr + 16 * i + RPI * it;
-        const float c = hc[it];
-        const kmb_f32x2 c2 = {c, c};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] - c2;
-        if (p.pick_col != nullptr) {   // uniform; optional (the engine does without: the shift IS the label's logit)
-          const int rel = (int)((long long)p.pick_col[grow] - (long long)gcol);   // the label's column relative to this lane's eight
-          if (rel >= 0 && rel < 8) {
-            float picked = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (rel == 2 * e) picked = v[e][0];
-              if (rel == 2 * e + 1) picked = v[e][1];
-            }
-            p.pick_out[grow] = picked;
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          // 2^115 bounds a stored value and a 50k-column row sum inside fp32 / bf16: a logit more than 80 above the label's (a
-          // row whose loss exceeds 80 nats) saturates instead of turning the row's sum, loss and gradients into inf / NaN
-          const kmb_f32x2 t = v[e] * 1.4426950408889634f;
-          v[e] = kmb_f32x2{__builtin_amdgcn_exp2f(fminf(t[0], 115.f)), __builtin_amdgcn_exp2f(fminf(t[1], 115.f))};
-        }
-        float sum = (v[0][0] + v[0][1]) + (v[1][0] + v[1][1]) + ((v[2][0] + v[2][1]) + (v[3][0] + v[3][1]));
-#pragma unroll
-        for (int o = 1; o < CL; o <<= 1) sum += __shfl_xor(sum, o);   // the CL column-lanes of a row are consecutive lanes
-        if ((lane % CL) == 0) {
-          float* slot = p.row_sums + (size_t)grow * p.row_sums_ld + (col0w >> 6);
-          slot[0] = sum;
-          if (WCOLS == 128) slot[1] = 0.f;
-        }
-      } else if (ACT == 1) {
-        if (pre != nullptr) {   // GeLU and GeLU' from one evaluation; the derivative is stored for backward (ACT 2)
-          kmb_f32x2 dv[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            kmb_f32x2 y;
-            gelu_both2(v[e], y, dv[e]);
-            v[e] = y;
-          }
-          const u32x4 pk = {pack2bf(dv[0][0], dv[0][1]), pack2bf(dv[1][0], dv[1][1]), pack2bf(dv[2][0], dv[2][1]), pack2bf(dv[3][0], dv[3][1])};
-          KMB_NT_STORE(pk, reinterpret_cast<u32x4*>(pre + roff * p.ld_preact));
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = gelu2(v[e]);
-        }
-      } else if (ACT == 2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] * kmb_f32x2{su[it][2 * e], su[it][2 * e + 1]};
-      }
-      if (DROP) {
-        const uint32_t grow = (uint32_t)(row0w + lr + 16 * i + RPI * it);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const kmb_f32x2 kept = v[e] * dscale2;
-          v[e][0] = drop_keep(p.drop_seed, grow, (uint32_t)(gcol + 2 * e), p.drop_thr16) ? kept[0] : 0.f;
-          v[e][1] = drop_keep(p.drop_seed, grow, (uint32_t)(gcol + 2 * e + 1), p.drop_thr16) ? kept[1] : 0.f;
-        }
-      }
-      if (RES) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] + kmb_f32x2{su[it][2 * e], su[it][2 * e + 1]};
-      }
-      if (CS) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) csum2[e] = csum2[e] + v[e];
-      }
-      if (F32) {
-        float* o = out32 + roff * p.ld_out_f32;
-        KMB_NT_STORE((f32x4{v[0][0], v[0][1], v[1][0], v[1][1]}), reinterpret_cast<f32x4*>(o));
-        KMB_NT_STORE((f32x4{v[2][0], v[2][1], v[3][0], v[3][1]}), reinterpret_cast<f32x4*>(o + 4));
-      } else {
-        const u32x4 pk = {pack2bf(v[0][0], v[0][1]), pack2bf(v[1][0], v[1][1]), pack2bf(v[2][0], v[2][1]), pack2bf(v[3][0], v[3][1])};
-#ifdef KMB_PLAIN_FFN_OUT   // experiment build: the FFN's wide activations (GeLU output, its gradient) with default-policy stores
-        if (ACT == 1 || ACT == 2) *reinterpret_cast<u32x4*>(out + roff * p.ld_out_bf16) = pk;
-        else KMB_NT_STORE(pk, reinterpret_cast<u32x4*>(out + roff * p.ld_out_bf16));
-#else
-        KMB_NT_STORE(pk, reinterpret_cast<u32x4*>(out + roff * p.ld_out_bf16));
-#endif
-      }
-    }
-  };
-  stage_chunk(0);
-  if constexpr (PAIRS) {
-#pragma unroll 1
-    for (int i = 0; i < WROWS / 16; i += 2) {
-      chunk(i, sE, hE);
-      chunk(i + 1, sO, hO);
-    }
-  } else {
-#pragma unroll 1
-    for (int i = 0; i < WROWS / 16; ++i) chunk(i, sE, hE);
-  }
-  if (CS) {
-    float csum[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { csum[2 * e] = csum2[e][0]; csum[2 * e + 1] = csum2[e][1]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {   // fold the row-lanes
-      if (CL == 8) csum[e] += __shfl_xor(csum[e], 8);
-      csum[e] += __shfl_xor(csum[e], 16);
-      csum[e] += __shfl_xor(csum[e], 32);
-    }
-    if (lane < CL) {
-      const int prow = row0w >> 6;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        p.colsum[(size_t)prow * p.N + gcol + e] = csum[e];
-        if (WROWS == 128) p.colsum[(size_t)(prow + 1) * p.N + gcol + e] = 0.f;
-      }
-    }
-  }
-}
 
 // BNT = 256: waves 2x2, each 128x128.  BNT = 128 (variant 12): waves 4x1, each 64x128 -- twice as many tiles, for shapes
 // whose 256x256 tile count is not a multiple of the 256 workgroups (N = 768: 1.5 tiles per workgroup -> 3).
@@ -2438,7 +2044,6 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
   retire();
 }
 
-#ifndef KMB_GEMM_DEVICE_ONLY
 // ------------------------------------------------------------------------------------------
 // Narrow tile for the generation path.  A decode step multiplies M = batch x beams rows (320 at the benchmark
 // setting) by every weight matrix: with 128x128 tiles that is 18-72 workgroups on 256 CUs and each launch costs a
@@ -2609,10 +2214,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_narrow(const KmbGemm p) {
 // (instruction fetch, not the stores, bounded the generic one), hoisted epilogue loads, hardware bf16 conversion,
 // split-K for the weight gradients, per-shape choice between the 128x128 and 256x256 tiles and the XCD tile order.
 
-#endif  // KMB_GEMM_DEVICE_ONLY
 }  // namespace
 
-#ifndef KMB_GEMM_DEVICE_ONLY   // host side: checks, launch rules, tuner
 void kmb_gemm_set_shared_device(int on) { g_shared_device = on ? 1 : 0; }
 
 const char* kmb_gemm_check(const KmbGemm& p) {
@@ -2676,78 +2279,6 @@ uint32_t* v11_sched_slot(hipStream_t stream) {
   return it->second.base + (size_t)(it->second.seq++ % NSLOT) * 16;
 }
 
-// variant 1: register-staged 128x128 (any K); 7: LDS-DMA + pipelined 128x128; 8: LDS-DMA + pipelined 256x256;
-// 10: role-split persistent 256x128 (eight waves: one group multiplies while the other fetches and runs the previous tile's epilogue);
-// 11 / 12 / 13: persistent 256x256 / 256x128 / 256x192 (four waves); 14 / 15: persistent 256x256 / 256x192, eight waves
-hipError_t launch_variant(int variant, const KmbGemm& p, hipStream_t stream) {
-  const int nsl = p.split_k > 1 ? p.split_k : 1;
-  if (variant == 6)   // eight-wave persistent kernel around the bare K loop (gemm_lean.hip); tiles from a counter while the device is shared
-    return kmb_gemm_lean_launch(p, stream, g_shared_device ? v11_sched_slot(stream) : nullptr, g_shared_device);
-  if (variant == 9) {   // two workgroups per CU (gemm_pair.hip)
-    // its tiles are dealt statically: while another kernel (RCCL, kmb_gemm_shared_device) holds CUs, the persistent 256 x 128
-    // kernel with dynamic hand-out takes the launch instead (same tile shape: every launch variant 9 admits, it admits)
-    if (!g_shared_device) return kmb_gemm_pair_launch(p, stream);
-    variant = 12;
-  }
-#ifdef KMB_WITH_ROLESPLIT   // experiment build only (tools/experiments/gemm_rolesplit.hip, build.py --variant rolesplit): not in the product library
-  if (variant == 10) return kmb_gemm_rs_launch(p, stream);
-#endif
-  if (variant == 11) {
-    dim3 grid(v11_grid(p, BN4)), block(256);
-    uint32_t* sched = p.K / BK >= 4 ? v11_sched_slot(stream) : nullptr;
-    if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, true, 256>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, false, 256>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else hipLaunchKernelGGL((gemm_kernel_v11<false, false, 256>), grid, block, LDS11, stream, p, sched, g_shared_device);
-  } else if (variant == 12) {
-    dim3 grid(v11_grid(p, 128)), block(256);
-    uint32_t* sched = p.K / BK >= 4 ? v11_sched_slot(stream) : nullptr;
-    if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, true, 128>), grid, block, LDS12, stream, p, sched, g_shared_device);
-    else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, false, 128>), grid, block, LDS12, stream, p, sched, g_shared_device);
-    else hipLaunchKernelGGL((gemm_kernel_v11<false, false, 128>), grid, block, LDS12, stream, p, sched, g_shared_device);
-  } else if (variant == 13) {
-    dim3 grid(v11_grid(p, 192)), block(256);
-    uint32_t* sched = p.K / BK >= 4 ? v11_sched_slot(stream) : nullptr;
-    if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, true, 192>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, false, 192>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else hipLaunchKernelGGL((gemm_kernel_v11<false, false, 192>), grid, block, LDS11, stream, p, sched, g_shared_device);
-  } else if (variant == 14) {
-    dim3 grid(v11_grid(p, BN4)), block(512);
-    uint32_t* sched = p.K / BK >= 4 ? v11_sched_slot(stream) : nullptr;
-    if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, true, 256, 8>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, false, 256, 8>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else hipLaunchKernelGGL((gemm_kernel_v11<false, false, 256, 8>), grid, block, LDS11, stream, p, sched, g_shared_device);
-  } else if (variant == 15) {
-    dim3 grid(v11_grid(p, 192)), block(512);
-    uint32_t* sched = p.K / BK >= 4 ? v11_sched_slot(stream) : nullptr;
-    if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, true, 192, 8>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v11<true, false, 192, 8>), grid, block, LDS11, stream, p, sched, g_shared_device);
-    else hipLaunchKernelGGL((gemm_kernel_v11<false, false, 192, 8>), grid, block, LDS11, stream, p, sched, g_shared_device);
-  } else if (variant == 8) {
-    const int tiles = ((p.M + BM4 - 1) / BM4) * ((p.N + BN4 - 1) / BN4);
-    dim3 grid(tiles * nsl), block(512);
-    if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v8<true, true>), grid, block, LDS4, stream, p);
-    else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v8<true, false>), grid, block, LDS4, stream, p);
-    else hipLaunchKernelGGL((gemm_kernel_v8<false, false>), grid, block, LDS4, stream, p);
-  } else {
-    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    dim3 grid(tiles * nsl), block(256);
-    if (variant == 5) {   // four LDS stages, one workgroup per CU (v7d_ok)
-      if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v7d<true, true>), grid, block, LDS_DEEP, stream, p);
-      else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v7d<true, false>), grid, block, LDS_DEEP, stream, p);
-      else hipLaunchKernelGGL((gemm_kernel_v7d<false, false>), grid, block, LDS_DEEP, stream, p);
-    } else if (variant == 7) {
-      if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel_v7<true, true>), grid, block, LDS_BYTES, stream, p);
-      else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel_v7<true, false>), grid, block, LDS_BYTES, stream, p);
-      else hipLaunchKernelGGL((gemm_kernel_v7<false, false>), grid, block, LDS_BYTES, stream, p);
-    } else {
-      if (p.a_kc && p.b_kc) hipLaunchKernelGGL((gemm_kernel<true, true>), grid, block, LDS_BYTES, stream, p);
-      else if (p.a_kc) hipLaunchKernelGGL((gemm_kernel<true, false>), grid, block, LDS_BYTES, stream, p);
-      else hipLaunchKernelGGL((gemm_kernel<false, false>), grid, block, LDS_BYTES, stream, p);
-    }
-  }
-  return hipGetLastError();
-}
-
 struct TuneKey {
   int akc, bkc, M, N, K, split, act;
   bool operator<(const TuneKey& o) const {
@@ -2797,94 +2328,63 @@ bool writes_an_input(const KmbGemm& p) {
   return p.beta != 0.f;
 }
 
-}  // namespace
+template <int BNT>
+bool v11_ok_bn(const KmbGemm& p) { return v11_ok(p, BNT); }
 
-namespace {
+// v8 (256x256 tiles): more than one 128x128 tile each way.  Smaller problems never reach the tuner either: they run variant 7.
+bool v8_ok(const KmbGemm& p) { return p.M > 128 && p.N > 128; }
 
-// A launch configuration: bits 0-3 kernel variant, bits 4-6 tile order, bit 8 / 9: L2 prefetch explicitly off / on (neither:
-// prefetch_a()'s rule).  Applies the launch rules that do not depend on timing and launches.
-hipError_t launch_config(const KmbGemm& p, int cfg, hipStream_t stream) {
-  KmbGemm q = p;
-  const int variant = cfg & 15;
-  bool pf = prefetch_a(p);
-  if (cfg & 0x100) pf = false;
-  if (cfg & 0x200) pf = p.a_kc != 0;
-  q.tile_order = ((cfg >> 4) & 7) | (pf ? 2 : 0);
-  if ((variant == 6 || variant == 9 || variant == 10) && p.a_kc && p.b_kc && p.N >= 32 * 256) q.tile_order |= 8;   // role-split: per-XCD ranges always; column blocks for wide outputs
-  if (variant >= 11) {
-    // Persistent variants: per-XCD contiguous tile ranges ALWAYS (bit 0), column blocks for wide outputs (bit 3).  The
-    // tuner's back-to-back timing cannot see the difference (operands sit in the Infinity Cache there); inside a step
-    // the round-robin order pulls every activation row panel into all eight L2s -- rocprofv3 FETCH_SIZE per launch,
-    // tools/r3_traffic.sh: fc1 forward 822 MB for 105 MB of operands, the N = 768 data gradients 1458 for 407 -- and
-    // measures 0.5-2 % slower (tools/gemm_ab_env.sh).  KMB_GEMM_FORCE_ORDER = 0 | 1 overrides bit 0, KMB_GEMM_COLBLOCKS=0
-    // switches the column blocks off (A/B measurements).
-    static int fo = -2, cbk = -1;
-    if (fo == -2) { const char* e = KMB_DIAG_ENV("KMB_GEMM_FORCE_ORDER"); fo = e ? atoi(e) : -1; }
-    if (cbk < 0) { const char* e = KMB_DIAG_ENV("KMB_GEMM_COLBLOCKS"); cbk = e ? atoi(e) : 1; }
-    q.tile_order = (q.tile_order & ~1) | (fo >= 0 ? (fo & 1) : 1);
-    if (cbk && p.a_kc && p.b_kc && p.N >= 32 * 256) q.tile_order |= 8;
-  }
-  {
-    // diagnostic (tools/gemm_epilogue_bound.py): KMB_GEMM_ABLATE_DYNAMIC=1 at process start makes the launcher re-read
-    // KMB_GEMM_ABLATE at every launch; "1" skips every epilogue (outputs are NOT written: timing only)
-    static const bool dyn_ablate = KMB_DIAG_ENV("KMB_GEMM_ABLATE_DYNAMIC") != nullptr;
-    if (dyn_ablate) {
-      const char* ab = KMB_DIAG_ENV("KMB_GEMM_ABLATE");
-      if (ab && ab[0] == '1') q.tile_order |= 512;
-    }
-  }
-  if (p.split_k > 1) {
-    // Split-K launches: per-XCD contiguous ranges + slice-major enumeration ALWAYS (bits 0 and 2), like the persistent rule
-    // above and for the same reason -- the tuner's back-to-back timing cannot tell the orders apart, the L2s can: with
-    // the round-robin order the 12 column tiles that share a 768-row operand slice sit on eight XCDs (fc2's weight
-    // gradient 768 x 3072 x 65536: 1544 MB fetched for 503 MB of operands, its transpose 3072 x 768 with the other order
-    // 628; profiles/r03_gemm_traffic_by_shape_b1024.txt).  In-step: b = 1024 neutral, b = 256 -0.4...-1.3 %
-    // (profiles/r03_ab_split_order_instep.txt).  KMB_GEMM_SPLIT_ORDER = 0 | 2: force slice-minor / leave the tuner's pick.
-    static int so = -2;
-    if (so == -2) { const char* e = KMB_DIAG_ENV("KMB_GEMM_SPLIT_ORDER"); so = e ? atoi(e) : 1; }
-    if (so == 0) q.tile_order &= ~4;
-    else if (so == 1) q.tile_order |= 5;
-  }
-  if (const char* e = KMB_DIAG_ENV("KMB_GEMM_STAGGER"))   // diagnostic build: start delay of a persistent workgroup, bits 16-23 (see gemm_kernel_v11)
-    q.tile_order |= (atoi(e) & 255) << 16;
-  if (p.act == 5) q.tile_order &= ~256;   // (diagnostic build) the store ablation has no exp / row-sum form: act 5 always takes its lean epilogue
-  return launch_variant(variant, q, stream);
+bool never_ok(const KmbGemm&) { return false; }
+
+// eight-wave persistent kernel around the bare K loop (gemm_lean.hip); tiles from a counter while the device is shared
+hipError_t lean_launch(const KmbGemm& p, hipStream_t stream) {
+  return kmb_gemm_lean_launch(p, stream, g_shared_device ? v11_sched_slot(stream) : nullptr, g_shared_device);
 }
 
-// In-step refinement of the tuner's choice.  The first launch of a shape ranks the variants by back-to-back launches on
-// operands that sit in the Infinity Cache; inside a training step (operands just streamed out by the previous kernel,
-// another stream's GEMM sharing the chip) the ranking is a different one: round 3 measured per-shape differences of up to
-// +-12 % between the back-to-back winner and the runner-up inside a step (profiles/r03_ab_eightwave_variants_instep_b1024.txt),
-// and +-10 % from the L2 prefetch depending on the shape.  Every variant returns the same bits, so exploring while the
-// job runs is safe: the next launches of the shape cycle through the back-to-back front-runners (within 8 % of the best,
-// at most three) x {L2 prefetch on, off}, each launch timed where it runs (two events on its own stream, read back
-// lazily when a later launch of the shape finds them complete), and the configuration with the lowest mean of its two
-// fastest of three samples is kept.  Entries preloaded from KMB_GEMM_TUNE_FILE are final.
-// MEASURED, and therefore OFF unless KMB_GEMM_REFINE=1: the GEMM launches of a step timed one at a time get 2 % faster with
-// the refined choices (41.0 / 41.7 / 41.1 ms against 42.2 / 42.0 / 42.2, same box), the step itself -- weight gradients
-// overlapping on the second stream -- does not (53.41 / 53.57 / 53.39 ms against 53.37 / 53.62 / 53.32 after 30 warm-up
-// steps), and while it explores it costs 1 % (52.6-52.8 against 52.1-52.2 with bench.py's 6 warm-up steps): a launch's
-// time inside an overlapped step depends more on which kernel of the other stream it shares the chip with than on the
-// variant, so three samples rank noise.
-struct Refine {
-  std::vector<int> cfg;
-  std::vector<std::vector<float>> ms;
-  struct Pend { hipEvent_t e0, e1; int idx; };
-  std::vector<Pend> pend;
-  std::vector<int> issued;
-  bool done = true;
-  int final_cfg = 7;
+// The launch variants, one row each.  Launching, the LDS attributes, the forced-variant fallback and the tuner's filter all
+// read this table and nothing else.
+//   0: the narrow kernel (128x32 tiles; routed to by narrow_ok, never forced or tuned)   1: register-staged 128x128 (any K)
+//   5: LDS-DMA + pipelined 128x128 with four LDS stages, one workgroup per CU             7: LDS-DMA + pipelined 128x128
+//   6: eight waves around the bare K loop, persistent 256x256 (gemm_lean.hip)             8: LDS-DMA + pipelined 256x256
+//   9: two persistent 256x128 workgroups per CU (gemm_pair.hip)
+//  10: role-split persistent 256x128 (tools/experiments/gemm_rolesplit.hip; experiment builds only: bit-identical, slower than
+//      the persistent variants on every benchmark-batch shape but two -- DESIGN.md section 4 "Round 4")
+//  11 / 12 / 13: persistent 256x256 / 256x128 / 256x192 (four waves); 14 / 15: persistent 256x256 / 256x192, eight waves
+struct Variant {
+  int variant;
+  const void* kernel[3];   // <true, true>, <true, false>, <false, false> of (A_KC, B_KC) ...
+  hipError_t (*launcher)(const KmbGemm&, hipStream_t);   // ... or the launcher of a variant that lives in another file
+  int bm, bn, threads, lds;   // tile rows and columns, workgroup size, dynamic LDS bytes (kernels of this file)
+  bool persistent;            // takes (sched, g_shared_device); grid from v11_grid
+  bool act5;                  // carries the act 5 epilogue (exp with row sums)
+  bool (*ok)(const KmbGemm&); // eligibility (nullptr: every problem)
+  int fallback;               // what a forced launch runs instead when ok() says no
 };
-std::map<TuneKey, Refine> g_refine;
-std::vector<hipEvent_t> g_refine_events;
-constexpr int REFINE_SAMPLES = 3;
-
-hipEvent_t refine_event() {
-  if (!g_refine_events.empty()) { hipEvent_t e = g_refine_events.back(); g_refine_events.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
-  return e;
-}
+#define KMB_LAYOUTS(...) {(const void*)__VA_ARGS__<true, true>, (const void*)__VA_ARGS__<true, false>, (const void*)__VA_ARGS__<false, false>}
+#define KMB_LAYOUTS_V11(...) {(const void*)gemm_kernel_v11<true, true, __VA_ARGS__>, (const void*)gemm_kernel_v11<true, false, __VA_ARGS__>, (const void*)gemm_kernel_v11<false, false, __VA_ARGS__>}
+// (Row order = the order the kernels are instantiated in, and with it their order in the code object: kept as it has always
+// been -- the persistent kernels first, the narrow kernel's row behind the all-rows and grouped launchers below.  Lookups go
+// through g_variant[], indexed by the variant number.)
+const Variant g_rows[] = {
+    {11, KMB_LAYOUTS_V11(256), nullptr, BM4, 256, 256, LDS11, true, true, v11_ok_bn<256>, 8},
+    {12, KMB_LAYOUTS_V11(128), nullptr, BM4, 128, 256, LDS12, true, true, v11_ok_bn<128>, 8},
+    {13, KMB_LAYOUTS_V11(192), nullptr, BM4, 192, 256, LDS11, true, false, v11_ok_bn<192>, 8},
+    {14, KMB_LAYOUTS_V11(256, 8), nullptr, BM4, 256, 512, LDS11, true, true, v11_ok_bn<256>, 8},
+    {15, KMB_LAYOUTS_V11(192, 8), nullptr, BM4, 192, 512, LDS11, true, false, v11_ok_bn<192>, 8},
+    {8, KMB_LAYOUTS(gemm_kernel_v8), nullptr, BM4, BN4, 512, LDS4, false, false, v8_ok, 7},
+    {5, KMB_LAYOUTS(gemm_kernel_v7d), nullptr, BM, BN, 256, LDS_DEEP, false, false, v7d_ok, 7},
+    {7, KMB_LAYOUTS(gemm_kernel_v7), nullptr, BM, BN, 256, LDS_BYTES, false, false, nullptr, 7},
+    {1, KMB_LAYOUTS(gemm_kernel), nullptr, BM, BN, 256, LDS_BYTES, false, false, nullptr, 7},
+    {6, {}, lean_launch, 256, 256, 512, 0, true, true, kmb_gemm_lean_ok, 11},
+    {9, {}, kmb_gemm_pair_launch, 256, 128, 256, 0, true, true, kmb_gemm_pair_ok, 11},
+#ifdef KMB_WITH_ROLESPLIT   // experiment build only (build.py --variant rolesplit): not in the product library
+    {10, {}, kmb_gemm_rs_launch, 256, 128, 512, 0, true, true, kmb_gemm_rs_ok, 11},
+#else
+    {10, {}, nullptr, 256, 128, 512, 0, true, true, never_ok, 11},
+#endif
+};
+#undef KMB_LAYOUTS
+#undef KMB_LAYOUTS_V11
 
 }  // namespace
 
@@ -2963,138 +2463,247 @@ hipError_t kmb_gemm_group_launch(const KmbGemm* probs, int n, hipStream_t stream
   return hipGetLastError();
 }
 
-// Every variant computes bit-identical results (same per-element accumulation order), so the choice is pure
-// speed: the first launch of a new shape times the eligible variants on the real operands (measure, don't guess).
-hipError_t kmb_gemm_launch(const KmbGemm& p, hipStream_t stream) {
-  static int forced = -1, autotune = 1, verbose = 0;
-  static const char* tune_file = nullptr;   // KMB_GEMM_TUNE_FILE: choices are appended here and preloaded from here, so a
-                                            // profiled run (rocprofv3 --pmc) contains no tuning launches
-  if (forced < 0) {
-    tune_file = getenv("KMB_GEMM_TUNE_FILE");
-    if (tune_file) {
-      if (FILE* f = fopen(tune_file, "r")) {
+namespace {
+
+// generation path: few rows, forward layout, plain epilogue -> narrow tiles (more, shorter workgroups)
+bool narrow_ok(const KmbGemm& p) {
+  static int on = -1;
+  if (on < 0) {
+    const char* e = KMB_DIAG_ENV("KMB_GEMM_NARROW");
+    on = !(e && e[0] == '0');
+  }
+  const int tiles128 = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+  return on && p.a_kc && p.b_kc && p.M <= 512 && tiles128 < 128 && (p.split_k <= 1 || (p.N & 7) == 0) && p.act <= 1 &&
+         p.preact == nullptr && p.colsum == nullptr && p.drop_thr16 == 0u && (p.act == 0 || p.aux == nullptr);
+}
+
+const Variant g_narrow_row = {0, {(const void*)gemm_kernel_narrow, nullptr, nullptr}, nullptr, BM, BNS, 256, LDS_S, false, false, narrow_ok, 7};
+
+const Variant* g_variant[16];   // by variant number; nullptr: a number that was never assigned or whose kernel is gone
+const bool g_variants_indexed = [] {
+  for (const Variant& row : g_rows) g_variant[row.variant] = &row;
+  g_variant[0] = &g_narrow_row;
+  return true;
+}();
+
+const Variant* variant_row(int v) { return v >= 0 && v < 16 ? g_variant[v] : nullptr; }   // (a direct index: nothing to search)
+
+// May variant v run problem p?  The one rule behind the forced-variant fallback and the tuner's candidate filter.
+bool eligible(int v, const KmbGemm& p) {
+  const Variant* row = variant_row(v);
+  return row && (!row->ok || row->ok(p)) && (p.act != 5 || row->act5);
+}
+
+// What KMB_GEMM_VARIANT=v runs on problem p: v itself, or down its fallbacks (5 -> 7; 6, 9, 10 -> 11; 11..15 -> 8; 8 -> 7;
+// a number without a kernel -> 7); act 5 runs on 11 unless the variant reached carries that epilogue.
+int forced_variant(int v, const KmbGemm& p) {
+  if (!variant_row(v)) v = 7;
+  while (g_variant[v]->ok && !g_variant[v]->ok(p)) v = g_variant[v]->fallback;
+  return eligible(v, p) ? v : 11;
+}
+
+// The kernel behind a variant number.  Variant 9's tiles are dealt statically: while another kernel (RCCL,
+// kmb_gemm_shared_device) holds CUs, the persistent 256 x 128 kernel with dynamic hand-out takes the launch instead (same
+// tile shape: every launch variant 9 admits, it admits)
+int kernel_variant(int v) { return v == 9 && g_shared_device ? 12 : v; }
+
+hipError_t launch_variant(int variant, const KmbGemm& p, hipStream_t stream) {
+  const Variant* row = variant_row(kernel_variant(variant));
+  if (!row) return hipErrorInvalidValue;
+  if (row->launcher) return row->launcher(p, stream);
+  const void* kernel = row->kernel[p.a_kc && p.b_kc ? 0 : p.a_kc ? 1 : 2];
+  if (!kernel) return hipErrorInvalidValue;
+  uint32_t* sched = nullptr;
+  int dyn_first = g_shared_device;
+  void* args[3] = {const_cast<KmbGemm*>(&p), &sched, &dyn_first};   // (a kernel that is not persistent takes the first only)
+  unsigned grid;
+  if (row->persistent) {
+    grid = v11_grid(p, row->bn);
+    if (p.K / BK >= 4) sched = v11_sched_slot(stream);
+  } else {
+    grid = (unsigned)(((p.M + row->bm - 1) / row->bm) * ((p.N + row->bn - 1) / row->bn) * (p.split_k > 1 ? p.split_k : 1));
+  }
+  (void)hipLaunchKernel(kernel, dim3(grid), dim3(row->threads), args, row->lds, stream);
+  return hipGetLastError();
+}
+
+// every kernel of the table may use the LDS it asks for; the first failure is the launch's error
+hipError_t set_lds_attributes() {
+  for (const Variant* row : g_variant)
+    for (int i = 0; row && i < 3; ++i)
+      if (row->kernel[i])
+        if (hipError_t e = hipFuncSetAttribute(row->kernel[i], hipFuncAttributeMaxDynamicSharedMemorySize, row->lds); e != hipSuccess) return e;
+  return hipSuccess;
+}
+
+// The tile_order a configuration (bits 0-3 kernel variant, bits 4-6 tile order) is launched with: the launch rules that do
+// not depend on timing.
+int config_tile_order(const KmbGemm& p, int cfg) {
+  const int variant = cfg & 15;
+  int order = ((cfg >> 4) & 7) | (prefetch_a(p) ? 2 : 0);
+  if ((variant == 6 || variant == 9 || variant == 10) && p.a_kc && p.b_kc && p.N >= 32 * 256) order |= 8;   // role-split: per-XCD ranges always; column blocks for wide outputs
+  if (variant >= 11) {
+    // Persistent variants: per-XCD contiguous tile ranges ALWAYS (bit 0), column blocks for wide outputs (bit 3).  The
+    // tuner's back-to-back timing cannot see the difference (operands sit in the Infinity Cache there); inside a step
+    // the round-robin order pulls every activation row panel into all eight L2s -- rocprofv3 FETCH_SIZE per launch,
+    // tools/r3_traffic.sh: fc1 forward 822 MB for 105 MB of operands, the N = 768 data gradients 1458 for 407 -- and
+    // measures 0.5-2 % slower (tools/gemm_ab_env.sh).  KMB_GEMM_FORCE_ORDER = 0 | 1 overrides bit 0, KMB_GEMM_COLBLOCKS=0
+    // switches the column blocks off (A/B measurements).
+    static int fo = -2, cbk = -1;
+    if (fo == -2) { const char* e = KMB_DIAG_ENV("KMB_GEMM_FORCE_ORDER"); fo = e ? atoi(e) : -1; }
+    if (cbk < 0) { const char* e = KMB_DIAG_ENV("KMB_GEMM_COLBLOCKS"); cbk = e ? atoi(e) : 1; }
+    order = (order & ~1) | (fo >= 0 ? (fo & 1) : 1);
+    if (cbk && p.a_kc && p.b_kc && p.N >= 32 * 256) order |= 8;
+  }
+  {
+    // diagnostic (tools/gemm_epilogue_bound.py): KMB_GEMM_ABLATE_DYNAMIC=1 at process start makes the launcher re-read
+    // KMB_GEMM_ABLATE at every launch; "1" skips every epilogue (outputs are NOT written: timing only)
+    static const bool dyn_ablate = KMB_DIAG_ENV("KMB_GEMM_ABLATE_DYNAMIC") != nullptr;
+    if (dyn_ablate) {
+      const char* ab = KMB_DIAG_ENV("KMB_GEMM_ABLATE");
+      if (ab && ab[0] == '1') order |= 512;
+    }
+  }
+  if (p.split_k > 1) {
+    // Split-K launches: per-XCD contiguous ranges + slice-major enumeration ALWAYS (bits 0 and 2), like the persistent rule
+    // above and for the same reason -- the tuner's back-to-back timing cannot tell the orders apart, the L2s can: with
+    // the round-robin order the 12 column tiles that share a 768-row operand slice sit on eight XCDs (fc2's weight
+    // gradient 768 x 3072 x 65536: 1544 MB fetched for 503 MB of operands, its transpose 3072 x 768 with the other order
+    // 628; profiles/r03_gemm_traffic_by_shape_b1024.txt).  In-step: b = 1024 neutral, b = 256 -0.4...-1.3 %
+    // (profiles/r03_ab_split_order_instep.txt).  KMB_GEMM_SPLIT_ORDER = 0 | 2: force slice-minor / leave the tuner's pick.
+    static int so = -2;
+    if (so == -2) { const char* e = KMB_DIAG_ENV("KMB_GEMM_SPLIT_ORDER"); so = e ? atoi(e) : 1; }
+    if (so == 0) order &= ~4;
+    else if (so == 1) order |= 5;
+  }
+  if (const char* e = KMB_DIAG_ENV("KMB_GEMM_STAGGER"))   // diagnostic build: start delay of a persistent workgroup, bits 16-23 (see gemm_kernel_v11)
+    order |= (atoi(e) & 255) << 16;
+  if (p.act == 5) order &= ~256;   // (diagnostic build) the store ablation has no exp / row-sum form: act 5 always takes its lean epilogue
+  return order;
+}
+
+// Every variant computes bit-identical results (same per-element accumulation order), so the choice is pure speed: the
+// first launch of a new shape times the eligible candidates on the real operands (measure, don't guess).  A candidate is
+// variant | (tile_order << 4).
+// (variant 10, the role-split kernel, lives in tools/experiments/ since round 5; `build.py --variant rolesplit` links it)
+constexpr int TUNE_CANDIDATES[21] = {5, 5 + 16, 5 + 16 * 5,                                          // four LDS stages (<= 256 workgroups)
+                                     7, 7 + 16, 8, 8 + 16, 11, 11 + 16, 12, 12 + 16, 13, 13 + 16,
+                                     14, 14 + 16, 15, 15 + 16,
+                                     7 + 16 * 5, 8 + 16 * 5,                                        // split-K only: slice-major
+                                     9,                                                             // two workgroups per CU (gemm_pair.hip)
+                                     6};                                                            // eight waves around the bare K loop (gemm_lean.hip)
+
+bool is_candidate(int cfg) {
+  for (int c : TUNE_CANDIDATES)
+    if (c == cfg) return true;
+  return false;
+}
+
+// the candidates the tuner times for p, in TUNE_CANDIDATES' order
+std::vector<int> tune_candidates(const KmbGemm& p) {
+  static unsigned exclude = ~0u;   // KMB_GEMM_EXCLUDE=14,15: variants the tuner may not pick (same-box A/B measurements)
+  if (exclude == ~0u) {
+    exclude = 0u;
+    if (const char* ex = KMB_DIAG_ENV("KMB_GEMM_EXCLUDE"))
+      for (const char* q = ex; *q;) {
+        const int v = atoi(q);
+        if (v > 0 && v < 32) exclude |= 1u << v;
+        while (*q && *q != ',') ++q;
+        if (*q == ',') ++q;
+      }
+  }
+  std::vector<int> out;
+  for (int c : TUNE_CANDIDATES) {
+    if (exclude & (1u << (c & 15))) continue;
+    if (!eligible(c & 15, p)) continue;
+    if (((c >> 4) & 4) && p.split_k <= 1) continue;
+    out.push_back(c);
+  }
+  return out;
+}
+
+// KMB_GEMM_VARIANT / KMB_GEMM_AUTOTUNE / KMB_GEMM_TUNE_FILE, read once; the tune file's choices are preloaded into g_best
+struct TuneEnv {
+  int forced = 0, autotune = 1, verbose = 0;
+  const char* tune_file = nullptr;   // choices are appended here and preloaded from here, so a profiled run (rocprofv3 --pmc)
+                                     // contains no tuning launches
+};
+const TuneEnv& tune_env() {
+  static const TuneEnv env = [] {
+    TuneEnv e;
+    e.tune_file = getenv("KMB_GEMM_TUNE_FILE");
+    if (e.tune_file) {
+      if (FILE* f = fopen(e.tune_file, "r")) {
         TuneKey k;
         int best;
         while (fscanf(f, "%d %d %d %d %d %d %d %d", &k.akc, &k.bkc, &k.M, &k.N, &k.K, &k.split, &k.act, &best) == 8)
-          g_best[k] = best;
+          if (is_candidate(best)) g_best[k] = best;   // (anything else -- an older build's in-step refinement wrote prefetch bits 0x100 / 0x200 -- is ignored)
         fclose(f);
       }
     }
     const char* ev = getenv("KMB_GEMM_VARIANT");
-    forced = ev ? atoi(ev) : 0;
+    e.forced = ev ? atoi(ev) : 0;
     const char* ea = getenv("KMB_GEMM_AUTOTUNE");
-    if (ea && ea[0] == '0') autotune = 0;
-    verbose = KMB_DIAG_ENV("KMB_GEMM_VERBOSE") != nullptr;
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v7<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v7<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v7<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v7d<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DEEP);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v7d<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DEEP);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v7d<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DEEP);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v8<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v8<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v8<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, true, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<false, false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, true, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS12);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, false, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS12);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<false, false, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS12);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, true, 192>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, false, 192>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<false, false, 192>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, true, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, false, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<false, false, 256, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, true, 192, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<true, false, 192, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
-    (void)hipFuncSetAttribute((const void*)gemm_kernel_v11<false, false, 192, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS11);
+    if (ea && ea[0] == '0') e.autotune = 0;
+    e.verbose = KMB_DIAG_ENV("KMB_GEMM_VERBOSE") != nullptr;
+    return e;
+  }();
+  return env;
+}
+
+// What a launch of p does, as far as it is decided without timing anything: configuration cfg (variant | (tile_order << 4);
+// variant 0: the narrow kernel) runs with p.tile_order = tile_order -- or, tune, the tuner's candidates are timed first.
+struct Route {
+  bool tune;
+  int cfg, tile_order;
+};
+Route gemm_route(const KmbGemm& p, int forced) {
+  if ((p.K % BK) != 0) return {false, 1, p.tile_order};   // LDS-DMA variants have no K-edge zero fill
+  if (!forced && narrow_ok(p)) return {false, 0, p.tile_order};
+  // a forced variant bypasses launch_config's rules: tools/gemm_v11_check.py and tools/kloop_time.py choose the tile order themselves
+  if (forced) return {false, forced_variant(forced, p), p.tile_order | (prefetch_a(p) ? 2 : 0)};
+  if (!v8_ok(p)) return {false, 7, p.tile_order};
+  const TuneEnv& env = tune_env();
+  auto it = g_best.find(TuneKey{p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act});
+  if (it != g_best.end()) return {false, it->second, config_tile_order(p, it->second)};
+  if (!env.autotune || writes_an_input(p)) return p.act == 5 ? Route{false, 11, config_tile_order(p, 11)} : Route{false, 7, p.tile_order};
+  return {true, 0, 0};
+}
+
+}  // namespace
+
+// Diagnostic (kmb_debug_gemm_route): the route of p as int32 words, no GPU call, operands never dereferenced.
+// out[0] = 0: one triple follows -- what the launch runs; 1: one triple per candidate the tuner would time, in its order.
+// A triple is (configuration, kernel variant that runs it, tile_order it is launched with once chosen).  Returns the words
+// written, -1 if cap is too small.
+int kmb_gemm_route(const KmbGemm& p, int forced, int32_t* out, int cap) {
+  const Route r = gemm_route(p, forced);
+  std::vector<int> cfgs = r.tune ? tune_candidates(p) : std::vector<int>{r.cfg};
+  if (cap < 1 + 3 * (int)cfgs.size()) return -1;
+  int n = 0;
+  out[n++] = r.tune;
+  for (int c : cfgs) {
+    out[n++] = c;
+    out[n++] = kernel_variant(c & 15);
+    out[n++] = r.tune ? config_tile_order(p, c) : r.tile_order;
   }
-  const bool dma_ok = (p.K % BK) == 0;           // LDS-DMA variants have no K-edge zero fill
-  const bool big = dma_ok && p.M > 128;
-  if (!dma_ok) return launch_variant(1, p, stream);
-  // generation path: few rows, forward layout, plain epilogue -> narrow tiles (more, shorter workgroups)
-  {
-    static int narrow_ok = -1;
-    if (narrow_ok < 0) {
-      const char* e = KMB_DIAG_ENV("KMB_GEMM_NARROW");
-      narrow_ok = !(e && e[0] == '0');
-      (void)hipFuncSetAttribute((const void*)gemm_kernel_narrow, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_S);
-    }
-    const int tiles128 = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    if (narrow_ok && !forced && p.a_kc && p.b_kc && p.M <= 512 && tiles128 < 128 && (p.split_k <= 1 || (p.N & 7) == 0) &&
-        p.act <= 1 && p.preact == nullptr && p.colsum == nullptr && p.drop_thr16 == 0u && (p.act == 0 || p.aux == nullptr)) {
-      dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BNS - 1) / BNS) * (p.split_k > 1 ? p.split_k : 1)), block(256);
-      hipLaunchKernelGGL(gemm_kernel_narrow, grid, block, LDS_S, stream, p);
-      return hipGetLastError();
-    }
+  return n;
+}
+
+hipError_t kmb_gemm_launch(const KmbGemm& p, hipStream_t stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipError_t e = set_lds_attributes(); e != hipSuccess) return e;
+    attr_set = true;
   }
-  if (forced) {
-    int v = forced;
-    if (v == 5 && !v7d_ok(p)) v = 7;
-    if (v == 6 && !kmb_gemm_lean_ok(p)) v = 11;
-    if (v == 9 && !kmb_gemm_pair_ok(p)) v = 11;
-#ifdef KMB_WITH_ROLESPLIT
-    if (v == 10 && !kmb_gemm_rs_ok(p)) v = 11;
-#else
-    if (v == 10) v = 11;   // the role-split experiment is not part of this library
-#endif
-    if (v == 11 && !v11_ok(p)) v = 8;
-    if (v == 12 && !v11_ok(p, 128)) v = 8;
-    if (v == 13 && !v11_ok(p, 192)) v = 8;
-    if (v == 14 && !v11_ok(p)) v = 8;
-    if (v == 15 && !v11_ok(p, 192)) v = 8;
-    if (v == 8 && !(big && p.N > 128)) v = 7;
-    if (v != 1 && v != 5 && v != 6 && v != 7 && v != 8 && v != 9 && v != 10 && (v < 11 || v > 15)) v = 7;
-    if (p.act == 5 && v != 6 && v != 9 && v != 10 && (v < 11 || v == 13 || v == 15)) v = 11;
-    KmbGemm q = p;
-    q.tile_order = p.tile_order | (prefetch_a(p) ? 2 : 0);
-    return launch_variant(v, q, stream);
-  }
-  if (!big || p.N <= 128) return launch_variant(7, p, stream);
-  const TuneKey key{p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act};
-  auto it = g_best.find(key);
-  if (it == g_best.end()) {
-    if (!autotune || writes_an_input(p)) return p.act == 5 ? launch_config(p, 11, stream) : launch_variant(7, p, stream);
-    // (variant 10, the role-split kernel, lives in tools/experiments/ since round 5: bit-identical, slower than the persistent
-    //  variants on every benchmark-batch shape but two -- DESIGN.md section 4 "Round 4"; `build.py --variant rolesplit` links it)
-    const int cands[21] = {5, 5 + 16, 5 + 16 * 5,                                          // four LDS stages (<= 256 workgroups)
-                           7, 7 + 16, 8, 8 + 16, 11, 11 + 16, 12, 12 + 16, 13, 13 + 16,   // variant | (tile_order << 4)
-                           14, 14 + 16, 15, 15 + 16,
-                           7 + 16 * 5, 8 + 16 * 5,                                        // split-K only: slice-major
-                           9,                                                             // two workgroups per CU (gemm_pair.hip)
-                           6};                                                            // eight waves around the bare K loop (gemm_lean.hip)
+  const TuneEnv& env = tune_env();
+  Route r = gemm_route(p, env.forced);
+  if (r.tune) {
     float best_ms = 1e30f;
     int best = p.act == 5 ? 11 : 7;
-    std::vector<std::pair<float, int>> timed;   // (ms, candidate) of every eligible candidate
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return launch_variant(7, p, stream);
-    static unsigned exclude = ~0u;   // KMB_GEMM_EXCLUDE=14,15: variants the tuner may not pick (same-box A/B measurements)
-    if (exclude == ~0u) {
-      exclude = 0u;
-      if (const char* ex = KMB_DIAG_ENV("KMB_GEMM_EXCLUDE"))
-        for (const char* q = ex; *q;) {
-          const int v = atoi(q);
-          if (v > 0 && v < 32) exclude |= 1u << v;
-          while (*q && *q != ',') ++q;
-          if (*q == ',') ++q;
-        }
-    }
-    for (int c : cands) {
-      if (exclude & (1u << (c & 15))) continue;
-      if ((c & 15) == 5 && !v7d_ok(p)) continue;
-      if ((c & 15) == 6 && !kmb_gemm_lean_ok(p)) continue;
-      if ((c & 15) == 9 && !kmb_gemm_pair_ok(p)) continue;
-      if ((c & 15) == 11 && !v11_ok(p)) continue;
-      if ((c & 15) == 12 && !v11_ok(p, 128)) continue;
-      if ((c & 15) == 13 && !v11_ok(p, 192)) continue;
-      if ((c & 15) == 14 && !v11_ok(p)) continue;
-      if ((c & 15) == 15 && !v11_ok(p, 192)) continue;
-      if (p.act == 5 && (c & 15) != 6 && (c & 15) != 9 && (c & 15) != 10 && ((c & 15) < 11 || (c & 15) == 13 || (c & 15) == 15)) continue;   // lean epilogue of the 256- / 128-column persistent variants (and the role-split one) only
-      if (((c >> 4) & 4) && p.split_k <= 1) continue;
+    for (int c : tune_candidates(p)) {
       KmbGemm q = p;
       q.tile_order = c >> 4;
       hipError_t e = launch_variant(c & 15, q, stream);  // warm
@@ -3109,111 +2718,23 @@ hipError_t kmb_gemm_launch(const KmbGemm& p, hipStream_t stream) {
         (void)hipEventElapsedTime(&t, e0, e1);
         ms = t < ms ? t : ms;
       }
-      if (verbose) fprintf(stderr, "[kmb gemm tune] akc=%d bkc=%d M=%d N=%d K=%d split=%d act=%d v%d order%d %.1f us\n",
-                           p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act, c & 15, c >> 4, ms / 3 * 1e3);
-      // diagnostic build: KMB_GEMM_BIAS6=<percent> ranks variant 6 as if it were that much faster than timed back-to-back (its
-      // cross-tile L2 touch costs it ~4 us per tile in this loop and pays inside a step: DESIGN.md section 4 "Round 4")
-      static const float bias6 = KMB_DIAG_ENV("KMB_GEMM_BIAS6") ? 1.f - 0.01f * (float)atof(KMB_DIAG_ENV("KMB_GEMM_BIAS6")) : 1.f;
-      const float rank_ms = (c & 15) == 6 ? ms * bias6 : ms;
-      if (rank_ms < best_ms) { best_ms = rank_ms; best = c; }
-      timed.emplace_back(ms, c);
+      if (env.verbose) fprintf(stderr, "[kmb gemm tune] akc=%d bkc=%d M=%d N=%d K=%d split=%d act=%d v%d order%d %.1f us\n",
+                               p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act, c & 15, c >> 4, ms / 3 * 1e3);
+      if (ms < best_ms) { best_ms = ms; best = c; }   // (strict: ties stay with the earlier candidate)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    it = g_best.emplace(key, best).first;
-    static const bool refine_on = KMB_DIAG_ENV("KMB_GEMM_REFINE") && KMB_DIAG_ENV("KMB_GEMM_REFINE")[0] == '1';   // opt-in: see Refine
-    Refine& R = g_refine[key];
-    R.final_cfg = best;
-    R.done = true;
-    if (refine_on) {
-      std::sort(timed.begin(), timed.end());
-      std::vector<int> front;   // front-runners: distinct variants (one tile order each: the faster one) within 8 % of the best
-      for (const auto& tc : timed) {
-        if (tc.first > best_ms * 1.08f || front.size() >= 3) break;
-        bool dup = false;
-        for (int f : front) dup = dup || (f & 15) == (tc.second & 15);
-        if (!dup) front.push_back(tc.second);
-      }
-      for (int f : front) {
-        if ((f & 15) >= 11 && p.a_kc) { R.cfg.push_back(f | 0x200); R.cfg.push_back(f | 0x100); }
-        else R.cfg.push_back(f);
-      }
-      if (R.cfg.size() > 1) {
-        R.done = false;
-        R.ms.assign(R.cfg.size(), {});
-        R.issued.assign(R.cfg.size(), 0);
-      }
-    }
-    if (tune_file && R.done) {
-      if (FILE* f = fopen(tune_file, "a")) {
+    const TuneKey key{p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act};
+    g_best.emplace(key, best);
+    if (env.tune_file) {
+      if (FILE* f = fopen(env.tune_file, "a")) {
         fprintf(f, "%d %d %d %d %d %d %d %d\n", key.akc, key.bkc, key.M, key.N, key.K, key.split, key.act, best);
         fclose(f);
       }
     }
+    r = {false, best, config_tile_order(p, best)};
   }
-  {
-    auto rit = g_refine.find(key);
-    if (rit != g_refine.end() && !rit->second.done) {
-      Refine& R = rit->second;
-      // harvest the launches of this shape that have completed since
-      for (size_t i = 0; i < R.pend.size();) {
-        if (hipEventQuery(R.pend[i].e1) == hipSuccess) {
-          float t = 0.f;
-          if (hipEventElapsedTime(&t, R.pend[i].e0, R.pend[i].e1) == hipSuccess) R.ms[R.pend[i].idx].push_back(t);
-          g_refine_events.push_back(R.pend[i].e0);
-          g_refine_events.push_back(R.pend[i].e1);
-          R.pend[i] = R.pend.back();
-          R.pend.pop_back();
-        } else {
-          ++i;
-        }
-      }
-      (void)hipGetLastError();   // hipErrorNotReady of a query is not an error of this launch
-      int pick = -1;
-      bool all = true;
-      for (size_t i = 0; i < R.cfg.size(); ++i) {
-        if ((int)R.ms[i].size() < REFINE_SAMPLES) all = false;
-        if (R.issued[i] < REFINE_SAMPLES && (pick < 0 || R.issued[i] < R.issued[pick])) pick = (int)i;
-      }
-      if (all) {
-        float best_s = 1e30f;
-        for (size_t i = 0; i < R.cfg.size(); ++i) {
-          std::sort(R.ms[i].begin(), R.ms[i].end());
-          const float sc = R.ms[i][0] + R.ms[i][1];   // the two fastest of three: one sample beside a long kernel of another stream does not decide
-          if (sc < best_s) { best_s = sc; R.final_cfg = R.cfg[i]; }
-        }
-        if (verbose) {
-          fprintf(stderr, "[kmb gemm refine] akc=%d bkc=%d M=%d N=%d K=%d split=%d act=%d:", p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act);
-          for (size_t i = 0; i < R.cfg.size(); ++i)
-            fprintf(stderr, " v%d|o%d|%s %.1f", R.cfg[i] & 15, (R.cfg[i] >> 4) & 7, (R.cfg[i] & 0x200) ? "pf" : (R.cfg[i] & 0x100) ? "nopf" : "rule",
-                    (R.ms[i][0] + R.ms[i][1]) * 500.f);
-          fprintf(stderr, " -> v%d\n", R.final_cfg & 15);
-        }
-        R.done = true;
-        it->second = R.final_cfg;
-        for (auto& pe : R.pend) { g_refine_events.push_back(pe.e0); g_refine_events.push_back(pe.e1); }   // none left: all sampled
-        R.pend.clear();
-        if (tune_file) {
-          if (FILE* f = fopen(tune_file, "a")) {
-            fprintf(f, "%d %d %d %d %d %d %d %d\n", key.akc, key.bkc, key.M, key.N, key.K, key.split, key.act, R.final_cfg);
-            fclose(f);
-          }
-        }
-      } else if (pick >= 0) {
-        hipEvent_t a = refine_event(), b = refine_event();
-        if (a && b) {
-          (void)hipEventRecord(a, stream);
-          const hipError_t e = launch_config(p, R.cfg[pick], stream);
-          (void)hipEventRecord(b, stream);
-          R.pend.push_back({a, b, pick});
-          R.issued[pick] += 1;
-          return e;
-        }
-      } else {
-        // every configuration has its launches in flight: run the back-to-back choice until they complete
-      }
-    }
-  }
-  return launch_config(p, it->second, stream);
+  KmbGemm q = p;
+  q.tile_order = r.tile_order;
+  return launch_variant(r.cfg & 15, q, stream);
 }
-#endif  // KMB_GEMM_DEVICE_ONLY

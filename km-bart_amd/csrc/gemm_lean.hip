@@ -16,8 +16,7 @@
 //   * the L2 touch of the activation panel as one register-free load per wave behind a stage's pieces; no role split, no second accumulator set.
 // Same LDS images, swizzles, MFMA operand order and k order per accumulator as every other variant: bit-identical results
 // (tools/gemm_v11_check.py).
-#define KMB_GEMM_DEVICE_ONLY
-#include "gemm.hip"
+#include "gemm_device.h"
 
 namespace {
 
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // ---- LDS-DMA: kernel-constant lane offsets (interior tiles), scalar tile bases; the cursor runs two steps ahead ----
   constexpr int NPW = 4;
-  // The token-major B's transposing reads as inline asm (gemm.hip, kmb_tr_read_asm) wherever the library uses them (KMB_TR_ALL).
+  // The token-major B's transposing reads as inline asm (gemm_device.h, kmb_tr_read_asm) wherever the library uses them (KMB_TR_ALL).
   constexpr bool TRASM = KMB_TR_ALL && !B_KC;
   uint32_t offA[NPW], offB[NPW];
   dma_offsets256w4<true, 4>(offA, p.lda, 0, 1 << 30, wave, lane);
@@ -149,7 +148,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // share a row panel (the tiles of one tm: consecutive tiles, side by side on one XCD) each touch THEIR share of its rows
   // LN_PFD steps ahead of the DMA cursor, one load instruction per wave right behind a stage's pieces; the step's counted wait leaves
   // it outstanding, so it has two steps to land.  Its result is never used and it has NO register destination (round 6; KMB_L2_TOUCH,
-  // gemm.hip): a 4-byte LDS-DMA into 256 bytes of the issuing wave's own epilogue staging image, which nothing reads or writes during
+  // gemm_device.h): a 4-byte LDS-DMA into 256 bytes of the issuing wave's own epilogue staging image, which nothing reads or writes during
   // a K loop.  Rounds 4-5 sent it to v255 on the premise that the allocator never hands v255 out -- a property of one compilation,
   // guarded by an ISA test, and false as soon as the transposing reads became inline asm -- because the cross-tile touches (the last
   // steps of a tile touch the next tile's first steps) were in flight DURING the epilogue, which owns the staging images.  Now a

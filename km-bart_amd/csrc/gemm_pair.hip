@@ -24,8 +24,7 @@
 //
 // Limits (kmb_gemm_pair_ok): both operands K-contiguous, M % 256 == 0, N % 128 == 0, K % 192 == 0 (the K loop is unrolled
 // over the three buffers x the two fragment sets), no split-K, bf16 output, one of the lean epilogue classes.
-#define KMB_GEMM_DEVICE_ONLY
-#include "gemm.hip"
+#include "gemm_device.h"
 
 namespace {
 
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) __a
   // ahead of the DMA cursor -- one load instruction per wave behind every stage's pieces, a 128-byte line serves two steps, the
   // step's parity picks which half of the wave's rows it touches -- and the pieces of all sharers then hit L2.  The load's result
   // is never used; every wait leaves it outstanding (vmcnt 8 = the previous touch, a stage's six pieces, this touch) so that it
-  // has three steps to land; it has no register destination: it lands in a dummy LDS word behind the stages (KMB_L2_TOUCH, gemm.hip).
+  // has three steps to land; it has no register destination: it lands in a dummy LDS word behind the stages (KMB_L2_TOUCH, gemm_device.h).
   constexpr int PR_PFD = 4;
   const int sharers = col_blocks ? CB : tiles_n;
   int pf_share = (PR_BM + sharers - 1) / sharers;

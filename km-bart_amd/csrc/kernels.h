@@ -10,6 +10,8 @@ typedef uint16_t bf16_t;
 // ------------------------------------------------------------------ gemm.hip
 const char* kmb_gemm_check(const KmbGemm& p);
 hipError_t kmb_gemm_launch(const KmbGemm& p, hipStream_t stream);
+// what kmb_gemm_launch would do with p (forced > 0: under KMB_GEMM_VARIANT=forced), as int32 words; no GPU call (kmb_debug_gemm_route)
+int kmb_gemm_route(const KmbGemm& p, int forced, int32_t* out, int cap);
 // the "all rows" kernel for decode-sized forward GEMMs (<= 320 rows, fp32 output, bias only): bit-identical to kmb_gemm_launch
 constexpr int KMB_GEMM_GROUP_MAX = 8;
 const char* kmb_gemm_group_check(const KmbGemm* probs, int n);

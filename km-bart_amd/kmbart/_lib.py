@@ -154,6 +154,7 @@ PROTOTYPES = {
                                            C.c_int, c_p, c_p, c_p, c_p, C.c_int64, C.c_int, c_p]),
     "kmb_gen_workspace_bytes": (i64, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kmb_gemm_shared_device": (C.c_int, [C.c_int]),
+    "kmb_debug_gemm_route": (C.c_int, [C.POINTER(KmbGemm), C.c_int, c_p, C.c_int32]),
     "kmb_comm_unique_id": (C.c_int, [c_p]),
     "kmb_comm_init": (C.c_int, [c_p, C.c_int, C.c_int, c_p]),
     "kmb_comm_destroy": (C.c_int, [c_p]),

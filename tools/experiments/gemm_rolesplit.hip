@@ -28,8 +28,7 @@
 //
 // Limits (kmb_gemm_rs_ok): K-contiguous A, M % 256 == 0, N % 128 == 0, K % 64 == 0 with >= 8 K steps, no split-K, bf16
 // output, one of the lean epilogue classes below, >= 128 tiles.  Everything else stays on the other variants.
-#define KMB_GEMM_DEVICE_ONLY
-#include "gemm.hip"
+#include "gemm_device.h"
 
 namespace {
 

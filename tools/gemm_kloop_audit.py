@@ -89,7 +89,7 @@ def audit_file(path, src="gemm.hip", sig_for=()):
     rows = []
     for name, b in ks:
         if src != "gemm.hip" and ("lean" not in name and "pair" not in name):
-            continue   # gemm_lean.hip / gemm_pair.hip include gemm.hip's device code: only their own kernels
+            continue   # gemm_lean.hip / gemm_pair.hip: only their own kernels
         lp = k_loop(b)
         if lp is None:
             continue
