@@ -288,7 +288,8 @@ int kmb_gen_encoder_states(kmb_handle* h, kmb_bf16* enc_out, void* stream);
  * tokens = NULL: the step runs on the tokens the preceding kmb_gen_beam_step(reorder_step = step - 1) chose and already
  * embedded (no embedding launch); fails when no such embedding is pending for `step` (kmb_gen_embedded_step). */
 int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_out, void* stream);
-/* the step whose tokens the last kmb_gen_beam_step embedded for a kmb_gen_step(tokens = NULL), or -1: none pending (any
+/* the step whose tokens the last kmb_gen_beam_step (or kmb_gen_beam_sample_step, kmb_gen_greedy_step) embedded for a
+ * kmb_gen_step(tokens = NULL), or -1: none pending (any
  * kmb_gen_step or kmb_gen_beam_step since, or that beam step did not embed -- no reorder, no next step inside max_length, or the
  * decoder states kmb_gen_last_hidden returns still lived where the embedding goes).  Host state only: no stream work. */
 int kmb_gen_embedded_step(const kmb_handle* h);
@@ -362,6 +363,33 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
 int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
                     const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
                     int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, void* stream);
+/* One decode step's greedy tail of generate(num_beams=1, do_sample=False) (transformers 3.0.2 _generate_no_beam_search, the
+ * mode the reference runs by default: vcg_generate.py --num_beams 1, the training callback of vcg_train.py:183-194), ONE
+ * launch, one pass over the logits; stateless like kmb_sample_step, whose argument conventions it keeps.  Per row r < R of
+ * logits [R, ld] (fp32, V real columns; columns >= V are never read): x = logits[r, :V], NaN read as -inf, x[ban_token] = -inf
+ * (ban_token -1: none; the min_length EOS ban, applied to the logits before any normalisation as postprocess_next_token_scores
+ * does there); token = argmax x, the lowest index on exact ties; lp = x[token] - logsumexp(x); a row with no finite entry
+ * gives token 0 and lp = -inf.
+ * unfinished (int64 [R], or NULL): a finished row takes pad_token, then unfinished[r] &= token != eos_token (-1: none).
+ * The token goes to next_tokens[r] (int64, the next kmb_gen_step's input) and, when ids != NULL, to ids[r * ld_ids + t];
+ * flag (int32, or NULL) is OR-ed with 1 when a row is still unfinished.
+ * logprob_sum (fp32 [R], or NULL): logprob_sum[r] += lp for the rows that were unfinished on entry (every row without
+ * `unfinished`) -- the EOS token's own log-probability included, a finished row adds nothing: the sum_logprobs of the
+ * reference's sample_sentence (src/model/utils.py:34-56).  logprob_out (fp32 [R], or NULL) receives this step's lp, 0 for a
+ * finished row.  Any V >= 1, ld >= V, R >= 1 (rows that do not start on 16 bytes are read one column per load).
+ * Deterministic: a fixed reduction order, no floating-point atomics.  Bad arguments fail with a message and launch nothing. */
+int kmb_greedy_step(const float* logits, int ld, int V, int R, int ban_token, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                    int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* logprob_sum, float* logprob_out,
+                    void* stream);
+/* The decode loop's form of kmb_greedy_step on the logits the last kmb_gen_step wrote (V and R are the handle's; needs
+ * kmb_gen_begin with num_beams == 1): same outputs.  embed_step >= 0: the same launch also embeds the chosen tokens for decode
+ * step embed_step (token embedding + position extra_pos_embeddings + embed_step + layernorm_embedding, kmb_gen_step's own row
+ * code, bit-identical rows) into the generation workspace -- unless that step lies outside the cache or d_model is not a
+ * multiple of 8 or > 1024: kmb_gen_embedded_step() tells, and kmb_gen_step(h, NULL, embed_step, ...) uses the rows.
+ * kmb_gen_last_hidden keeps returning the step's decoder states.  embed_step -1: no embedding. */
+int kmb_gen_greedy_step(kmb_handle* h, const float* logits, int ld, int ban_token, int64_t* unfinished, int64_t pad_token,
+                        int64_t eos_token, int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* logprob_sum,
+                        float* logprob_out, int embed_step, void* stream);
 /* One decode step of beam sampling (generate(do_sample=True, num_beams > 1): transformers 3.0.2 _generate_beam_search, sampling
  * branch, reached from the reference's --num_beams with --do_sample, src/generation.py:22-32), two launches, stateless
  * like kmb_beam_step.  Per row r = b * num_beams + j of logits [B * num_beams, ld] (fp32, V real columns, NaN read as -inf):

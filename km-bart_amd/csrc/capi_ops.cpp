@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "sample.h"
 #include "beam_sample.h"
+#include "greedy.h"
 
 extern "C" const char* kmb_last_error(void);
 int kmb_set_error(const char* msg);  // engine.cpp
@@ -260,6 +261,17 @@ int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature
                  "sample_step");
 }
 
+int kmb_greedy_step(const float* logits, int ld, int V, int R, int ban_token, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                    int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* logprob_sum, float* logprob_out,
+                    void* stream) {
+  if (kmb_greedy_validate("kmb_greedy_step", logits, ld, V, R, ban_token, unfinished, pad_token, eos_token, next_tokens, ids, t,
+                          ld_ids) != 0)
+    return -1;
+  return hipfail(kmb_greedy_step_launch(logits, ld, V, R, ban_token, unfinished, pad_token, eos_token, next_tokens, ids, t, ld_ids, flag,
+                                        logprob_sum, logprob_out, (hipStream_t)stream),
+                 "greedy_step");
+}
+
 int64_t kmb_beam_sample_scratch(int rows) { return (int64_t)kmb_beam_sample_scratch_floats(rows); }
 int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beams, const float* add, float temperature, int top_k,
                          float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
@@ -298,5 +310,22 @@ int kmb_beam_sample_validate(const char* who, const float* logits, int ld, int V
   if (!(top_p > 0.f && top_p <= 1.f)) return bad("top_p must lie in (0, 1]");
   if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
   if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
+  return 0;
+}
+
+// The argument checks of kmb_greedy_step and kmb_gen_greedy_step (`who` names the caller in the message).
+int kmb_greedy_validate(const char* who, const float* logits, int ld, int V, int R, int ban_token, const int64_t* unfinished,
+                        int64_t pad_token, int64_t eos_token, const int64_t* next_tokens, const int64_t* ids, int t, int ld_ids) {
+  char buf[256];
+  auto bad = [&](const char* what) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return kmb_set_error(buf);
+  };
+  if (!logits || !next_tokens) return bad("logits and next_tokens are required");
+  if (V < 1 || R < 1 || ld < V) return bad("need V >= 1, R >= 1, ld >= V");
+  if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
+  if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
+  if (unfinished && (pad_token < 0 || pad_token >= V)) return bad("pad_token must be a token id < V");
+  if (ids && (t < 0 || t >= ld_ids)) return bad("need 0 <= t < ld_ids");
   return 0;
 }

@@ -18,6 +18,7 @@
 #include <rccl/rccl.h>
 #include "kernels.h"
 #include "beam_sample.h"
+#include "greedy.h"
 #include "diag.h"
 
 namespace {
@@ -2369,6 +2370,16 @@ static int gen_reordered(kmb_handle* h, const int32_t* beam_idx, hipStream_t s) 
   return 0;
 }
 
+// The embedding of decode step `step` as a step's tail folds it into its own launch: kmb_gen_step's embedding arguments, rows into x0.
+static KmbEmbedNext gen_embed_next(kmb_handle* h, int step) {
+  const int d = h->d;
+  KmbEmbedNext en;
+  en.E = h->pf(h->shared); en.prow = h->pf(h->dec_pos) + (size_t)(h->cfg.extra_pos_embeddings + step) * d;
+  en.gamma = h->pf(h->dec_lne_g); en.beta = h->pf(h->dec_lne_b); en.y = h->gen.x0;
+  en.scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f; en.D = d; en.eps = h->cfg.layer_norm_eps; en.V = h->V;
+  return en;
+}
+
 // What a beam step of the decode loop folds into its launch (kmb_gen_beam_step, kmb_gen_beam_sample_step): the history-index reorder
 // (fold) and the next step's embedding (embed).
 static void gen_fold_plan(kmb_handle* h, int reorder_step, bool& fold, KmbHistGather& hg, bool& embed, KmbEmbedNext& en) {
@@ -2381,12 +2392,7 @@ static void gen_fold_plan(kmb_handle* h, int reorder_step, bool& fold, KmbHistGa
   // ... not when x0 still holds the step's final decoder states (the launch-per-operation path swaps x0 / x1 once per layer, so an even
   // number of layers ends there): kmb_gen_last_hidden must keep returning them; the next kmb_gen_step embeds then
   embed = reorder_step >= 0 && reorder_step + 1 < G.Tmax && (d & 7) == 0 && d > 512 && d <= 1024 && G.last_x != G.x0;
-  en = KmbEmbedNext{};
-  if (embed) {
-    en.E = h->pf(h->shared); en.prow = h->pf(h->dec_pos) + (size_t)(h->cfg.extra_pos_embeddings + reorder_step + 1) * d;
-    en.gamma = h->pf(h->dec_lne_g); en.beta = h->pf(h->dec_lne_b); en.y = G.x0;
-    en.scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f; en.D = d; en.eps = h->cfg.layer_norm_eps; en.V = h->V;
-  }
+  en = embed ? gen_embed_next(h, reorder_step + 1) : KmbEmbedNext{};
 }
 
 // After the beam step's launch: the state of the reorder and of the embedding it folded in.
@@ -2452,6 +2458,34 @@ int kmb_gen_beam_sample_step(kmb_handle* h, const float* logits, int ld, int num
                                      out, eos_token, next_scores, next_tokens, next_beam_idx, scratch, (size_t)scratch_floats,
                                      (hipStream_t)stream, fold ? &hg : nullptr, embed ? &en : nullptr));
   return gen_fold_finish(h, fold, embed, reorder_step, next_beam_idx, stream);
+}
+
+// The greedy step of the decode loop (kmb_greedy_step on the logits of the last kmb_gen_step).  embed_step >= 0: another decode step
+// follows at that position on the tokens chosen here, and the same launch embeds them, as gen_fold_plan has the beam steps do -- the step
+// must lie inside the cache.  One wave embeds one row here, so any d_model <= 1024 that is a multiple of 8 folds (with
+// kmb_embed_ln_fwd_launch's chunk count for that width), and where x0 still holds the decoder states kmb_gen_last_hidden returns (the
+// launch-per-operation path with an even number of layers) the rows go to x1, which is free once the step's layers are queued, and the
+// two buffers change names: last_x keeps pointing at the states.
+int kmb_gen_greedy_step(kmb_handle* h, const float* logits, int ld, int ban_token, int64_t* unfinished, int64_t pad_token,
+                        int64_t eos_token, int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* logprob_sum,
+                        float* logprob_out, int embed_step, void* stream) {
+  auto& G = h->gen;
+  if (!G.active) return fail("kmb_gen_greedy_step: call kmb_gen_begin first");
+  if (G.nb != 1) return fail("kmb_gen_greedy_step: needs num_beams == 1, kmb_gen_begin had %d", G.nb);
+  if (embed_step < -1) return fail("kmb_gen_greedy_step: embed_step must be -1 or a decode step");
+  // the stateless form's argument checks, before anything is launched or the generation state changes
+  if (kmb_greedy_validate("kmb_gen_greedy_step", logits, ld, h->V, G.R, ban_token, unfinished, pad_token, eos_token, next_tokens, ids, t,
+                          ld_ids) != 0)
+    return -1;
+  const int d = h->d;
+  const bool embed = embed_step >= 0 && embed_step < G.Tmax && (d & 7) == 0 && d <= 1024;
+  if (embed && G.last_x == G.x0) std::swap(G.x0, G.x1);
+  const KmbEmbedNext en = embed ? gen_embed_next(h, embed_step) : KmbEmbedNext{};
+  G.x0_step = -1;
+  HIPCHK(kmb_greedy_step_launch(logits, ld, h->V, G.R, ban_token, unfinished, pad_token, eos_token, next_tokens, ids, t, ld_ids, flag,
+                                logprob_sum, logprob_out, (hipStream_t)stream, embed ? &en : nullptr));
+  if (embed) G.x0_step = embed_step;
+  return 0;
 }
 
 int kmb_gen_last_hidden(kmb_handle* h, kmb_bf16* out, void* stream) {

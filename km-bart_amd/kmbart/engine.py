@@ -724,6 +724,37 @@ class Engine:
                                            ids.stride(0) if ids is not None else 0, ptr(flag), ptr(info_out), _stream()))
         return next_tokens
 
+    def greedy_step(self, logits, ban_token=-1, unfinished=None, pad_token=0, eos_token=-1, next_tokens=None, ids=None, t=0,
+                    flag=None, logprob_sum=None, logprob_out=None, embed_step=-1):
+        """One decode step's greedy tail (kmb_greedy_step): EOS ban, argmax (lowest index on ties), the chosen token's
+        log-probability and the finished-row bookkeeping in one launch.  `logits` may be gen_step's padded view.  Returns
+        next_tokens (int64 [R]); unfinished (int64 [R]) and the id buffer ids (int64 [R, ld], column t) are updated in place;
+        flag (int32, one element) is OR-ed with 1 while a row is unfinished; logprob_sum (fp32 [R]) gains the log-probability
+        of the rows unfinished on entry, logprob_out (fp32 [R]) receives this step's (0 for a finished row).
+        embed_step >= 0, when `logits` are gen_step's, unedited since (their _version unchanged): the launch also embeds the
+        chosen tokens for that decode step (kmb_gen_greedy_step), and gen_step(next_tokens, embed_step) then runs without an
+        embedding launch, as after beam_step."""
+        R, V = logits.shape[0], int(self.config.vocab_size)
+        for x, dt in ((logits, torch.float32), (unfinished, torch.int64), (ids, torch.int64), (flag, torch.int32),
+                      (logprob_sum, torch.float32), (logprob_out, torch.float32)):
+            assert x is None or (x.device == self.device and x.dtype == dt and x.stride(-1) == 1), "greedy_step: bad tensor"
+        assert (unfinished is None or unfinished.numel() == R) and (ids is None or ids.shape[0] == R)
+        assert all(x is None or (x.is_contiguous() and x.numel() == R) for x in (logprob_sum, logprob_out))
+        if next_tokens is None:
+            next_tokens = torch.empty((R,), dtype=torch.int64, device=self.device)
+        assert next_tokens.is_contiguous() and next_tokens.numel() == R and next_tokens.dtype == torch.int64
+        self._folded = None
+        args = (int(ban_token), ptr(unfinished), int(pad_token), int(eos_token), ptr(next_tokens), ptr(ids), int(t),
+                ids.stride(0) if ids is not None else 0, ptr(flag), ptr(logprob_sum), ptr(logprob_out))
+        with torch.cuda.device(self.device):
+            if logits is self.__dict__.get("_gen_logits") and logits._version == self._gen_logits_version:
+                check(self.lib.kmb_gen_greedy_step(self.h, ptr(logits), logits.stride(0), *args, int(embed_step), _stream()))
+                if embed_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == embed_step:
+                    self._folded = (next_tokens, next_tokens._version, int(embed_step))
+            else:
+                check(self.lib.kmb_greedy_step(ptr(logits), logits.stride(0), V, R, *args, _stream()))
+        return next_tokens
+
     def _topk_scratch_for(self, R):
         nscr = int(self.lib.kmb_logsoftmax_topk_scratch(R))
         scr = self.__dict__.get("_topk_scratch")

@@ -204,6 +204,13 @@ def _decode_route(num_beams, do_sample, processors_on, fp32, device_sampling, ha
     return "host_beams"
 
 
+def _one_beam_on_device(do_sample, processors_on, fp32, device_greedy):
+    """Whether the "one_beam" route of generate() runs greedy decoding on the device (_greedy_on_device) instead of the torch
+    loop (_one_beam_loop): greedy only, without score post-processors, not in the fp32 validation mode.  device_greedy is
+    model._device_greedy (falsy: the torch loop)."""
+    return not do_sample and not processors_on and not fp32 and bool(device_greedy)
+
+
 def _forced_tokens(cur_len, max_length, bos_token_id, eos_token_id):
     """adjust_logits_during_generation (mixins.py:400-405) of a greedy beam search: the tokens forced at decode step cur_len, in
     the reference's order -- BOS on the first step, EOS on the last.  Both only when max_length == 2: the pipelined loop then
@@ -767,7 +774,12 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                  **model_specific_kwargs):
         """Reference src/model/mixins.py:33-384 (+ transformers 3.0.2 _generate_beam_search /
         _generate_no_beam_search).  Encoder once, KV-cached decoder steps on the device, beam
-        bookkeeping on the host exactly as the reference does it."""
+        bookkeeping on the host exactly as the reference does it.
+        return_scores=True returns (ids, scores): with beams the chosen hypotheses' scores; with num_beams == 1 and
+        do_sample=False a float32 [B] tensor on the model's device, the sum of the generated tokens' log-probabilities (after
+        the min_length ban and any score processors; the EOS token's included, nothing after it, no length normalisation --
+        the sum_logprobs of the reference's sample_sentence, src/model/utils.py:34-56).  do_sample=True with num_beams == 1
+        returns the ids only, whatever return_scores says: the sampling kernel leaves no log-probability."""
         eng = self._need_engine()
         cfg = self.config
 
@@ -855,7 +867,11 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                             bos_token_id=cfg.bos_token_id, decoder_start_token_id=decoder_start_token_id, fp32=fp32,
                             length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences)
         if route == "one_beam":
-            return self._one_beam_loop(eng, s, step_logits)
+            want_scores = return_scores and not do_sample
+            if _one_beam_on_device(do_sample, processors_on, fp32, getattr(self, "_device_greedy", True)):
+                return self._greedy_on_device(eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id,
+                                              want_scores)
+            return self._one_beam_loop(eng, s, step_logits, want_scores)
         book = _BeamBook(s)
         if route == "pipelined_beams":
             self._pipelined_beam_loop(eng, s, book)
@@ -866,11 +882,13 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         out = out.to(eng.device)
         return (out, torch.tensor(best_scores)) if return_scores else out
 
-    def _one_beam_loop(self, eng, s, step_logits):
+    def _one_beam_loop(self, eng, s, step_logits, want_scores=False):
         """Greedy / sampling without beams (transformers 3.0.2 _generate_no_beam_search): everything stays on the device; the
-        "every sentence has finished" test is read one step late (_LateStop)."""
+        "every sentence has finished" test is read one step late (_LateStop).  want_scores (greedy): also the sum over the
+        steps of log_softmax(the logits the token was chosen from)[token] for the rows unfinished on entry."""
         dev = eng.device
         unfinished = torch.ones(s.B, dtype=torch.long, device=dev)
+        scores = torch.zeros(s.B, dtype=torch.float32, device=dev) if want_scores else None
         cols = [torch.full((s.B,), s.decoder_start_token_id, dtype=torch.long, device=dev)]
         stop = _LateStop(eng, s.max_length + 1, torch.long)
         cur_len, keep = 1, None
@@ -887,6 +905,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                 nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1).squeeze(1)
             else:
                 nxt = torch.argmax(logits, dim=-1)
+                if want_scores:
+                    lp = torch.log_softmax(logits.float(), dim=-1).gather(1, nxt[:, None]).squeeze(1)
+                    scores += torch.where(unfinished.bool(), lp, torch.zeros_like(lp))
             tok = nxt * unfinished + s.pad_token_id * (1 - unfinished) if s.eos_token_id is not None else nxt
             cols.append(tok)
             cur_len += 1
@@ -897,7 +918,38 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                     break
         out = torch.stack(cols[:keep] if keep is not None else cols, dim=1)
         _inputs_end(eng, s.fp32)
-        return out
+        return (out, scores) if want_scores else out
+
+    def _greedy_on_device(self, eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id, want_scores):
+        """generate(num_beams=1, do_sample=False) without score post-processing: every decode step is gen_step ->
+        kmb_gen_greedy_step (EOS ban, argmax, the token's log-probability, the finished-row bookkeeping and the next step's
+        embedding in one launch).  It reads the fp32 logits the torch path reads and breaks ties to the lowest index as
+        torch.argmax does: the same tokens.  model._device_greedy = False selects the torch path."""
+        dev = eng.device
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        ids = torch.full((B, max_length), pad_token_id if pad_token_id is not None else 0, dtype=torch.long, device=dev)
+        ids[:, 0] = decoder_start_token_id
+        toks = [ids[:, 0].contiguous(), torch.empty(B, dtype=torch.long, device=dev)]   # ping-pong: step t reads one, writes the other
+        unfinished = torch.ones(B, dtype=torch.long, device=dev) if eos_token_id is not None else None
+        scores = torch.zeros(B, dtype=torch.float32, device=dev) if want_scores else None
+        dflags = torch.zeros(max_length + 1, dtype=torch.int32, device=dev)
+        stop = _LateStop(eng, max_length + 1, torch.int32)
+        cur_len, keep = 1, None
+        while cur_len < max_length:
+            # the tokens of step cur_len - 1 were embedded by the greedy step that chose them whenever it could (gen_step tells)
+            logits = eng.gen_step(toks[(cur_len - 1) % 2], cur_len - 1)
+            ban = eos if (eos >= 0 and cur_len < min_length) else -1
+            eng.greedy_step(logits, ban_token=ban, unfinished=unfinished, pad_token=pad_token_id if unfinished is not None else 0,
+                            eos_token=eos, next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1],
+                            logprob_sum=scores, embed_step=cur_len if cur_len + 1 < max_length else -1)
+            cur_len += 1
+            if unfinished is not None:   # the finished flag, read one step late as in the torch path
+                keep = stop.after(cur_len, dflags[cur_len - 1])
+                if keep is not None:
+                    break
+        out = ids[:, :keep if keep is not None else cur_len].contiguous()
+        eng.check_inputs_end()
+        return (out, scores) if want_scores else out
 
     def _pipelined_beam_loop(self, eng, s, book):
         """Greedy beam search and beam sampling on the device (kmb_beam_merge_select / kmb_beam_sample_step: the first num_beams
