@@ -93,9 +93,12 @@ typedef struct KmbAttn {
   kmb_bf16* O; int32_t ldo;
   float* lse;
   const kmb_bf16* dO; int32_t lddo;
-  kmb_bf16* dQ; kmb_bf16* dK; kmb_bf16* dV; int32_t lddq, lddk, lddv;
+  kmb_bf16* dQ; kmb_bf16* dK; kmb_bf16* dV; int32_t lddq, lddk, lddv;   /* backward: dO, dQ, dK, dV 16-byte aligned, strides multiples of 8 */
   float dq_scale;
-  /* optional bias-gradient partials (backward): per-batch-item column sums of dQ / dK / dV, row stride ld_colsum */
+  /* optional bias-gradient partials (backward): per-batch-item column sums of dQ (scaled by dq_scale) / dK / dV, fp32, taken from the
+   * accumulators before the bf16 rounding; head h of batch item b goes to columns 64 h .. 64 h + 63 of row b, row stride ld_colsum.
+   * All three pointers or none (a partial set is refused), and ld_colsum >= 64 H when they are given; the three may share one
+   * buffer (training: parts, parts + d, parts + 2 d with ld_colsum = 3 d).  Columns that no head owns are not written. */
   float* dq_colsum; float* dk_colsum; float* dv_colsum; int32_t ld_colsum;
 } KmbAttn;
 

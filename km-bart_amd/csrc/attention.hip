@@ -8,7 +8,8 @@
 // Forward : grid (B*H, ceil(Tq/64)), 4 waves, wave w owns 16 query rows; K/V tiles of 64 keys are
 //           staged once per workgroup in LDS; online softmax over key tiles.
 // Backward: grid (B*H); loops key tiles (outer) and query tiles (inner); P is recomputed from the
-//           saved log-sum-exp; dK/dV live in registers across the inner loop, dQ in LDS (fp32).
+//           saved log-sum-exp; dK/dV live in registers across the inner loop, dQ in LDS (fp32);
+//           delta = sum_k P * dP comes from a first pass over the tiles (the saved O is not read).
 // One LDS image per tile serves both MFMA operand shapes: row reads (ds_read_b128) and
 // transposed reads (ds_read_b64_tr_b16); the XOR swizzle below makes both conflict-free.
 #include <cstdlib>
@@ -383,8 +384,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
   char* Ps = smem + 4 * TILE_BYTES;
   char* dSs = smem + 5 * TILE_BYTES;
   float* lse_s = reinterpret_cast<float*>(smem + 6 * TILE_BYTES);
-  float* del_s = lse_s + 64;
-  float* colk = del_s + 64;   // [4 waves][64] column sums of dK over each wave's keys (bias-gradient partials)
+  float* colk = lse_s + 128;  // [4 waves][64] column sums of dK over each wave's keys (bias-gradient partials)
   float* colv = colk + 256;   // [4 waves][64] same for dV
   float* dQacc = colv + 256;  // [nqt*64][64] fp32
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -393,10 +393,74 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
   const bf16_t* Qh = p.Q + h * HD;
   const bf16_t* Kh = p.K + h * HD;
   const bf16_t* Vh = p.V + h * HD;
-  const bf16_t* Oh = p.O + h * HD;
   const bf16_t* dOh = p.dO + h * HD;
 
   const int nkt = (p.Tk + 63) / 64;
+  float* delta_all = dQacc + (size_t)nqt * 64 * 64;   // [nqt*64] the softmax backward's correction term of every query row
+  // S = Q K^T, dP = dO V^T and P = exp(S - lse) (0 where masked) of this wave's 16 query rows x the tile's 64 keys, from the staged images;
+  // P replaces S in `s`.  Both passes below go through it: the same bits.
+  auto probs = [&](int kt, int qt, f32x4 (&s)[4], f32x4 (&dp)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      const bf16x8 qf = frag_rows(Qs, wave, kk, r, g);
+      const bf16x8 df = frag_rows(dOs, wave, kk, r, g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, frag_rows(Ks, j, kk, r, g), s[j], 0, 0, 0);
+        dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, frag_rows(Vs, j, kk, r, g), dp[j], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = kt * 64 + j * 16 + r;
+      bool kv = key < p.Tk;
+      if (kv && p.key_mask != nullptr) kv = p.key_mask[(size_t)b * p.Tk + key] != 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int lrow = wave * 16 + g * 4 + q;
+        const int qi = qt * 64 + lrow;
+        const bool ok = kv && qi < p.Tq && (!p.causal || key <= qi);
+        const float lse = lse_s[lrow];
+        s[j][q] = (ok && lse != -INFINITY) ? __expf(s[j][q] - lse) : 0.f;
+      }
+    }
+  };
+  auto stage_lse = [&](int qt) {   // the tile's 64 log-sum-exps (rows past Tq: the last row's, masked later)
+    if (tid < 64) {
+      const int q = qt * 64 + tid;
+      lse_s[tid] = p.lse[((size_t)b * p.H + h) * p.Tq + (q < p.Tq ? q : p.Tq - 1)];
+    }
+  };
+  // ---- first pass: delta[q] = sum over ALL keys of P[q][k] * dP[q][k], in fp32 from the probabilities the second pass uses.  (It used to be
+  // rowsum(dO * O) from the forward's saved bf16 output: one rounding error per query row, the same for all its keys, which does not cancel
+  // in dK -- 1.6 x the error of the single-tile kernel on dQ / dK and 2.4 x on the dK column sums, whose exact value is zero.)
+  for (int qt = 0; qt < nqt; ++qt) {
+    __syncthreads();
+    stage_tile(Qs, Qh, (size_t)b * p.Tq, qt * 64, p.Tq, p.ldq, tid);
+    stage_tile(dOs, dOh, (size_t)b * p.Tq, qt * 64, p.Tq, p.lddo, tid);
+    stage_lse(qt);
+    float del4[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < nkt; ++kt) {
+      if (kt > 0) __syncthreads();   // everyone is done with the previous key tile
+      stage_tile(Ks, Kh, (size_t)b * p.Tk, kt * 64, p.Tk, p.ldk, tid);
+      stage_tile(Vs, Vh, (size_t)b * p.Tk, kt * 64, p.Tk, p.ldv, tid);
+      __syncthreads();
+      f32x4 s[4], dp[4];
+      probs(kt, qt, s, dp);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) del4[q] += s[j][q] * dp[j][q];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float v = group16_sum(del4[q]);   // a row's keys sit in the 16 lanes of the group
+      if (r == 0) delta_all[qt * 64 + wave * 16 + g * 4 + q] = v;
+    }
+  }
+  // ---- second pass: key tiles outside, query tiles inside ----
   for (int i = tid; i < 512; i += 256) colk[i] = 0.f;  // colk and colv are adjacent
   for (int kt = 0; kt < nkt; ++kt) {
     __syncthreads();
@@ -410,58 +474,19 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
       __syncthreads();
       stage_tile(Qs, Qh, (size_t)b * p.Tq, qt * 64, p.Tq, p.ldq, tid);
       stage_tile(dOs, dOh, (size_t)b * p.Tq, qt * 64, p.Tq, p.lddo, tid);
-      {  // delta = rowsum(dO * O), lse: wave w owns rows w*16..w*16+15 of the tile
-        int q = qt * 64 + wave * 16 + r;
-        q = q < p.Tq ? q : p.Tq - 1;
-        const bf16_t* orow = Oh + ((size_t)b * p.Tq + q) * p.ldo;
-        const bf16_t* drow = dOh + ((size_t)b * p.Tq + q) * p.lddo;
-        float a8[8], b8[8], acc = 0.f;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          unpack8(*reinterpret_cast<const u32x4*>(orow + half * 32 + g * 8), a8);
-          unpack8(*reinterpret_cast<const u32x4*>(drow + half * 32 + g * 8), b8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc += a8[e] * b8[e];
-        }
-        acc += __shfl_xor(acc, 16, 64);
-        acc += __shfl_xor(acc, 32, 64);
-        if (g == 0) {
-          del_s[wave * 16 + r] = acc;
-          lse_s[wave * 16 + r] = p.lse[((size_t)b * p.H + h) * p.Tq + q];
-        }
-      }
+      stage_lse(qt);
       __syncthreads();
-      // S = Q K^T and dP = dO V^T for this wave's 16 query rows x 64 keys
       f32x4 s[4], dp[4];
+      probs(kt, qt, s, dp);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const bf16x8 qf = frag_rows(Qs, wave, kk, r, g);
-        const bf16x8 df = frag_rows(dOs, wave, kk, r, g);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, frag_rows(Ks, j, kk, r, g), s[j], 0, 0, 0);
-          dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, frag_rows(Vs, j, kk, r, g), dp[j], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int key = kt * 64 + j * 16 + r;
-        bool kv = key < p.Tk;
-        if (kv && p.key_mask != nullptr) kv = p.key_mask[(size_t)b * p.Tk + key] != 0;
+      for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int lrow = wave * 16 + g * 4 + q;
-          const int qi = qt * 64 + lrow;
-          const bool ok = kv && qi < p.Tq && (!p.causal || key <= qi);
-          const float lse = lse_s[lrow];
-          const float pv = (ok && lse != -INFINITY) ? __expf(s[j][q] - lse) : 0.f;
-          const float ds = pv * (dp[j][q] - del_s[lrow]);
-          *reinterpret_cast<bf16_t*>(Ps + elem_off(lrow, j * 16 + r)) = f2bf(pv);
+          const float ds = s[j][q] * (dp[j][q] - delta_all[qt * 64 + lrow]);
+          *reinterpret_cast<bf16_t*>(Ps + elem_off(lrow, j * 16 + r)) = f2bf(s[j][q]);
           *reinterpret_cast<bf16_t*>(dSs + elem_off(lrow, j * 16 + r)) = f2bf(ds);
         }
-      }
       __syncthreads();
       // dQ[16 rows of this wave] += dS K ; dV[16 keys of this wave] += P^T dO ; dK += dS^T Q
       f32x4 dq[4];
@@ -898,6 +923,12 @@ const char* kmb_attn_check(const KmbAttn& p, int backward) {
     if (!p.dO || !p.dQ || !p.dK || !p.dV || !p.lse) return "attention backward: missing tensor";
     if ((p.lddo & 7) || (p.lddq & 7) || (p.lddk & 7) || (p.lddv & 7)) return "attention backward: row strides";
     if (((uintptr_t)p.dO & 15) || ((uintptr_t)p.dQ & 15)) return "attention backward: alignment";
+    // (the single-tile kernel stores dK / dV rows 16 bytes at a time, like dQ)
+    if (((uintptr_t)p.dK & 15) || ((uintptr_t)p.dV & 15)) return "attention backward: dK / dV must be 16-byte aligned";
+    // the single-tile kernel gates all three column sums on dk_colsum alone: a partial set would be skipped or dereference NULL
+    const int ncs = (p.dq_colsum != nullptr) + (p.dk_colsum != nullptr) + (p.dv_colsum != nullptr);
+    if (ncs != 0 && ncs != 3) return "attention backward: dq_colsum / dk_colsum / dv_colsum must be given all three or none";
+    if (ncs == 3 && p.ld_colsum < p.H * HD) return "attention backward: ld_colsum must be at least H * 64";
     if (p.Tq > 384) return "attention backward: Tq > 384 is not supported (dQ accumulator lives in LDS)";
   }
   return nullptr;
@@ -948,7 +979,7 @@ hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream) {
     else hipLaunchKernelGGL(attn_bwd_small_kernel<false>, dim3(grid), dim3(256), lds_s, stream, p);
     return hipGetLastError();
   }
-  const size_t lds = 6 * TILE_BYTES + (128 + 512) * sizeof(float) + (size_t)nqt * 64 * 64 * sizeof(float);
+  const size_t lds = 6 * TILE_BYTES + (128 + 512) * sizeof(float) + (size_t)nqt * 64 * (64 + 1) * sizeof(float);   // ... dQ accumulator, delta
   static size_t lds_set = 0;
   if (lds > lds_set) {
     hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

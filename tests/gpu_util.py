@@ -74,6 +74,19 @@ def attn_struct(Q, K, V, B, H, Tq, Tk, key_mask, causal, O, lse):
     return a
 
 
+def attn_bwd_fields(a, dO, dQ, dK, dV, colsums=None, dq_scale=0.125):
+    """Backward fields of a KmbAttn: dO / dQ / dK / dV are 2-D views (row strides from the views), colsums an optional
+    (dq_colsum, dk_colsum, dv_colsum) triple of fp32 views sharing one row stride."""
+    a.dO, a.lddo = ptr(dO), dO.stride(-2)
+    a.dQ, a.dK, a.dV = ptr(dQ), ptr(dK), ptr(dV)
+    a.lddq, a.lddk, a.lddv = dQ.stride(-2), dK.stride(-2), dV.stride(-2)
+    a.dq_scale = dq_scale
+    if colsums is not None:
+        a.dq_colsum, a.dk_colsum, a.dv_colsum = (ptr(c) for c in colsums)
+        a.ld_colsum = colsums[0].stride(-2)
+    return a
+
+
 def rel_err(a, b):
     a = a.float()
     b = b.float()
