@@ -291,8 +291,8 @@ int kmb_gen_encoder_states(kmb_handle* h, kmb_bf16* enc_out, void* stream);
  * tokens = NULL: the step runs on the tokens the preceding kmb_gen_beam_step(reorder_step = step - 1) chose and already
  * embedded (no embedding launch); fails when no such embedding is pending for `step` (kmb_gen_embedded_step). */
 int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_out, void* stream);
-/* the step whose tokens the last kmb_gen_beam_step (or kmb_gen_beam_sample_step, kmb_gen_greedy_step) embedded for a
- * kmb_gen_step(tokens = NULL), or -1: none pending (any
+/* the step whose tokens the last kmb_gen_beam_step (or kmb_gen_beam_sample_step, kmb_gen_greedy_step,
+ * kmb_gen_sample_step) embedded for a kmb_gen_step(tokens = NULL), or -1: none pending (any
  * kmb_gen_step or kmb_gen_beam_step since, or that beam step did not embed -- no reorder, no next step inside max_length, or the
  * decoder states kmb_gen_last_hidden returns still lived where the embedding goes).  Host state only: no stream work. */
 int kmb_gen_embedded_step(const kmb_handle* h);
@@ -366,6 +366,33 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
 int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
                     const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
                     int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, void* stream);
+/* kmb_sample_step that also says how likely its token was: the same launch, the same tokens and outputs for the same inputs, and
+ * lp = log(m_tok / sum of m_i over the kept i), m_i = exp(x_i - max x) -- the chosen token's log-probability under the distribution
+ * it was drawn from, i.e. after the EOS ban, NaN -> -inf, the division by the temperature, top-k and top-p (log_softmax of the
+ * filtered logits at the token: the `_scores` of the reference's sample_sentence, src/model/utils.py:30-36).  m is the mass the draw
+ * itself uses: 1 at the row maximum even when that is infinite, so lp is finite and <= 0 -- 0 when one token is kept,
+ * -log(number kept) for an all -inf or all-NaN row.  (Finite for finite positive noise, which Exp(1) draws are: only an infinite
+ * or NaN noise value at the maximum lets a kept token of mass 0 win the race, and its lp is -inf.)
+ * logprob_sum (fp32 [R], or NULL): logprob_sum[r] += lp for the rows that were unfinished on entry (every row without
+ * `unfinished`) -- the EOS token's own lp included, a finished row adds nothing: sample_sentence's sum_logprobs
+ * (src/model/utils.py:52-56).  logprob_out (fp32, or NULL): element r at logprob_out[r * ld_logprob] (ld_logprob >= 1; a column of
+ * a [R, max_length] buffer is written in place) receives this step's lp, 0 for a finished row.
+ * Deterministic: the kept masses are added in a fixed order, no floating-point atomics.  Bad arguments fail with a message and
+ * launch nothing. */
+int kmb_sample_scored_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
+                           const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                           int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, float* logprob_sum,
+                           float* logprob_out, int ld_logprob, void* stream);
+/* The decode loop's form of kmb_sample_scored_step on the logits the last kmb_gen_step wrote (V and R are the handle's; needs
+ * kmb_gen_begin with num_beams == 1): same outputs.  embed_step as in kmb_gen_greedy_step: >= 0, the same launch also embeds the
+ * chosen tokens for decode step embed_step (kmb_gen_step's own row code, bit-identical rows) into the generation workspace --
+ * unless that step lies outside the cache or d_model is not a multiple of 8 or > 1024: kmb_gen_embedded_step() tells, and
+ * kmb_gen_step(h, NULL, embed_step, ...) uses the rows.  kmb_gen_last_hidden keeps returning the step's decoder states.
+ * embed_step -1: no embedding. */
+int kmb_gen_sample_step(kmb_handle* h, const float* logits, int ld, float temperature, int top_k, float top_p, int ban_token,
+                        const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                        int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, float* logprob_sum,
+                        float* logprob_out, int ld_logprob, int embed_step, void* stream);
 /* One decode step's greedy tail of generate(num_beams=1, do_sample=False) (transformers 3.0.2 _generate_no_beam_search, the
  * mode the reference runs by default: vcg_generate.py --num_beams 1, the training callback of vcg_train.py:183-194), ONE
  * launch, one pass over the logits; stateless like kmb_sample_step, whose argument conventions it keeps.  Per row r < R of

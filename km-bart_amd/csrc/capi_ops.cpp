@@ -246,19 +246,24 @@ int64_t kmb_logsoftmax_topk_scratch(int rows) { return (int64_t)kmb_logsoftmax_t
 int kmb_sample_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
                     const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
                     int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, void* stream) {
-  if (!logits || !noise || !next_tokens) return kmb_set_error("kmb_sample_step: logits, noise and next_tokens are required");
-  if (V < 1 || V > KMB_SAMPLE_MAX_V || R < 0 || ld < V || ld_noise < V)
-    return kmb_set_error("kmb_sample_step: need 1 <= V <= 65536, R >= 0, ld >= V, ld_noise >= V");
-  if (!(temperature > 0.f) || std::isinf(temperature)) return kmb_set_error("kmb_sample_step: temperature must be finite and > 0");
-  if (top_k < 0) return kmb_set_error("kmb_sample_step: top_k must be >= 0");
-  if (!(top_p >= 0.f && top_p <= 1.f)) return kmb_set_error("kmb_sample_step: top_p must lie in [0, 1]");
-  if (ban_token < -1 || ban_token >= V) return kmb_set_error("kmb_sample_step: ban_token must be -1 or a token id < V");
-  if (unfinished && (pad_token < 0 || pad_token >= V || eos_token < -1 || eos_token >= V))
-    return kmb_set_error("kmb_sample_step: pad_token must be a token id, eos_token -1 or a token id");
-  if (ids && (t < 0 || t >= ld_ids)) return kmb_set_error("kmb_sample_step: need 0 <= t < ld_ids");
+  if (kmb_sample_validate("kmb_sample_step", logits, ld, V, R, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished,
+                          pad_token, eos_token, next_tokens, ids, t, ld_ids) != 0)
+    return -1;
   return hipfail(kmb_sample_step_launch(logits, ld, V, R, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished,
                                         pad_token, eos_token, next_tokens, ids, t, ld_ids, flag, info_out, (hipStream_t)stream),
                  "sample_step");
+}
+int kmb_sample_scored_step(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p, int ban_token,
+                           const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                           int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, float* logprob_sum,
+                           float* logprob_out, int ld_logprob, void* stream) {
+  if (kmb_sample_validate("kmb_sample_scored_step", logits, ld, V, R, temperature, top_k, top_p, ban_token, noise, ld_noise,
+                          unfinished, pad_token, eos_token, next_tokens, ids, t, ld_ids, logprob_out != nullptr, ld_logprob) != 0)
+    return -1;
+  return hipfail(kmb_sample_scored_step_launch(logits, ld, V, R, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished,
+                                               pad_token, eos_token, next_tokens, ids, t, ld_ids, flag, info_out, logprob_sum,
+                                               logprob_out, ld_logprob, (hipStream_t)stream),
+                 "sample_scored_step");
 }
 
 int kmb_greedy_step(const float* logits, int ld, int V, int R, int ban_token, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
@@ -310,6 +315,30 @@ int kmb_beam_sample_validate(const char* who, const float* logits, int ld, int V
   if (!(top_p > 0.f && top_p <= 1.f)) return bad("top_p must lie in (0, 1]");
   if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
   if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
+  return 0;
+}
+
+// The argument checks of kmb_sample_step, kmb_sample_scored_step and kmb_gen_sample_step (`who` names the caller in the message).
+int kmb_sample_validate(const char* who, const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p,
+                        int ban_token, const float* noise, int ld_noise, const int64_t* unfinished, int64_t pad_token,
+                        int64_t eos_token, const int64_t* next_tokens, const int64_t* ids, int t, int ld_ids, bool has_logprob_out,
+                        int ld_logprob) {
+  char buf[256];
+  auto bad = [&](const char* what) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return kmb_set_error(buf);
+  };
+  if (!logits || !noise || !next_tokens) return bad("logits, noise and next_tokens are required");
+  if (V < 1 || V > KMB_SAMPLE_MAX_V || R < 0 || ld < V || ld_noise < V)
+    return bad("need 1 <= V <= 65536, R >= 0, ld >= V, ld_noise >= V");
+  if (!(temperature > 0.f) || std::isinf(temperature)) return bad("temperature must be finite and > 0");
+  if (top_k < 0) return bad("top_k must be >= 0");
+  if (!(top_p >= 0.f && top_p <= 1.f)) return bad("top_p must lie in [0, 1]");
+  if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
+  if (unfinished && (pad_token < 0 || pad_token >= V || eos_token < -1 || eos_token >= V))
+    return bad("pad_token must be a token id, eos_token -1 or a token id");
+  if (ids && (t < 0 || t >= ld_ids)) return bad("need 0 <= t < ld_ids");
+  if (has_logprob_out && ld_logprob < 1) return bad("need ld_logprob >= 1 with logprob_out");
   return 0;
 }
 

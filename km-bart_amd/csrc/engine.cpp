@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "beam_sample.h"
 #include "greedy.h"
+#include "sample.h"
 #include "diag.h"
 
 namespace {
@@ -2484,6 +2485,33 @@ int kmb_gen_greedy_step(kmb_handle* h, const float* logits, int ld, int ban_toke
   G.x0_step = -1;
   HIPCHK(kmb_greedy_step_launch(logits, ld, h->V, G.R, ban_token, unfinished, pad_token, eos_token, next_tokens, ids, t, ld_ids, flag,
                                 logprob_sum, logprob_out, (hipStream_t)stream, embed ? &en : nullptr));
+  if (embed) G.x0_step = embed_step;
+  return 0;
+}
+
+// The sampling step of the decode loop (kmb_sample_scored_step on the logits of the last kmb_gen_step), with kmb_gen_greedy_step's
+// embed_step contract: the launch that draws the tokens embeds them for the next decode step.
+int kmb_gen_sample_step(kmb_handle* h, const float* logits, int ld, float temperature, int top_k, float top_p, int ban_token,
+                        const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token, int64_t eos_token,
+                        int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* info_out, float* logprob_sum,
+                        float* logprob_out, int ld_logprob, int embed_step, void* stream) {
+  if (!h) return fail("kmb_gen_sample_step: call kmb_gen_begin first");
+  auto& G = h->gen;
+  if (!G.active) return fail("kmb_gen_sample_step: call kmb_gen_begin first");
+  if (G.nb != 1) return fail("kmb_gen_sample_step: needs num_beams == 1, kmb_gen_begin had %d", G.nb);
+  if (embed_step < -1) return fail("kmb_gen_sample_step: embed_step must be -1 or a decode step");
+  // the stateless form's argument checks, before anything is launched or the generation state changes
+  if (kmb_sample_validate("kmb_gen_sample_step", logits, ld, h->V, G.R, temperature, top_k, top_p, ban_token, noise, ld_noise,
+                          unfinished, pad_token, eos_token, next_tokens, ids, t, ld_ids, logprob_out != nullptr, ld_logprob) != 0)
+    return -1;
+  const int d = h->d;
+  const bool embed = embed_step >= 0 && embed_step < G.Tmax && (d & 7) == 0 && d <= 1024;
+  if (embed && G.last_x == G.x0) std::swap(G.x0, G.x1);
+  const KmbEmbedNext en = embed ? gen_embed_next(h, embed_step) : KmbEmbedNext{};
+  G.x0_step = -1;
+  HIPCHK(kmb_sample_scored_step_launch(logits, ld, h->V, G.R, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished,
+                                       pad_token, eos_token, next_tokens, ids, t, ld_ids, flag, info_out, logprob_sum, logprob_out,
+                                       ld_logprob, (hipStream_t)stream, embed ? &en : nullptr));
   if (embed) G.x0_step = embed_step;
   return 0;
 }

@@ -1,6 +1,7 @@
 // Sampling tail of generate(do_sample=True, num_beams=1): transformers 3.0.2 _generate_no_beam_search as reached from the
 // reference's nucleus-sampling mode (src/generation.py:22-32, vcg_generate.py:97-106), per row in one launch:
-// EOS ban -> / temperature -> top-k -> top-p -> softmax -> exponential-race draw -> finished-row bookkeeping.
+// EOS ban -> / temperature -> top-k -> top-p -> softmax -> exponential-race draw -> finished-row bookkeeping
+// [-> the chosen token's log-probability under the filtered distribution -> the next step's embedding] (the scored form).
 //
 // One workgroup of 1024 lanes per row; the row stays in registers (NPER values per lane, token i = j * 1024 + lane).
 // Both thresholds come from a radix select over a 48-bit rank key (order-preserving value key << 16 | 0xffff - index:
@@ -12,6 +13,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "embed_row.h"
 #include "sample.h"
 #include "sample_keys.h"
 
@@ -31,6 +33,8 @@ struct SampleArgs {
   int64_t* unfinished; int64_t pad_token, eos_token;
   int64_t* next_tokens; int64_t* ids; int t, ld_ids;
   int32_t* flag; float* info_out;
+  float* logprob_sum; float* logprob_out; int ld_logprob;   // the scored form only
+  KmbEmbedNext en;
 };
 
 struct Smem {
@@ -43,6 +47,8 @@ struct Smem {
   uint32_t sel_bin, sel_cnt, sel_key;
   int sel_idx;
   unsigned long long sel_above;
+  float wsum[kWaves];     // the scored form: a wave's kept mass and the key of its best token
+  uint32_t wkey[kWaves];
 };
 
 // A new name for the lane index in every phase: nothing derived from it (a token index, a 64-bit address offset) is
@@ -150,7 +156,12 @@ __device__ __forceinline__ uint64_t select_rank(Smem& sh, uint32_t (&key)[NPER],
   return prefix;
 }
 
-template <int NPER>
+// kScored: also lp = log(m_tok / sum of m_i over the kept tokens), m = rel_exp, the masses the draw itself uses -- summed in the
+// draw loop, which already visits every kept token once, per lane in ascending j, by a butterfly inside the wave (a + b == b + a: every
+// lane holds the same bits) and over the waves in wave order: a fixed order, no floating-point atomics.  The row maximum is always kept
+// and has mass 1, so the sum is >= 1 and lp <= 0; log(m_tok) is taken as x_tok - max (0 at the maximum itself, infinite or not).
+// Then wave 0 embeds the chosen token for the next decode step (a.en.E != nullptr; NCH as kmb_embed_ln_fwd_launch picks it).
+template <int NPER, bool kScored, int NCH>
 __global__ __launch_bounds__(kThreads) void sample_step_kernel(SampleArgs a) {
   __shared__ Smem sh;
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -193,8 +204,8 @@ __global__ __launch_bounds__(kThreads) void sample_step_kernel(SampleArgs a) {
   // draw: argmax over the kept tokens of p / q, p = softmax over them; q is read at kept tokens only
   const float* q = a.noise + (size_t)r * a.ld_noise;
   const uint32_t cut_key = (uint32_t)(cut >> 16), cut_inv = (uint32_t)(cut & 0xffffu);
-  uint32_t n = 0, kmin = 0xffffffffu;
-  float best = -INFINITY;
+  uint32_t n = 0, kmin = 0xffffffffu, bestk = 0;
+  float best = -INFINITY, msum = 0.f;
   int besti = kNone;
   const int lt = fresh_tid();
   fence_keys(key);
@@ -204,8 +215,13 @@ __global__ __launch_bounds__(kThreads) void sample_step_kernel(SampleArgs a) {
     if (key[j] > cut_key || (key[j] == cut_key && (uint32_t)(0xffff - i) >= cut_inv)) {
       ++n;
       kmin = min(kmin, key[j]);
-      float v = rel_exp(key[j], mx) / q[i];
+      const float m = rel_exp(key[j], mx);
+      float v = m / q[i];
       if (v != v) v = -INFINITY;
+      if (kScored) {
+        msum += m;
+        if (v > best || besti == kNone) bestk = key[j];
+      }
       if (v > best || besti == kNone) { best = v; besti = i; }   // i ascends with j: the lowest index wins a tie
     }
   }
@@ -215,31 +231,74 @@ __global__ __launch_bounds__(kThreads) void sample_step_kernel(SampleArgs a) {
     kmin = min(kmin, __shfl_xor(kmin, o, 64));
     const float ob = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(besti, o, 64);
-    if (oi != kNone && (besti == kNone || ob > best || (ob == best && oi < besti))) { best = ob; besti = oi; }
+    const bool take = oi != kNone && (besti == kNone || ob > best || (ob == best && oi < besti));
+    if (kScored) {
+      msum += __shfl_xor(msum, o, 64);
+      const uint32_t ok = __shfl_xor(bestk, o, 64);
+      if (take) bestk = ok;
+    }
+    if (take) { best = ob; besti = oi; }
   }
-  if (lane == 0) { sh.wc[w] = n; sh.wm[w] = kmin; sh.wf[w] = best; sh.wi[w] = besti; }
+  if (lane == 0) {
+    sh.wc[w] = n; sh.wm[w] = kmin; sh.wf[w] = best; sh.wi[w] = besti;
+    if (kScored) { sh.wsum[w] = msum; sh.wkey[w] = bestk; }
+  }
   __syncthreads();
-  if (tid != 0) return;
-  for (int v = 1; v < kWaves; ++v) {
-    n += sh.wc[v];
-    kmin = min(kmin, (uint32_t)sh.wm[v]);
-    const float ob = sh.wf[v];
-    const int oi = sh.wi[v];
-    if (oi != kNone && (besti == kNone || ob > best || (ob == best && oi < besti))) { best = ob; besti = oi; }
+  if (kScored ? w != 0 : tid != 0) return;
+  int tok32 = 0;
+  if (lane == 0) {
+    for (int v = 1; v < kWaves; ++v) {
+      n += sh.wc[v];
+      kmin = min(kmin, (uint32_t)sh.wm[v]);
+      const float ob = sh.wf[v];
+      const int oi = sh.wi[v];
+      const bool take = oi != kNone && (besti == kNone || ob > best || (ob == best && oi < besti));
+      if (kScored) {
+        msum += sh.wsum[v];
+        if (take) bestk = sh.wkey[v];
+      }
+      if (take) { best = ob; besti = oi; }
+    }
+    int64_t tok = besti;   // the top token is always kept: a real column
+    bool live = true;
+    if (a.unfinished) {
+      int64_t u = a.unfinished[r];
+      live = u != 0;
+      if (!u) tok = a.pad_token;
+      u = (u && tok != a.eos_token) ? 1 : 0;
+      a.unfinished[r] = u;
+      if (u && a.flag) atomicOr(a.flag, 1);
+    } else if (a.flag) {
+      atomicOr(a.flag, 1);
+    }
+    a.next_tokens[r] = tok;
+    if (a.ids) a.ids[(size_t)r * a.ld_ids + a.t] = tok;
+    if (a.info_out) { a.info_out[2 * r] = (float)n; a.info_out[2 * r + 1] = key_value(kmin); }
+    if (kScored) {
+      const float x = key_value(bestk);
+      const float lp = live ? (x == mx ? 0.f : x - mx) - logf(msum) : 0.f;
+      if (a.logprob_sum && live) a.logprob_sum[r] += lp;
+      if (a.logprob_out) a.logprob_out[(size_t)r * a.ld_logprob] = lp;
+    }
+    tok32 = (int)tok;
   }
-  int64_t tok = besti;   // the top token is always kept: a real column
-  if (a.unfinished) {
-    int64_t u = a.unfinished[r];
-    if (!u) tok = a.pad_token;
-    u = (u && tok != a.eos_token) ? 1 : 0;
-    a.unfinished[r] = u;
-    if (u && a.flag) atomicOr(a.flag, 1);
-  } else if (a.flag) {
-    atomicOr(a.flag, 1);
-  }
-  a.next_tokens[r] = tok;
-  if (a.ids) a.ids[(size_t)r * a.ld_ids + a.t] = tok;
-  if (a.info_out) { a.info_out[2 * r] = (float)n; a.info_out[2 * r + 1] = key_value(kmin); }
+  if (!kScored) return;
+  // the next decode step's input row, by this wave (greedy.hip's tail)
+  if (a.en.E == nullptr) return;
+  int etok = __shfl(tok32, 0, 64);
+  etok = etok < 0 ? 0 : (etok >= a.en.V ? a.en.V - 1 : etok);   // never read outside the table
+  embed_ln_row<NCH>(a.en.E + (size_t)etok * a.en.D, a.en.prow, a.en.scale, a.en.gamma, a.en.beta, nullptr, a.en.y, nullptr, nullptr, r,
+                    a.en.D, a.en.eps, KmbDrop{0u, 0u, 1.f}, lane);
+}
+
+template <bool kScored, int NCH>
+void launch_for(int V, int R, const SampleArgs& a, hipStream_t stream) {
+  if (V <= 16 * kThreads)
+    hipLaunchKernelGGL((sample_step_kernel<16, kScored, NCH>), dim3(R), dim3(kThreads), 0, stream, a);
+  else if (V <= 52 * kThreads)   // vcg_base: 50 320
+    hipLaunchKernelGGL((sample_step_kernel<52, kScored, NCH>), dim3(R), dim3(kThreads), 0, stream, a);
+  else
+    hipLaunchKernelGGL((sample_step_kernel<64, kScored, NCH>), dim3(R), dim3(kThreads), 0, stream, a);
 }
 
 }  // namespace
@@ -251,12 +310,28 @@ hipError_t kmb_sample_step_launch(const float* logits, int ld, int V, int R, flo
   if (V > KMB_SAMPLE_MAX_V) return hipErrorNotSupported;
   if (R <= 0) return hipSuccess;
   const SampleArgs a{logits, ld, V, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished, pad_token, eos_token,
-                     next_tokens, ids, t, ld_ids, flag, info_out};
-  if (V <= 16 * kThreads)
-    hipLaunchKernelGGL(sample_step_kernel<16>, dim3(R), dim3(kThreads), 0, stream, a);
-  else if (V <= 52 * kThreads)   // vcg_base: 50 320
-    hipLaunchKernelGGL(sample_step_kernel<52>, dim3(R), dim3(kThreads), 0, stream, a);
+                     next_tokens, ids, t, ld_ids, flag, info_out, nullptr, nullptr, 0, KmbEmbedNext{}};
+  launch_for<false, 1>(V, R, a, stream);
+  return hipGetLastError();
+}
+
+hipError_t kmb_sample_scored_step_launch(const float* logits, int ld, int V, int R, float temperature, int top_k, float top_p,
+                                         int ban_token, const float* noise, int ld_noise, int64_t* unfinished, int64_t pad_token,
+                                         int64_t eos_token, int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag,
+                                         float* info_out, float* logprob_sum, float* logprob_out, int ld_logprob, hipStream_t stream,
+                                         const KmbEmbedNext* embed) {
+  if (V > KMB_SAMPLE_MAX_V) return hipErrorNotSupported;
+  if (R <= 0) return hipSuccess;
+  SampleArgs a{logits, ld, V, temperature, top_k, top_p, ban_token, noise, ld_noise, unfinished, pad_token, eos_token,
+               next_tokens, ids, t, ld_ids, flag, info_out, logprob_sum, logprob_out, ld_logprob, KmbEmbedNext{}};
+  if (embed != nullptr && embed->E != nullptr) {
+    if ((embed->D & 7) || embed->D < 8 || embed->D > 1024) return hipErrorNotSupported;
+    a.en = *embed;
+  }
+  // the chunk count of kmb_embed_ln_fwd_launch for this width: the rows must come out with the same bits
+  if (a.en.E != nullptr && a.en.D > 512)
+    launch_for<true, 2>(V, R, a, stream);
   else
-    hipLaunchKernelGGL(sample_step_kernel<64>, dim3(R), dim3(kThreads), 0, stream, a);
+    launch_for<true, 1>(V, R, a, stream);
   return hipGetLastError();
 }

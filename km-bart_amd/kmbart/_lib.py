@@ -147,6 +147,10 @@ PROTOTYPES = {
                                          C.c_int64, c_p]),
     "kmb_sample_step": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, f32, C.c_int, f32, C.c_int, c_p, C.c_int, c_p, i64, i64, c_p,
                                   c_p, C.c_int, C.c_int, c_p, c_p, c_p]),
+    "kmb_sample_scored_step": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, f32, C.c_int, f32, C.c_int, c_p, C.c_int, c_p, i64, i64, c_p,
+                                         c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p, C.c_int, c_p]),
+    "kmb_gen_sample_step": (C.c_int, [c_p, c_p, C.c_int, f32, C.c_int, f32, C.c_int, c_p, C.c_int, c_p, i64, i64, c_p,
+                                      c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p, C.c_int, C.c_int, c_p]),
     "kmb_greedy_step": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, i64, i64, c_p, c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p]),
     "kmb_gen_greedy_step": (C.c_int, [c_p, c_p, C.c_int, C.c_int, c_p, i64, i64, c_p, c_p, C.c_int, C.c_int, c_p, c_p, c_p, C.c_int,
                                       c_p]),

@@ -702,26 +702,47 @@ class Engine:
             lambda: self.lib.kmb_beam_sample_step(ptr(logits), logits.stride(0), V, B, int(num_beams), ptr(add), *args, _stream()))
 
     def sample_step(self, logits, noise, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, unfinished=None, pad_token=0,
-                    eos_token=-1, next_tokens=None, ids=None, t=0, flag=None, info_out=None):
+                    eos_token=-1, next_tokens=None, ids=None, t=0, flag=None, info_out=None, logprob_sum=None, logprob_out=None,
+                    embed_step=-1):
         """One decode step's sampling tail (kmb_sample_step): EOS ban, temperature, top-k, top-p and the exponential-race
         draw on `noise` (fp32 [R, >= V] Exp(1) draws) in one launch.  `logits` may be gen_step's padded view.  Returns
         next_tokens (int64 [R]); unfinished (int64 [R]) and the id buffer ids (int64 [R, ld], column t) are updated in place;
         flag (int32, one element) is OR-ed with 1 while a row is unfinished; info_out (fp32 [R, 2]): kept count, smallest
-        kept value."""
+        kept value.
+        logprob_sum (fp32 [R]) gains the chosen token's log-probability under the filtered distribution for the rows unfinished
+        on entry, logprob_out (fp32, R elements, may be a strided column view) receives this step's (0 for a finished row):
+        the same launch, the same tokens (kmb_sample_scored_step).  embed_step >= 0, when `logits` are gen_step's, unedited
+        since (their _version unchanged): the launch also embeds the chosen tokens for that decode step
+        (kmb_gen_sample_step), and gen_step(next_tokens, embed_step) then runs without an embedding launch, as after
+        greedy_step.  With none of the three given the call is kmb_sample_step itself."""
         R, V = logits.shape[0], int(self.config.vocab_size)
         for x, dt in ((logits, torch.float32), (noise, torch.float32), (unfinished, torch.int64), (ids, torch.int64),
-                      (flag, torch.int32), (info_out, torch.float32)):
+                      (flag, torch.int32), (info_out, torch.float32), (logprob_sum, torch.float32)):
             assert x is None or (x.device == self.device and x.dtype == dt and x.stride(-1) == 1), "sample_step: bad tensor"
         assert noise.shape[0] == R and (unfinished is None or unfinished.numel() == R) and (ids is None or ids.shape[0] == R)
         assert info_out is None or info_out.is_contiguous() and info_out.numel() == 2 * R
+        assert logprob_sum is None or (logprob_sum.is_contiguous() and logprob_sum.numel() == R)
+        assert logprob_out is None or (logprob_out.device == self.device and logprob_out.dtype == torch.float32
+                                       and logprob_out.dim() == 1 and logprob_out.numel() == R
+                                       and (R == 1 or logprob_out.stride(0) >= 1)), "sample_step: bad logprob_out"
         if next_tokens is None:
             next_tokens = torch.empty((R,), dtype=torch.int64, device=self.device)
         assert next_tokens.is_contiguous() and next_tokens.numel() == R and next_tokens.dtype == torch.int64
+        args = (float(temperature), int(top_k), float(top_p), int(ban_token), ptr(noise), noise.stride(0), ptr(unfinished),
+                int(pad_token), int(eos_token), ptr(next_tokens), ptr(ids), int(t), ids.stride(0) if ids is not None else 0,
+                ptr(flag), ptr(info_out))
+        self._folded = None   # next_tokens may be the buffer an earlier step's pending embedding was recorded for
         with torch.cuda.device(self.device):
-            check(self.lib.kmb_sample_step(ptr(logits), logits.stride(0), V, R, float(temperature), int(top_k), float(top_p),
-                                           int(ban_token), ptr(noise), noise.stride(0), ptr(unfinished), int(pad_token),
-                                           int(eos_token), ptr(next_tokens), ptr(ids), int(t),
-                                           ids.stride(0) if ids is not None else 0, ptr(flag), ptr(info_out), _stream()))
+            if logprob_sum is None and logprob_out is None and embed_step == -1:
+                check(self.lib.kmb_sample_step(ptr(logits), logits.stride(0), V, R, *args, _stream()))
+                return next_tokens
+            scored = (ptr(logprob_sum), ptr(logprob_out), max(int(logprob_out.stride(0)), 1) if logprob_out is not None else 1)
+            if logits is self.__dict__.get("_gen_logits") and logits._version == self._gen_logits_version:
+                check(self.lib.kmb_gen_sample_step(self.h, ptr(logits), logits.stride(0), *args, *scored, int(embed_step), _stream()))
+                if embed_step >= 0 and self.lib.kmb_gen_embedded_step(self.h) == embed_step:
+                    self._folded = (next_tokens, next_tokens._version, int(embed_step))
+            else:
+                check(self.lib.kmb_sample_scored_step(ptr(logits), logits.stride(0), V, R, *args, *scored, _stream()))
         return next_tokens
 
     def greedy_step(self, logits, ban_token=-1, unfinished=None, pad_token=0, eos_token=-1, next_tokens=None, ids=None, t=0,

@@ -1,6 +1,6 @@
 from src.model.config import MultiModalBartConfig
-from src.model.model import (LazyLogits, MultiModalBartForConditionalGeneration, MultiModalBartForPreTraining,
+from src.model.model import (GenerationLogprobs, LazyLogits, MultiModalBartForConditionalGeneration, MultiModalBartForPreTraining,
                              MultiModalBartModel, SequenceScore)
 
 __all__ = ["MultiModalBartConfig", "MultiModalBartForConditionalGeneration", "MultiModalBartForPreTraining",
-           "MultiModalBartModel", "LazyLogits", "SequenceScore"]
+           "MultiModalBartModel", "LazyLogits", "SequenceScore", "GenerationLogprobs"]

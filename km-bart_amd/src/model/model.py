@@ -116,6 +116,22 @@ class SequenceScore(collections.namedtuple("SequenceScore", ("token_logprobs", "
         return torch.exp(self.nll / self.count.to(torch.float32))
 
 
+class GenerationLogprobs(collections.namedtuple("GenerationLogprobs", ("token_logprobs", "sum_logprobs"))):
+    """What `generate(num_beams=1, return_logprobs=True)` returns next to the ids, on the model's device: token_logprobs fp32
+    [B_eff, ids.shape[1] - 1], entry [:, t - 1] the log-probability of ids[:, t] under the distribution it was chosen from (for
+    sampling: after the min_length ban, the temperature, top-k and top-p), 0 after a row's EOS; sum_logprobs fp32 [B_eff], their
+    sum per row -- the EOS token's included, no length normalisation: the sum_logprobs of the reference's sample_sentence
+    (src/model/utils.py:52-56)."""
+    __slots__ = ()
+
+
+def _chosen_logprobs(logits, tokens, unfinished=None):
+    """The per-step score of the torch one-beam loop: log_softmax(logits)[token] per row in fp32, `logits` [R, V] being what the
+    token was chosen from (for sampling the filtered logits, -inf at removed tokens); 0 where unfinished [R] is 0."""
+    lp = torch.log_softmax(logits.float(), dim=-1).gather(1, tokens[:, None]).squeeze(1)
+    return lp if unfinished is None else torch.where(unfinished.bool(), lp, torch.zeros_like(lp))
+
+
 class LazyLogits:
     """outputs[1] of a training forward: the fp32 logits are produced on first use -- ONE head GEMM on the decoder
     states that forward left in the engine's workspace (the actual training logits, dropout included, as the reference
@@ -771,7 +787,7 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                  repetition_penalty=None, bad_words_ids=None, bos_token_id=None, pad_token_id=None,
                  eos_token_id=None, length_penalty=None, no_repeat_ngram_size=None, num_return_sequences=None,
                  attention_mask=None, decoder_start_token_id=None, use_cache=None, return_scores=False,
-                 **model_specific_kwargs):
+                 return_logprobs=False, **model_specific_kwargs):
         """Reference src/model/mixins.py:33-384 (+ transformers 3.0.2 _generate_beam_search /
         _generate_no_beam_search).  Encoder once, KV-cached decoder steps on the device, beam
         bookkeeping on the host exactly as the reference does it.
@@ -779,7 +795,14 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         do_sample=False a float32 [B] tensor on the model's device, the sum of the generated tokens' log-probabilities (after
         the min_length ban and any score processors; the EOS token's included, nothing after it, no length normalisation --
         the sum_logprobs of the reference's sample_sentence, src/model/utils.py:34-56).  do_sample=True with num_beams == 1
-        returns the ids only, whatever return_scores says: the sampling kernel leaves no log-probability."""
+        returns the ids only, whatever return_scores says (use return_logprobs).
+        return_logprobs=True (num_beams == 1 only, greedy or sampling, every one-beam path) returns (ids,
+        GenerationLogprobs(token_logprobs, sum_logprobs)) whatever return_scores says: each generated token's log-probability
+        under the distribution it was chosen from and their sum per row; the device sampler writes them in the launch that
+        draws the token (kmb_gen_sample_step)."""
+        if return_logprobs and (num_beams if num_beams is not None else self.config.num_beams) != 1:
+            raise ValueError("generate(return_logprobs=True) needs num_beams == 1: a beam hypothesis's score is what "
+                             "return_scores=True returns")
         eng = self._need_engine()
         cfg = self.config
 
@@ -859,7 +882,7 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                               getattr(self, "_sampler", None) is not None, V)
         if route == "device_sampling":
             return self._sample_on_device(eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id,
-                                          eos_token_id, decoder_start_token_id)
+                                          eos_token_id, decoder_start_token_id, return_logprobs)
         s = SimpleNamespace(B=B, V=V, R=B * num_beams, num_beams=num_beams, max_length=max_length, min_length=min_length,
                             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, processors_on=processors_on,
                             repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -870,8 +893,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             want_scores = return_scores and not do_sample
             if _one_beam_on_device(do_sample, processors_on, fp32, getattr(self, "_device_greedy", True)):
                 return self._greedy_on_device(eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id,
-                                              want_scores)
-            return self._one_beam_loop(eng, s, step_logits, want_scores)
+                                              want_scores, return_logprobs)
+            return self._one_beam_loop(eng, s, step_logits, want_scores, return_logprobs)
         book = _BeamBook(s)
         if route == "pipelined_beams":
             self._pipelined_beam_loop(eng, s, book)
@@ -882,13 +905,16 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         out = out.to(eng.device)
         return (out, torch.tensor(best_scores)) if return_scores else out
 
-    def _one_beam_loop(self, eng, s, step_logits, want_scores=False):
+    def _one_beam_loop(self, eng, s, step_logits, want_scores=False, want_logprobs=False):
         """Greedy / sampling without beams (transformers 3.0.2 _generate_no_beam_search): everything stays on the device; the
         "every sentence has finished" test is read one step late (_LateStop).  want_scores (greedy): also the sum over the
-        steps of log_softmax(the logits the token was chosen from)[token] for the rows unfinished on entry."""
+        steps of log_softmax(the logits the token was chosen from)[token] for the rows unfinished on entry.  want_logprobs
+        (greedy or sampling; wins over want_scores): GenerationLogprobs of the same quantity per step, for sampling on the
+        filtered logits."""
         dev = eng.device
         unfinished = torch.ones(s.B, dtype=torch.long, device=dev)
-        scores = torch.zeros(s.B, dtype=torch.float32, device=dev) if want_scores else None
+        scores = torch.zeros(s.B, dtype=torch.float32, device=dev) if (want_scores or want_logprobs) else None
+        lps = []
         cols = [torch.full((s.B,), s.decoder_start_token_id, dtype=torch.long, device=dev)]
         stop = _LateStop(eng, s.max_length + 1, torch.long)
         cur_len, keep = 1, None
@@ -904,10 +930,13 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                 lg = _top_k_top_p_filtering(lg.clone(), top_k=s.top_k, top_p=s.top_p)
                 nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1).squeeze(1)
             else:
+                lg = logits
                 nxt = torch.argmax(logits, dim=-1)
-                if want_scores:
-                    lp = torch.log_softmax(logits.float(), dim=-1).gather(1, nxt[:, None]).squeeze(1)
-                    scores += torch.where(unfinished.bool(), lp, torch.zeros_like(lp))
+            if want_logprobs or (want_scores and not s.do_sample):
+                lp = _chosen_logprobs(lg, nxt, unfinished)
+                scores += lp
+                if want_logprobs:
+                    lps.append(lp)
             tok = nxt * unfinished + s.pad_token_id * (1 - unfinished) if s.eos_token_id is not None else nxt
             cols.append(tok)
             cur_len += 1
@@ -918,9 +947,12 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                     break
         out = torch.stack(cols[:keep] if keep is not None else cols, dim=1)
         _inputs_end(eng, s.fp32)
+        if want_logprobs:
+            return out, GenerationLogprobs(torch.stack(lps[:out.shape[1] - 1], dim=1), scores)
         return (out, scores) if want_scores else out
 
-    def _greedy_on_device(self, eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id, want_scores):
+    def _greedy_on_device(self, eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id, want_scores,
+                          want_logprobs=False):
         """generate(num_beams=1, do_sample=False) without score post-processing: every decode step is gen_step ->
         kmb_gen_greedy_step (EOS ban, argmax, the token's log-probability, the finished-row bookkeeping and the next step's
         embedding in one launch).  It reads the fp32 logits the torch path reads and breaks ties to the lowest index as
@@ -931,7 +963,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         ids[:, 0] = decoder_start_token_id
         toks = [ids[:, 0].contiguous(), torch.empty(B, dtype=torch.long, device=dev)]   # ping-pong: step t reads one, writes the other
         unfinished = torch.ones(B, dtype=torch.long, device=dev) if eos_token_id is not None else None
-        scores = torch.zeros(B, dtype=torch.float32, device=dev) if want_scores else None
+        scores = torch.zeros(B, dtype=torch.float32, device=dev) if (want_scores or want_logprobs) else None
+        token_lps = torch.zeros((B, max_length - 1), dtype=torch.float32, device=dev) if want_logprobs else None
+        step_lp = torch.empty(B, dtype=torch.float32, device=dev) if want_logprobs else None
         dflags = torch.zeros(max_length + 1, dtype=torch.int32, device=dev)
         stop = _LateStop(eng, max_length + 1, torch.int32)
         cur_len, keep = 1, None
@@ -941,7 +975,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             ban = eos if (eos >= 0 and cur_len < min_length) else -1
             eng.greedy_step(logits, ban_token=ban, unfinished=unfinished, pad_token=pad_token_id if unfinished is not None else 0,
                             eos_token=eos, next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1],
-                            logprob_sum=scores, embed_step=cur_len if cur_len + 1 < max_length else -1)
+                            logprob_sum=scores, logprob_out=step_lp, embed_step=cur_len if cur_len + 1 < max_length else -1)
+            if want_logprobs:
+                token_lps[:, cur_len - 1].copy_(step_lp)
             cur_len += 1
             if unfinished is not None:   # the finished flag, read one step late as in the torch path
                 keep = stop.after(cur_len, dflags[cur_len - 1])
@@ -949,6 +985,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                     break
         out = ids[:, :keep if keep is not None else cur_len].contiguous()
         eng.check_inputs_end()
+        if want_logprobs:
+            return out, GenerationLogprobs(token_lps[:, :out.shape[1] - 1].contiguous(), scores)
         return (out, scores) if want_scores else out
 
     def _pipelined_beam_loop(self, eng, s, book):
@@ -1062,9 +1100,10 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             cur_len += 1
 
     def _sample_on_device(self, eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id, eos_token_id,
-                          decoder_start_token_id):
+                          decoder_start_token_id, want_logprobs=False):
         """generate(do_sample=True, num_beams=1) without score post-processing: every decode step is gen_step -> Exp(1)
-        noise -> kmb_sample_step (EOS ban, temperature, top-k, top-p, draw and the finished-row bookkeeping in one launch).
+        noise -> kmb_gen_sample_step (EOS ban, temperature, top-k, top-p, draw, the finished-row bookkeeping, the next step's
+        embedding and, with want_logprobs, the token's log-probability under the filtered distribution, in one launch).
         The noise is drawn as torch.multinomial(probs, 1) draws it ([B, V] exponential_ on the default generator), so a
         seeded run consumes the random stream the torch path consumes and picks the same tokens except where fp32 rounding
         decides a near-tie.  model._device_sampling = False selects the torch path."""
@@ -1075,16 +1114,21 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         toks = [ids[:, 0].contiguous(), torch.empty(B, dtype=torch.long, device=dev)]   # ping-pong: step t reads one, writes the other
         unfinished = torch.ones(B, dtype=torch.long, device=dev) if eos_token_id is not None else None
         noise = torch.empty((B, V), dtype=torch.float32, device=dev)
+        sums = torch.zeros(B, dtype=torch.float32, device=dev) if want_logprobs else None
+        token_lps = torch.zeros((B, max_length - 1), dtype=torch.float32, device=dev) if want_logprobs else None
         dflags = torch.zeros(max_length + 1, dtype=torch.int32, device=dev)
         stop = _LateStop(eng, max_length + 1, torch.int32)
         cur_len, keep = 1, None
         while cur_len < max_length:
+            # the tokens of step cur_len - 1 were embedded by the sampling step that drew them whenever it could (gen_step tells)
             logits = eng.gen_step(toks[(cur_len - 1) % 2], cur_len - 1)
             ban = eos if (eos >= 0 and cur_len < min_length) else -1
             noise.exponential_(1)
             eng.sample_step(logits, noise, temperature, top_k, top_p, ban_token=ban, unfinished=unfinished,
                             pad_token=pad_token_id if unfinished is not None else 0, eos_token=eos,
-                            next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1])
+                            next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1],
+                            logprob_sum=sums, logprob_out=token_lps[:, cur_len - 1] if want_logprobs else None,
+                            embed_step=cur_len if cur_len + 1 < max_length else -1)
             cur_len += 1
             if unfinished is not None:   # the finished flag, read one step late as in the torch path
                 keep = stop.after(cur_len, dflags[cur_len - 1])
@@ -1092,6 +1136,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                     break
         out = ids[:, :keep if keep is not None else cur_len].contiguous()
         eng.check_inputs_end()
+        if want_logprobs:
+            return out, GenerationLogprobs(token_lps[:, :out.shape[1] - 1].contiguous(), sums)
         return out
 
     @staticmethod

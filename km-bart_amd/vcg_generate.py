@@ -71,6 +71,8 @@ def parse_args(argv=None):
     p.add_argument("--do_sample", action="store_true")
     p.add_argument("--top_p", default=1.0, type=float)
     p.add_argument("--top_k", default=0, type=int)
+    p.add_argument("--with_scores", action="store_true",
+                   help="with --num_beams 1: add \"scores\" to every record, the generations' sums of token log-probabilities")
     p.add_argument("--gpu_num", default=1, type=int)
     p.add_argument("--cpu", action="store_true")
     p.add_argument("--amp", action="store_true")

@@ -7,6 +7,8 @@ cross-attention K/V computed once per batch item.  Prints one JSON line.
 sampler (kmb_sample_step), with --beams N > 1 beam sampling on kmb_beam_sample_step; unless --no-host, the torch host loop
 (model._device_sampling = False) is alternated with it in one process, each generate timed to a device synchronise; one JSON
 line per path, the first row of each seeded output shared between them.  --host-sampling times the torch path alone.
+--logprobs (with --beams 1) asks generate for return_logprobs=True: the sampler then also writes every token's log-probability.
+Each line carries the repetitions' own times ("rep_ms"): their spread is the noise a difference between two runs is read against.
 """
 import argparse
 import json
@@ -34,6 +36,7 @@ ap.add_argument("--temperature", type=float, default=1.0)
 ap.add_argument("--num-gen", type=int, default=1)
 ap.add_argument("--host-sampling", action="store_true", help="time the torch sampling path only")
 ap.add_argument("--no-host", action="store_true", help="time the device sampler only")
+ap.add_argument("--logprobs", action="store_true", help="generate(return_logprobs=True): one-beam sampling with token log-probabilities")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
@@ -44,9 +47,12 @@ feats = [f.to(dev) for f in b["image_features"]]
 if args.do_sample:
     kw = dict(num_beams=args.beams, do_sample=True, top_p=args.top_p, top_k=args.top_k, temperature=args.temperature,
               num_return_sequences=args.num_gen, max_length=args.max_length)
+    if args.logprobs:
+        kw["return_logprobs"] = True
     paths = ["host"] if args.host_sampling else (["device"] if args.no_host else ["device", "host"])
     tot = {p: 0.0 for p in paths}
     steps = {p: 0 for p in paths}
+    rep_ms = {p: [] for p in paths}
     for rep in range(args.reps + 1):          # rep 0 warms both paths up
         for p in paths:
             model._device_sampling = p == "device"
@@ -55,14 +61,19 @@ if args.do_sample:
             t0 = time.perf_counter()
             out = model.generate(input_ids=ids, image_features=feats, attention_mask=am, **kw)
             torch.cuda.synchronize()
+            if args.logprobs:
+                out = out[0]
             if rep:
-                tot[p] += time.perf_counter() - t0
+                dt = time.perf_counter() - t0
+                tot[p] += dt
+                rep_ms[p].append(round(dt * 1e3, 2))
                 steps[p] += out.shape[1] - 1
     for p in paths:
         dt = tot[p] / args.reps
         print(json.dumps({"metric": "sampled_generate_ms", "path": p, "value": round(dt * 1e3, 2), "unit": "ms/generate",
                           "ms_per_decode_step": round(tot[p] / max(steps[p], 1) * 1e3, 3),
-                          "sequences_per_sec": round(args.batch * args.num_gen / dt, 1),
+                          "sequences_per_sec": round(args.batch * args.num_gen / dt, 1), "rep_ms": rep_ms[p],
+                          "logprobs": bool(args.logprobs),
                           "config": {"workload": "vcg_base generate, sampling", "batch": args.batch, "num_gen": args.num_gen,
                                      "rows": args.batch * args.num_gen, "top_k": args.top_k, "top_p": args.top_p,
                                      "temperature": args.temperature, "max_length": args.max_length,
