@@ -100,6 +100,10 @@ typedef struct KmbAttn {
    * All three pointers or none (a partial set is refused), and ld_colsum >= 64 H when they are given; the three may share one
    * buffer (training: parts, parts + d, parts + 2 d with ld_colsum = 3 d).  Columns that no head owns are not written. */
   float* dq_colsum; float* dk_colsum; float* dv_colsum; int32_t ld_colsum;
+  /* attention dropout (training kernels only; all zero = none): probability element (b, h, q, k) is kept when
+   * kmb_op_dropout_mask(drop_seed, thr16 / 65536, B * H * Tq, Tk) keeps element (row (b * H + h) * Tq + q, column k); kept ones are multiplied by
+   * drop_scale = 1 / (1 - thr16 / 65536) on their way into P V.  lse stays the undropped softmax's.  Backward must be given the forward's values. */
+  uint32_t drop_thr16, drop_seed; float drop_scale;
 } KmbAttn;
 
 typedef struct KmbAttnDecode {
@@ -176,6 +180,15 @@ int kmb_bind_workspace(kmb_handle* h, void* ws, int64_t bytes);
 /* refresh the bf16 mirror from the fp32 master parameters (after init / load_state_dict) */
 int kmb_sync_params(kmb_handle* h, void* stream);
 int kmb_set_seed(kmb_handle* h, uint64_t seed);
+/* Attention dropout (the reference's config.attention_dropout: F.dropout on the softmax weights of every attention block).  A run-time
+ * setting of the handle -- kmb_create refuses a non-zero kmb_config.attention_dropout -- that takes effect from the next forward; p in [0, 1).
+ * Only training-mode forwards (train = 1) and their backward draw masks: eval forwards, kmb_score, generation and the fp32 validation mode
+ * run without.  kmb_attention_dropout_site reports what the LAST training forward used at a site (kind 0 encoder self-attention, 1 decoder
+ * self-attention, 2 decoder cross-attention; zeros when it ran without): probability (b, h, q, k) was kept where
+ * kmb_op_dropout_mask(seed, thr16 / 65536, B * H * Tq, Tk) keeps element ((b * H + h) * Tq + q, k). */
+int kmb_set_attention_dropout(kmb_handle* h, float p);
+int kmb_attention_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed);
+int kmb_abi_sizeof_attn(void);   /* sizeof(KmbAttn) as the library was compiled: a binding checks its own layout against it */
 
 /* gradient buckets for data-parallel overlap (DDP reducer, vcg_train.py:98): bucket i is complete
  * on the compute stream once kmb_backward has passed its event */

@@ -3,7 +3,8 @@
 // Semantics (transformers 3.0.2 SelfAttention as used by the reference, src/model/modules.py:84,
 // src/model/model.py:35): q already carries the head_dim**-0.5 scale (applied by the projection
 // epilogue), scores get -inf at padded keys (key_mask == 0) and above the diagonal (causal),
-// softmax in fp32, attention_dropout = 0.
+// softmax in fp32; attention_dropout (F.dropout on the softmax weights) through the DROP instantiations of the four training kernels, picked when
+// KmbAttn.drop_thr16 != 0 ("attention dropout" below); the decode kernel and the fp32 validation forward run without it.
 //
 // Forward : grid (B*H, ceil(Tq/64)), 4 waves, wave w owns 16 query rows; K/V tiles of 64 keys are
 //           staged once per workgroup in LDS; online softmax over key tiles.
@@ -87,7 +88,20 @@ __device__ __forceinline__ float group16_sum(float v) {
   return v;
 }
 
+// ---- attention dropout (the DROP instantiations; DROP = false is the code without it, instruction for instruction) ----
+// keep(b, h, q, k) = drop_keep(drop_seed, row = (b * H + h) * Tq + q, col = k, drop_thr16) on LOGICAL coordinates: the real head and the positions inside
+// it, so that no tile layout (PACK: two heads per tile) changes the mask and kmb_op_dropout_mask(seed, p, B * H * Tq, Tk) returns it.  The pieces of
+// drop_keep's one hash: rowterm = row * DROP_ROW_MUL (the next query row adds the constant: no multiply per element), colseed = drop_colterm(k) ^ seed.
+// Forward: P~ = keep ? P * scale : 0 goes into P V only -- the maximum, the row sum and the log-sum-exp are the undropped softmax's.
+// Backward: dP~ = keep ? dP * scale : 0, delta = sum_k P dP~, dS = P (dP~ - delta); the image behind dV holds P~.
+constexpr uint32_t DROP_ROW_MUL = 0x9E3779B1u;
+__device__ __forceinline__ bool attn_keep(uint32_t rowterm, uint32_t colseed, uint32_t odd, uint32_t thr16) {
+  const uint32_t h = kmb_hash32(rowterm ^ colseed);
+  return (odd ? (h >> 16) : (h & 0xffffu)) >= thr16;
+}
+
 // ------------------------------------------------------------------ forward
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const KmbAttn p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * TILE_BYTES + 4 * 2048];
   char* Ks = smem;
@@ -159,6 +173,16 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const KmbAttn p) {
       m_run[q] = m_new;
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j][q] *= alpha;
+    }
+    if constexpr (DROP) {   // behind the row sums: only the probabilities that go into P V are dropped
+      const uint32_t rt0 = (((uint32_t)b * (uint32_t)p.H + (uint32_t)h) * (uint32_t)p.Tq + (uint32_t)(q0 + g * 4)) * DROP_ROW_MUL;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t cs = drop_colterm((uint32_t)(kt * 64 + j * 16 + r)) ^ p.drop_seed;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          s[j][q] = attn_keep(rt0 + (uint32_t)q * DROP_ROW_MUL, cs, r & 1, p.drop_thr16) ? s[j][q] * p.drop_scale : 0.f;
+      }
     }
     // P (C layout) -> LDS -> A layout
 #pragma unroll
@@ -235,7 +259,7 @@ __device__ __forceinline__ void fwd_load_item(const KmbAttn& p, int item, int ti
   }
 }
 
-template <bool PACK>
+template <bool PACK, bool DROP>
 __global__ __launch_bounds__(256, 4) void attn_fwd_small_kernel(const KmbAttn p) {
   __shared__ __attribute__((aligned(16))) char smem[3 * TILE_BYTES + 4 * 2048];
   __shared__ float msk_s[64];   // key-mask flags of the tile's 64 keys
@@ -315,6 +339,19 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_small_kernel(const KmbAttn p)
       l_run[q] = lsum;
       m_run[q] = mx;
     }
+    if constexpr (DROP) {   // this lane's four query rows are consecutive positions of ONE head (PACK: the tile's second head from row 32 on)
+      const int qt = q0 + g * 4;
+      const uint32_t hq = (uint32_t)(PACK ? h + (qt >> 5) : h), ql = (uint32_t)(PACK ? (qt & 31) : qt);
+      const uint32_t rt0 = (((uint32_t)b * (uint32_t)p.H + hq) * (uint32_t)p.Tq + ql) * DROP_ROW_MUL;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int key = j * 16 + r;
+        const uint32_t cs = drop_colterm((uint32_t)(PACK ? (key & 31) : key)) ^ p.drop_seed;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          s[j][q] = attn_keep(rt0 + (uint32_t)q * DROP_ROW_MUL, cs, r & 1, p.drop_thr16) ? s[j][q] * p.drop_scale : 0.f;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -375,6 +412,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_small_kernel(const KmbAttn p)
 }
 
 // ----------------------------------------------------------------- backward
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Qs = smem;
@@ -398,8 +436,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
   const int nkt = (p.Tk + 63) / 64;
   float* delta_all = dQacc + (size_t)nqt * 64 * 64;   // [nqt*64] the softmax backward's correction term of every query row
   // S = Q K^T, dP = dO V^T and P = exp(S - lse) (0 where masked) of this wave's 16 query rows x the tile's 64 keys, from the staged images;
-  // P replaces S in `s`.  Both passes below go through it: the same bits.
-  auto probs = [&](int kt, int qt, f32x4 (&s)[4], f32x4 (&dp)[4]) {
+  // P replaces S in `s`.  Both passes below go through it: the same bits.  DROP: dp comes back as dP~ (dropped and scaled), and bit 4 j + q of
+  // `kbits` says whether element [j][q] was kept (the second pass builds P~ for dV from it).
+  auto probs = [&](int kt, int qt, f32x4 (&s)[4], f32x4 (&dp)[4], [[maybe_unused]] uint32_t& kbits) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
@@ -426,6 +465,20 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
         s[j][q] = (ok && lse != -INFINITY) ? __expf(s[j][q] - lse) : 0.f;
       }
     }
+    if constexpr (DROP) {
+      const uint32_t rt0 = (((uint32_t)b * (uint32_t)p.H + (uint32_t)h) * (uint32_t)p.Tq + (uint32_t)(qt * 64 + wave * 16 + g * 4)) * DROP_ROW_MUL;
+      kbits = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t cs = drop_colterm((uint32_t)(kt * 64 + j * 16 + r)) ^ p.drop_seed;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bool keep = attn_keep(rt0 + (uint32_t)q * DROP_ROW_MUL, cs, r & 1, p.drop_thr16);
+          dp[j][q] = keep ? dp[j][q] * p.drop_scale : 0.f;
+          kbits |= keep ? (1u << (j * 4 + q)) : 0u;
+        }
+      }
+    }
   };
   auto stage_lse = [&](int qt) {   // the tile's 64 log-sum-exps (rows past Tq: the last row's, masked later)
     if (tid < 64) {
@@ -448,7 +501,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
       stage_tile(Vs, Vh, (size_t)b * p.Tk, kt * 64, p.Tk, p.ldv, tid);
       __syncthreads();
       f32x4 s[4], dp[4];
-      probs(kt, qt, s, dp);
+      [[maybe_unused]] uint32_t kbits;
+      probs(kt, qt, s, dp, kbits);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -477,13 +531,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const KmbAttn p, int nqt)
       stage_lse(qt);
       __syncthreads();
       f32x4 s[4], dp[4];
-      probs(kt, qt, s, dp);
+      [[maybe_unused]] uint32_t kbits;
+      probs(kt, qt, s, dp, kbits);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int lrow = wave * 16 + g * 4 + q;
           const float ds = s[j][q] * (dp[j][q] - delta_all[qt * 64 + lrow]);
+          if constexpr (DROP) s[j][q] = ((kbits >> (j * 4 + q)) & 1u) ? s[j][q] * p.drop_scale : 0.f;   // P~: what the forward multiplied V by
           *reinterpret_cast<bf16_t*>(Ps + elem_off(lrow, j * 16 + r)) = f2bf(s[j][q]);
           *reinterpret_cast<bf16_t*>(dSs + elem_off(lrow, j * 16 + r)) = f2bf(ds);
         }
@@ -619,7 +675,7 @@ __device__ __forceinline__ void bwd_load_item(const KmbAttn& p, int item, int ti
   }
 }
 
-template <bool PACK>
+template <bool PACK, bool DROP>
 __global__ __launch_bounds__(256, 3) void attn_bwd_small_kernel(const KmbAttn p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Qs = smem;
@@ -721,11 +777,20 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_small_kernel(const KmbAttn p)
     // delta[q] = sum over the keys of P[q][k] * dP[q][k] (= rowsum(dO * O), the softmax backward's correction term) from the probabilities
     // and dP this wave holds in registers -- the saved output O is not read at all (an eighth of an item's bytes, two of its sixteen loads)
     float del4[4] = {0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] uint32_t kbits = 0u;   // DROP: bit 4 j + q = element [j][q] was kept
+    [[maybe_unused]] uint32_t rt0 = 0u;
+    if constexpr (DROP) {   // this lane's four query rows are consecutive positions of ONE head (PACK: the tile's second head from row 32 on)
+      const int qt = wave * 16 + g * 4;
+      const uint32_t hq = (uint32_t)(PACK ? h + (qt >> 5) : h), ql = (uint32_t)(PACK ? (qt & 31) : qt);
+      rt0 = (((uint32_t)b * (uint32_t)p.H + hq) * (uint32_t)p.Tq + ql) * DROP_ROW_MUL;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int key = j * 16 + r;
       const int keyl = PACK ? (key & 31) : key;                 // the key's position inside its head
       const bool kv = keyl < p.Tk && key_on[j];
+      [[maybe_unused]] uint32_t cs = 0u;
+      if constexpr (DROP) cs = drop_colterm((uint32_t)keyl) ^ p.drop_seed;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int lrow = wave * 16 + g * 4 + q;
@@ -733,6 +798,11 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_small_kernel(const KmbAttn p)
         const bool ok = kv && rowl < p.Tq && (!p.causal || keyl <= rowl) && (!PACK || (key >> 5) == (lrow >> 5));   // PACK: a query only sees its own head's keys
         const float pvq = (ok && lse4[q] != -INFINITY) ? __expf(s4[j][q] - lse4[q]) : 0.f;
         s4[j][q] = pvq;
+        if constexpr (DROP) {   // dP~
+          const bool keep = attn_keep(rt0 + (uint32_t)q * DROP_ROW_MUL, cs, r & 1, p.drop_thr16);
+          dp[j][q] = keep ? dp[j][q] * p.drop_scale : 0.f;
+          kbits |= keep ? (1u << (j * 4 + q)) : 0u;
+        }
         del4[q] += pvq * dp[j][q];
       }
     }
@@ -751,6 +821,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_small_kernel(const KmbAttn p)
       float ds[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) ds[q] = s4[j][q] * (dp[j][q] - del4[q]);
+      if constexpr (DROP) {   // P~ for dV: what the forward multiplied V by
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s4[j][q] = ((kbits >> (j * 4 + q)) & 1u) ? s4[j][q] * p.drop_scale : 0.f;
+      }
       const int off = elem_off(key, wave * 16 + g * 4);
       *reinterpret_cast<uint2*>(Ps + off) = uint2{pack2bf(s4[j][0], s4[j][1]), pack2bf(s4[j][2], s4[j][3])};
       *reinterpret_cast<uint2*>(dSs + off) = uint2{pack2bf(ds[0], ds[1]), pack2bf(ds[2], ds[3])};
@@ -931,10 +1005,16 @@ const char* kmb_attn_check(const KmbAttn& p, int backward) {
     if (ncs == 3 && p.ld_colsum < p.H * HD) return "attention backward: ld_colsum must be at least H * 64";
     if (p.Tq > 384) return "attention backward: Tq > 384 is not supported (dQ accumulator lives in LDS)";
   }
+  // the dropout mask's row index (b * H + h) * Tq + q is 32 bits wide (kmb_op_dropout_mask takes int rows)
+  if ((uint64_t)p.B * (uint64_t)p.H * (uint64_t)p.Tq > 0xffffffffull) return "attention: B * H * Tq does not fit in 32 bits";
+  if (p.drop_thr16 > 65535u) return "attention: drop_thr16 must be at most 65535";
+  if (p.drop_thr16 != 0u && !(p.drop_scale > 0.f && p.drop_scale <= 3.4028234e38f))
+    return "attention: drop_scale must be finite and positive when drop_thr16 != 0";
   return nullptr;
 }
 
 hipError_t kmb_attn_fwd_launch(const KmbAttn& p, hipStream_t stream) {
+  const bool drop = p.drop_thr16 != 0u;   // attention dropout: the DROP instantiations
   static const bool small_ok = !(KMB_DIAG_ENV("KMB_ATTN_FWD_SMALL") && KMB_DIAG_ENV("KMB_ATTN_FWD_SMALL")[0] == '0');
   // (the single-tile kernel's 32-bit byte offsets: every tensor below 4 GB)
   int ld_max = p.ldq;
@@ -944,16 +1024,24 @@ hipError_t kmb_attn_fwd_launch(const KmbAttn& p, hipStream_t stream) {
     static const bool pack_ok = !(KMB_DIAG_ENV("KMB_ATTN_PACK") && KMB_DIAG_ENV("KMB_ATTN_PACK")[0] == '0');
     const bool pack = pack_ok && p.Tq <= 32 && p.Tk <= 32 && (p.H & 1) == 0;   // two heads per tile (32-token self-attention)
     const int items = pack ? p.B * (p.H >> 1) : p.B * p.H;
-    if (pack) hipLaunchKernelGGL(attn_fwd_small_kernel<true>, dim3(items < 1024 ? items : 1024), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(attn_fwd_small_kernel<false>, dim3(items < 1024 ? items : 1024), dim3(256), 0, stream, p);   // four workgroups per CU
+    const dim3 grid(items < 1024 ? items : 1024);   // four workgroups per CU
+    if (drop) {
+      if (pack) hipLaunchKernelGGL((attn_fwd_small_kernel<true, true>), grid, dim3(256), 0, stream, p);
+      else hipLaunchKernelGGL((attn_fwd_small_kernel<false, true>), grid, dim3(256), 0, stream, p);
+    } else {
+      if (pack) hipLaunchKernelGGL((attn_fwd_small_kernel<true, false>), grid, dim3(256), 0, stream, p);
+      else hipLaunchKernelGGL((attn_fwd_small_kernel<false, false>), grid, dim3(256), 0, stream, p);
+    }
     return hipGetLastError();
   }
   dim3 grid(p.B * p.H, (p.Tq + 63) / 64), block(256);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0, stream, p);
+  if (drop) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, block, 0, stream, p);
+  else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, block, 0, stream, p);
   return hipGetLastError();
 }
 
 hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream) {
+  const bool drop = p.drop_thr16 != 0u;   // attention dropout: the DROP instantiations
   const int nqt = (p.Tq + 63) / 64;
   static const bool small_ok = !(KMB_DIAG_ENV("KMB_ATTN_BWD_SMALL") && KMB_DIAG_ENV("KMB_ATTN_BWD_SMALL")[0] == '0');
   // (its 32-bit byte offsets: every tensor below 4 GB)
@@ -965,8 +1053,10 @@ hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream) {
     const size_t lds_s = 6 * TILE_BYTES + (128 + 768) * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_small_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_small_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
+      hipError_t e = hipSuccess;
+      for (const void* f : {(const void*)attn_bwd_small_kernel<false, false>, (const void*)attn_bwd_small_kernel<true, false>,
+                            (const void*)attn_bwd_small_kernel<false, true>, (const void*)attn_bwd_small_kernel<true, true>})
+        if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
       if (e != hipSuccess) return e;
       attr_set = true;
     }
@@ -975,18 +1065,25 @@ hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream) {
     const bool pack = pack_ok && p.Tq <= 32 && p.Tk <= 32 && (p.H & 1) == 0;
     const int items = pack ? p.B * (p.H >> 1) : p.B * p.H;
     const int grid = items < 768 ? items : 768;   // three workgroups per CU (165 VGPRs, 52.6 KB of LDS each)
-    if (pack) hipLaunchKernelGGL(attn_bwd_small_kernel<true>, dim3(grid), dim3(256), lds_s, stream, p);
-    else hipLaunchKernelGGL(attn_bwd_small_kernel<false>, dim3(grid), dim3(256), lds_s, stream, p);
+    if (drop) {
+      if (pack) hipLaunchKernelGGL((attn_bwd_small_kernel<true, true>), dim3(grid), dim3(256), lds_s, stream, p);
+      else hipLaunchKernelGGL((attn_bwd_small_kernel<false, true>), dim3(grid), dim3(256), lds_s, stream, p);
+    } else {
+      if (pack) hipLaunchKernelGGL((attn_bwd_small_kernel<true, false>), dim3(grid), dim3(256), lds_s, stream, p);
+      else hipLaunchKernelGGL((attn_bwd_small_kernel<false, false>), dim3(grid), dim3(256), lds_s, stream, p);
+    }
     return hipGetLastError();
   }
   const size_t lds = 6 * TILE_BYTES + (128 + 512) * sizeof(float) + (size_t)nqt * 64 * (64 + 1) * sizeof(float);   // ... dQ accumulator, delta
-  static size_t lds_set = 0;
-  if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static size_t lds_set[2] = {0, 0};   // per instantiation
+  if (lds > lds_set[drop]) {
+    hipError_t e = hipFuncSetAttribute(drop ? (const void*)attn_bwd_kernel<true> : (const void*)attn_bwd_kernel<false>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    lds_set = lds;
+    lds_set[drop] = lds;
   }
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3(p.B * p.H), dim3(256), lds, stream, p, nqt);
+  if (drop) hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(p.B * p.H), dim3(256), lds, stream, p, nqt);
+  else hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(p.B * p.H), dim3(256), lds, stream, p, nqt);
   return hipGetLastError();
 }
 

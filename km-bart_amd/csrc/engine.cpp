@@ -208,6 +208,27 @@ struct kmb_handle {
     dr.scale = 1.f / (1.f - (float)thr / 65536.f);
     return dr;
   }
+  // Attention dropout (F.dropout on the softmax weights, HF 3.0.2 SelfAttention): a run-time setting of the handle (kmb_set_attention_dropout), NOT
+  // cfg.attention_dropout, which kmb_create keeps refusing.  Its sites draw their seeds like drop_site but from numbers of their own --
+  // ATTN_SITE_BASE + 3 * layer + kind (0 encoder self, 1 decoder self, 2 decoder cross), far above every drop_site number (1, 2, 10 + 2 l, 11 + 2 l,
+  // 100 + 3 l .. 102 + 3 l) and below the next step's (a step advances the mixed word by 0x10001) -- so no existing mask moves.
+  // attn_used[kind][layer]: what the LAST training forward launched with (zeros: none); backward reads it back instead of drawing again.
+  static constexpr uint64_t ATTN_SITE_BASE = 0x40000000ull;
+  float attn_p = 0.f;
+  std::vector<KmbDrop> attn_used[3];
+  KmbDrop attn_drop_site(int kind, int layer, bool train) {
+    KmbDrop dr{0u, 0u, 1.f};
+    if (!train || attn_p <= 0.f) return dr;
+    uint32_t thr = (uint32_t)lrintf(attn_p * 65536.f);
+    if (thr > 65535u) thr = 65535u;
+    if (thr == 0u) return dr;
+    dr.thr16 = thr;
+    dr.seed = (uint32_t)splitmix(seed ^ splitmix(step * 0x10001ull + ATTN_SITE_BASE + (uint64_t)(3 * layer + kind)));
+    dr.scale = 1.f / (1.f - (float)thr / 65536.f);
+    attn_used[kind][layer] = dr;
+    return dr;
+  }
+  KmbDrop attn_drop_used(int kind, int layer, bool train) const { return train ? attn_used[kind][layer] : KmbDrop{0u, 0u, 1.f}; }
   bf16_t* wb(size_t off) const { return g_f32 ? reinterpret_cast<bf16_t*>(P + off) : PB + off; }   // GEMM B operand: bf16 mirror (fp32 master in validation mode)
   float* pf(size_t off) const { return P + off; }
   float* gf(size_t off) const { return G + off; }
@@ -731,8 +752,10 @@ int check_bound(const kmb_handle* h) {
 // ------------------------------------------------------------------ shared sub-graphs
 struct AttnIO { const bf16_t* q; int ldq; const bf16_t* k; const bf16_t* v; int ldkv; int Tq, Tk; const int64_t* mask; int causal; };
 
-int attn_forward(kmb_handle* h, const AttnIO& io, int B, int H, bf16_t* o, float* lse, hipStream_t s) {
+int attn_forward(kmb_handle* h, const AttnIO& io, int B, int H, bf16_t* o, float* lse, KmbDrop adr, hipStream_t s) {
   KmbAttn a; memset(&a, 0, sizeof(a));
+  if (g_f32 && adr.thr16) return fail("fp32 validation mode runs without dropout");
+  if (adr.thr16) { a.drop_thr16 = adr.thr16; a.drop_seed = adr.seed; a.drop_scale = adr.scale; }
   a.Q = io.q; a.K = io.k; a.V = io.v; a.ldq = io.ldq; a.ldk = io.ldkv; a.ldv = io.ldkv;
   a.B = B; a.H = H; a.Tq = io.Tq; a.Tk = io.Tk; a.key_mask = io.mask; a.causal = io.causal;
   a.O = o; a.ldo = h->d; a.lse = lse;
@@ -766,8 +789,9 @@ int embed_ln_forward(const int64_t* ids, const int32_t* img_src, const float* E,
 
 int attn_backward(kmb_handle* h, const AttnIO& io, int B, int H, bf16_t* o, float* lse, const bf16_t* dO, bf16_t* dq,
                   int lddq, bf16_t* dk, bf16_t* dv, int lddkv, float* cs_q, float* cs_k, float* cs_v, int ld_cs,
-                  hipStream_t s) {
+                  KmbDrop adr, hipStream_t s) {
   KmbAttn a; memset(&a, 0, sizeof(a));
+  if (adr.thr16) { a.drop_thr16 = adr.thr16; a.drop_seed = adr.seed; a.drop_scale = adr.scale; }   // the forward's mask
   a.Q = io.q; a.K = io.k; a.V = io.v; a.ldq = io.ldq; a.ldk = io.ldkv; a.ldv = io.ldkv;
   a.B = B; a.H = H; a.Tq = io.Tq; a.Tk = io.Tk; a.key_mask = io.mask; a.causal = io.causal;
   a.O = o; a.ldo = h->d; a.lse = lse; a.dO = dO; a.lddo = h->d;
@@ -822,13 +846,13 @@ int ffn_backward(kmb_handle* h, const LayerP& L, int F, const bf16_t* x, const b
 // self-attention block forward: z = x + drop(out_proj(attn(qkv(x)))) ; out = LN(z)
 int self_attn_forward(kmb_handle* h, const AttnP& A, int H, const bf16_t* x, bf16_t* qkv, bf16_t* o, float* lse,
                       bf16_t* z, float* mean, float* rstd, bf16_t* out, int B, int T, const int64_t* mask, int causal,
-                      KmbDrop dr, hipStream_t s) {
+                      KmbDrop dr, KmbDrop adr, hipStream_t s) {
   const int d = h->d, M = B * T;
   KmbGemm g = lin_fwd(x, d, h->wb(A.qkv_w), h->pf(A.qkv_b), M, 3 * d, d);
   g.col_scale = 0.125f; g.col_scale_n = d; g.out_bf16 = qkv; g.ld_out_bf16 = 3 * d;
   KCHK(run_gemm(g, s));
   AttnIO io{qkv, 3 * d, EP(qkv, d), EP(qkv, 2 * d), 3 * d, T, T, mask, causal};
-  KCHK(attn_forward(h, io, B, H, o, lse, s));
+  KCHK(attn_forward(h, io, B, H, o, lse, adr, s));
   g = lin_fwd(o, d, h->wb(A.o_w), h->pf(A.o_b), M, d, d);
   g.drop_thr16 = dr.thr16; g.drop_seed = dr.seed; g.drop_scale = dr.scale;
   g.residual = x; g.ld_res = d; g.out_bf16 = z; g.ld_out_bf16 = d;
@@ -839,7 +863,7 @@ int self_attn_forward(kmb_handle* h, const AttnP& A, int H, const bf16_t* x, bf1
 
 int self_attn_backward(kmb_handle* h, const AttnP& A, int H, const bf16_t* x, bf16_t* qkv, bf16_t* o, float* lse,
                        const bf16_t* z, const float* mean, const float* rstd, const bf16_t* dy, bf16_t* dx_out, int B,
-                       int T, const int64_t* mask, int causal, KmbDrop dr, kmb_handle::BwdBufs& bb, hipStream_t s) {
+                       int T, const int64_t* mask, int causal, KmbDrop dr, KmbDrop adr, kmb_handle::BwdBufs& bb, hipStream_t s) {
   const int d = h->d, M = B * T;
   bf16_t* dz = bb.dz[1];
   bf16_t* dsub = dr.thr16 ? bb.dsub[1] : dz;
@@ -855,7 +879,7 @@ int self_attn_backward(kmb_handle* h, const AttnP& A, int H, const bf16_t* x, bf
   KCHK(trace("sa.qkv(saved)", qkv, (size_t)M * 3 * d * 2, s));
   AttnIO io{qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, T, T, mask, causal};
   KCHK(attn_backward(h, io, B, H, o, lse, h->dob, bb.dqkv, 3 * d, bb.dqkv + d, bb.dqkv + 2 * d, 3 * d, bb.parts[3],
-                     bb.parts[3] + d, bb.parts[3] + 2 * d, 3 * d, s));
+                     bb.parts[3] + d, bb.parts[3] + 2 * d, 3 * d, adr, s));
   HIPCHK(kmb_reduce_parts_launch(bb.parts[3], B, 3 * d, h->gf(A.qkv_b), 3 * d, reducer_stream(h, s)));
   KCHK(trace("sa.dqkv", bb.dqkv, (size_t)M * 3 * d * 2, s));
   KCHK(wgrad_side(h, lin_wgrad(bb.dqkv, 3 * d, x, d, h->gf(A.qkv_w), M, 3 * d, d, 0.f), s));
@@ -941,7 +965,7 @@ int encoder_forward(kmb_handle* h, const kmb_batch& bt, bool train, hipStream_t 
     const LayerP& L = h->enc[l];
     EncAct& a = h->ea[l];
     KCHK(self_attn_forward(h, L.sa, h->He, h->xe[l], a.qkv, a.o, a.lse, a.z1, a.m1, a.r1, a.y1, B, S,
-                           bt.attention_mask, 0, h->drop_site(10 + 2 * l, train), s));
+                           bt.attention_mask, 0, h->drop_site(10 + 2 * l, train), h->attn_drop_site(0, l, train), s));
     KCHK(ffn_forward(h, L, h->Fe, a.y1, a.u, a.hh, a.z2, a.m2, a.r2, h->xe[l + 1], Me, h->drop_site(11 + 2 * l, train), s));
   }
   return 0;
@@ -981,6 +1005,9 @@ int kmb_create(const kmb_config* cfg, kmb_handle** out) {
   h->enc_lne_g = add_param(h, "model.encoder.layernorm_embedding.weight", 1, d);
   h->enc_lne_b = add_param(h, "model.encoder.layernorm_embedding.bias", 1, d);
   std::vector<size_t> marks;  // bucket boundaries in arena order
+  h->attn_used[0].assign(cfg->encoder_layers, KmbDrop{0u, 0u, 1.f});
+  h->attn_used[1].assign(cfg->decoder_layers, KmbDrop{0u, 0u, 1.f});
+  h->attn_used[2].assign(cfg->decoder_layers, KmbDrop{0u, 0u, 1.f});
   h->enc.resize(cfg->encoder_layers);
   for (int l = 0; l < cfg->encoder_layers; ++l) {
     marks.push_back(align_up(h->arena, 64));
@@ -1109,6 +1136,24 @@ int kmb_bind_workspace(kmb_handle* h, void* ws, int64_t bytes) {
 
 int kmb_set_seed(kmb_handle* h, uint64_t seed) { h->seed = seed; h->step = 0; return 0; }
 
+int kmb_set_attention_dropout(kmb_handle* h, float p) {
+  if (!h) return fail("kmb_set_attention_dropout: null handle");
+  if (!(p >= 0.f && p < 1.f)) return fail("kmb_set_attention_dropout: the probability must be in [0, 1), got %g", (double)p);   // (NaN fails both)
+  h->attn_p = p;
+  return 0;
+}
+
+int kmb_attention_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed) {
+  if (!h || !thr16 || !seed) return fail("kmb_attention_dropout_site: null argument");
+  if (kind < 0 || kind > 2) return fail("kmb_attention_dropout_site: kind must be 0 (encoder self), 1 (decoder self) or 2 (decoder cross)");
+  if (layer < 0 || layer >= (int)h->attn_used[kind].size()) return fail("kmb_attention_dropout_site: no layer %d", layer);
+  const KmbDrop& dr = h->attn_used[kind][layer];
+  *thr16 = dr.thr16; *seed = dr.thr16 ? dr.seed : 0u;
+  return 0;
+}
+
+int kmb_abi_sizeof_attn(void) { return (int)sizeof(KmbAttn); }
+
 int kmb_sync_params(kmb_handle* h, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!h->P || !h->PB) return fail("kmb_sync_params: arenas are not bound");
@@ -1203,7 +1248,10 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
   h->bt = bt; h->Me = Me; h->Md = Md; h->Ntot = bt.n_features;
   h->fwd_train = train != 0; h->have_fwd = false; h->have_hdec = false; h->have_bwd = false;
   h->enc_given = enc_in != nullptr;
-  if (train) h->step += 1;
+  if (train) {
+    h->step += 1;
+    for (auto& v : h->attn_used) std::fill(v.begin(), v.end(), KmbDrop{0u, 0u, 1.f});   // what THIS training forward uses is recorded as it goes
+  }
   const bool tr = train != 0;
   const float eps = h->cfg.layer_norm_eps;
   const float scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f;
@@ -1230,13 +1278,13 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
     const LayerP& L = h->dec[l];
     DecAct& a = h->da[l];
     KCHK(self_attn_forward(h, L.sa, h->Hd, h->xd[l], a.qkv, a.o1, a.lse1, a.z1, a.m1, a.r1, a.y1, B, T,
-                           bt.decoder_attention_mask, 1, h->drop_site(100 + 3 * l, tr), s));
+                           bt.decoder_attention_mask, 1, h->drop_site(100 + 3 * l, tr), h->attn_drop_site(1, l, tr), s));
     // cross attention: q from decoder states (scaled), k|v from the encoder output
     KmbGemm g = lin_fwd(a.y1, d, h->wb(L.ca.qkv_w), h->pf(L.ca.qkv_b), Md, d, d);
     g.col_scale = 0.125f; g.col_scale_n = d; g.out_bf16 = a.cq; g.ld_out_bf16 = d;
     KCHK(run_gemm(g, s));
     AttnIO io{a.cq, d, a.ckv, EP(a.ckv, d), ldkv, T, S, bt.attention_mask, 0};
-    KCHK(attn_forward(h, io, B, h->Hd, a.o2, a.lse2, s));
+    KCHK(attn_forward(h, io, B, h->Hd, a.o2, a.lse2, h->attn_drop_site(2, l, tr), s));
     const KmbDrop dr = h->drop_site(101 + 3 * l, tr);
     g = lin_fwd(a.o2, d, h->wb(L.ca.o_w), h->pf(L.ca.o_b), Md, d, d);
     g.drop_thr16 = dr.thr16; g.drop_seed = dr.seed; g.drop_scale = dr.scale;
@@ -1676,7 +1724,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
       bf16_t* dkv = h->dckv_all + (size_t)l * 2 * d;   // this layer's columns of the batched k | v gradient
       AttnIO io{a.cq, d, a.ckv, a.ckv + d, ldkv, T, S, bt.attention_mask, 0};
       KCHK(attn_backward(h, io, B, h->Hd, a.o2, a.lse2, h->dob, bb.dcq, d, dkv, dkv + d, ldkv, bb.parts[5],
-                         bb.parts[5] + d, bb.parts[5] + 2 * d, 3 * d, s));
+                         bb.parts[5] + d, bb.parts[5] + 2 * d, 3 * d, h->attn_drop_used(2, l, tr), s));
       // bias gradients from the attention kernel's per-batch-item column sums [B][q | k | v]: q's bias lives in the layer,
       // the k | v biases of all layers together (kmb_handle::xkv_b)
       HIPCHK(kmb_reduce_parts2_launch(bb.parts[5], B, 3 * d, h->gf(L.ca.qkv_b), d, h->gf(L.ca_kv_b), 2 * d, reducer_stream(h, s)));
@@ -1689,7 +1737,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
       KCHK(trace("ca.t1", t1, (size_t)Md * d * 2, s));
     }
     KCHK(self_attn_backward(h, L.sa, h->Hd, h->xd[l], a.qkv, a.o1, a.lse1, a.z1, a.m1, a.r1, t1, t0, B, T,
-                            bt.decoder_attention_mask, 1, h->drop_site(100 + 3 * l, tr), bb, s));
+                            bt.decoder_attention_mask, 1, h->drop_site(100 + 3 * l, tr), h->attn_drop_used(1, l, tr), bb, s));
     dy = t0;  // t0 now holds d(loss)/d(xd[l]); keep it as the input of the next iteration
     cur ^= 1;  // next iteration writes its first result into the other buffer
     KCHK(layer_end(c, ev++));
@@ -1758,7 +1806,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
     bf16_t* t0 = pp[cur]; bf16_t* t1 = pp[cur ^ 1];
     KCHK(ffn_backward(h, L, h->Fe, a.y1, a.u, a.hh, a.z2, a.m2, a.r2, dy, t0, Me, h->drop_site(11 + 2 * l, tr), bb, s));
     KCHK(self_attn_backward(h, L.sa, h->He, h->xe[l], a.qkv, a.o, a.lse, a.z1, a.m1, a.r1, t0, t1, B, S,
-                            bt.attention_mask, 0, h->drop_site(10 + 2 * l, tr), bb, s));
+                            bt.attention_mask, 0, h->drop_site(10 + 2 * l, tr), h->attn_drop_used(0, l, tr), bb, s));
     dy = t1;  // t0 / t1 keep their roles: the next ffn_backward reads t1 and writes t0
     KCHK(layer_end(c, ev++));
   }

@@ -56,7 +56,8 @@ class KmbAttn(C.Structure):
                 ("B", i32), ("H", i32), ("Tq", i32), ("Tk", i32), ("key_mask", c_p), ("causal", i32),
                 ("O", c_p), ("ldo", i32), ("lse", c_p), ("dO", c_p), ("lddo", i32),
                 ("dQ", c_p), ("dK", c_p), ("dV", c_p), ("lddq", i32), ("lddk", i32), ("lddv", i32),
-                ("dq_scale", f32), ("dq_colsum", c_p), ("dk_colsum", c_p), ("dv_colsum", c_p), ("ld_colsum", i32)]
+                ("dq_scale", f32), ("dq_colsum", c_p), ("dk_colsum", c_p), ("dv_colsum", c_p), ("ld_colsum", i32),
+                ("drop_thr16", u32), ("drop_seed", u32), ("drop_scale", f32)]
 
 
 class KmbAttnDecode(C.Structure):
@@ -105,6 +106,9 @@ PROTOTYPES = {
     "kmb_bind_workspace": (C.c_int, [c_p, c_p, i64]),
     "kmb_sync_params": (C.c_int, [c_p, c_p]),
     "kmb_set_seed": (C.c_int, [c_p, C.c_uint64]),
+    "kmb_set_attention_dropout": (C.c_int, [c_p, f32]),
+    "kmb_attention_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
+    "kmb_abi_sizeof_attn": (C.c_int, []),
     "kmb_bucket_count": (C.c_int, [c_p]),
     "kmb_bucket_range": (C.c_int, [c_p, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
     "kmb_stream_wait_bucket": (C.c_int, [c_p, C.c_int, c_p]),

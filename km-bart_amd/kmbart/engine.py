@@ -68,7 +68,7 @@ class Engine:
             setattr(c, f, int(getattr(config, f)))
         c.scale_embedding = 1 if getattr(config, "scale_embedding", False) else 0
         c.dropout = float(config.dropout)
-        c.attention_dropout = float(config.attention_dropout)
+        c.attention_dropout = 0.0   # a run-time setting of the handle (set_attention_dropout below); the creation struct refuses it
         c.activation_dropout = float(config.activation_dropout)
         c.layer_norm_eps = 1e-5
         if with_heads:  # MultiModalBartForPreTraining (reference src/model/model.py:133-158)
@@ -81,6 +81,7 @@ class Engine:
         h = C.c_void_p()
         check(self.lib.kmb_create(C.byref(c), C.byref(h)))
         self.h = h
+        self.set_attention_dropout(float(getattr(config, "attention_dropout", 0.0)))
         with torch.cuda.device(self.device):
             n = self.lib.kmb_arena_elems(h)
             nb = self.lib.kmb_bf16_arena_elems(h)
@@ -142,6 +143,19 @@ class Engine:
 
     def set_seed(self, seed):
         check(self.lib.kmb_set_seed(self.h, C.c_uint64(int(seed) & (2 ** 64 - 1))))
+
+    def set_attention_dropout(self, p):
+        """Dropout probability of the attention weights (config.attention_dropout), from the next training-mode forward on;
+        eval forwards, score() and generation never drop."""
+        check(self.lib.kmb_set_attention_dropout(self.h, C.c_float(float(p))))
+        self.attention_dropout = float(p)
+
+    def attention_dropout_site(self, kind, layer):
+        """(thr16, seed) the last training forward used at an attention site (kind 0 encoder self, 1 decoder self, 2 decoder
+        cross); (0, 0) when it ran without dropout.  kmb_op_dropout_mask(seed, thr16 / 65536, B * H * Tq, Tk) rebuilds the mask."""
+        thr, seed = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.kmb_attention_dropout_site(self.h, int(kind), int(layer), C.byref(thr), C.byref(seed)))
+        return int(thr.value), int(seed.value)
 
     # ---- workspace --------------------------------------------------------------------------
     def _ensure_ws(self, nbytes):
