@@ -63,7 +63,13 @@ typedef struct KmbGemm {
   const float* bias;
   float col_scale; int32_t col_scale_n;
   int32_t act;                    /* 0 none, 1 GeLU (erf form), 2 multiply by aux (the stored GeLU'), 3 tanh, 4 multiply by 1 - aux^2,
-                                   * 5 exp(v - row_shift[row]) with per-row sums (the tied head's cross-entropy: fields at the end) */
+                                   * 5 exp(v - row_shift[row]) with per-row sums (the tied head's cross-entropy: fields at the end).
+                                   * act 1 with drop_thr16 != 0 (activation dropout): the output is keep ? GeLU(v) * drop_scale : 0 and
+                                   * preact receives keep ? GeLU'(v) * drop_scale : 0 -- the derivative of what was stored, so an act 2
+                                   * launch on it needs no mask.  (Until activation dropout went in, this combination stored the
+                                   * UNDROPPED derivative beside a dropped output; nothing in the engine, the tools or the tests
+                                   * launched it -- searched: every act 1 launch ran with drop_thr16 = 0, and those return the bits
+                                   * they always did.)  Launch variants 8, 14 and 15 do not carry the class and hand it on to 7. */
   kmb_bf16* preact; int32_t ld_preact;   /* act 1, optional: receives GeLU'(pre-activation) -- what the backward pass needs */
   const kmb_bf16* aux; int32_t ld_aux;   /* act 2: the tensor act 1 stored; act 4: tanh output */
   uint32_t drop_thr16; uint32_t drop_seed; float drop_scale;
@@ -188,6 +194,15 @@ int kmb_set_seed(kmb_handle* h, uint64_t seed);
  * kmb_op_dropout_mask(seed, thr16 / 65536, B * H * Tq, Tk) keeps element ((b * H + h) * Tq + q, k). */
 int kmb_set_attention_dropout(kmb_handle* h, float p);
 int kmb_attention_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed);
+/* Activation dropout (the reference's config.activation_dropout: F.dropout on gelu(fc1(x)) of every FFN block).  A run-time setting of the
+ * handle, exactly like attention dropout -- kmb_create refuses a non-zero kmb_config.activation_dropout -- that takes effect from the next
+ * forward; p in [0, 1).  Only training-mode forwards draw masks: eval forwards, kmb_score, generation and the fp32 validation mode run
+ * without.  The fc1 GEMM folds the mask into its GeLU output and into the stored GeLU' (KmbGemm.act), so backward neither stores nor redraws
+ * it.  kmb_activation_dropout_site reports what the LAST training forward used at a site (kind 0 encoder FFN, 1 decoder FFN; zeros when it
+ * ran without): element (row, col) of the [rows, F] hidden activations (rows = B * S for the encoder, B * T for the decoder, F the FFN
+ * width) was kept where kmb_op_dropout_mask(seed, thr16 / 65536, rows, F) keeps it. */
+int kmb_set_activation_dropout(kmb_handle* h, float p);
+int kmb_activation_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed);
 int kmb_abi_sizeof_attn(void);   /* sizeof(KmbAttn) as the library was compiled: a binding checks its own layout against it */
 
 /* gradient buckets for data-parallel overlap (DDP reducer, vcg_train.py:98): bucket i is complete

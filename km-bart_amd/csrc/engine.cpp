@@ -229,6 +229,30 @@ struct kmb_handle {
     return dr;
   }
   KmbDrop attn_drop_used(int kind, int layer, bool train) const { return train ? attn_used[kind][layer] : KmbDrop{0u, 0u, 1.f}; }
+  // Activation dropout (F.dropout on gelu(fc1(x)), HF 3.0.2 EncoderLayer / DecoderLayer): a run-time setting of the handle too
+  // (kmb_set_activation_dropout; cfg.activation_dropout stays refused by kmb_create).  The fc1 launch folds the mask into its output AND the stored
+  // GeLU' (KmbGemm, act 1 with drop_thr16), so backward neither stores nor redraws a mask.  Sites: ACT_SITE_BASE + 2 * layer + kind (0 encoder FFN,
+  // 1 decoder FFN).  The mixed word of a site is step * 0x10001 + site; ACT_SITE_BASE = 0x60000000 = 24576 * 0x10001 - 24576, so an activation site of
+  // step t carries the word (t + 24576) * 0x10001 - 24576 + 2 l + k.  It equals an existing site's word (t' * 0x10001 + c, c in 1, 2, 10 + 2 l', 11 + 2 l',
+  // 100 + 3 l' .. 102 + 3 l') only if 2 l + k - 24576 - c is a multiple of 0x10001 = 65537, and an attention site's (c = 0x40000000 + 3 l' + k' =
+  // 16384 * 0x10001 - 16384 + 3 l' + k') only if 2 l + k - 8192 - 3 l' - k' is: for layer counts below 4096 both differences lie strictly between
+  // -65537 and 0.  So no word meets another at any step, and every existing mask stays the one it was.
+  // act_used[kind][layer]: what the LAST training forward launched with (zeros: none), for kmb_activation_dropout_site.
+  static constexpr uint64_t ACT_SITE_BASE = 0x60000000ull;
+  float act_p = 0.f;
+  std::vector<KmbDrop> act_used[2];
+  KmbDrop act_drop_site(int kind, int layer, bool train) {
+    KmbDrop dr{0u, 0u, 1.f};
+    if (!train || act_p <= 0.f) return dr;
+    uint32_t thr = (uint32_t)lrintf(act_p * 65536.f);
+    if (thr > 65535u) thr = 65535u;
+    if (thr == 0u) return dr;
+    dr.thr16 = thr;
+    dr.seed = (uint32_t)splitmix(seed ^ splitmix(step * 0x10001ull + ACT_SITE_BASE + (uint64_t)(2 * layer + kind)));
+    dr.scale = 1.f / (1.f - (float)thr / 65536.f);
+    act_used[kind][layer] = dr;
+    return dr;
+  }
   bf16_t* wb(size_t off) const { return g_f32 ? reinterpret_cast<bf16_t*>(P + off) : PB + off; }   // GEMM B operand: bf16 mirror (fp32 master in validation mode)
   float* pf(size_t off) const { return P + off; }
   float* gf(size_t off) const { return G + off; }
@@ -803,12 +827,14 @@ int attn_backward(kmb_handle* h, const AttnIO& io, int B, int H, bf16_t* o, floa
   return 0;
 }
 
-// post-LN FFN block forward: z = x + drop(fc2(gelu(fc1(x)))) ; out = LN(z)
+// post-LN FFN block forward: z = x + drop(fc2(adrop(gelu(fc1(x))))) ; out = LN(z).  adr (activation dropout): hh = m * GeLU(a) and
+// u = m * GeLU'(a) come out of the fc1 launch, m = keep ? scale : 0 -- everything behind it, backward included, runs unchanged
 int ffn_forward(kmb_handle* h, const LayerP& L, int F, const bf16_t* x, bf16_t* u, bf16_t* hh, bf16_t* z, float* mean,
-                float* rstd, bf16_t* out, int M, KmbDrop dr, hipStream_t s) {
+                float* rstd, bf16_t* out, int M, KmbDrop dr, KmbDrop adr, hipStream_t s) {
   const int d = h->d;
   KmbGemm g = lin_fwd(x, d, h->wb(L.fc1_w), h->pf(L.fc1_b), M, F, d);
   g.act = 1; g.preact = u; g.ld_preact = F; g.out_bf16 = hh; g.ld_out_bf16 = F;
+  if (adr.thr16) { g.drop_thr16 = adr.thr16; g.drop_seed = adr.seed; g.drop_scale = adr.scale; }
   KCHK(run_gemm(g, s));
   g = lin_fwd(hh, F, h->wb(L.fc2_w), h->pf(L.fc2_b), M, d, F);
   g.drop_thr16 = dr.thr16; g.drop_seed = dr.seed; g.drop_scale = dr.scale;
@@ -966,7 +992,8 @@ int encoder_forward(kmb_handle* h, const kmb_batch& bt, bool train, hipStream_t 
     EncAct& a = h->ea[l];
     KCHK(self_attn_forward(h, L.sa, h->He, h->xe[l], a.qkv, a.o, a.lse, a.z1, a.m1, a.r1, a.y1, B, S,
                            bt.attention_mask, 0, h->drop_site(10 + 2 * l, train), h->attn_drop_site(0, l, train), s));
-    KCHK(ffn_forward(h, L, h->Fe, a.y1, a.u, a.hh, a.z2, a.m2, a.r2, h->xe[l + 1], Me, h->drop_site(11 + 2 * l, train), s));
+    KCHK(ffn_forward(h, L, h->Fe, a.y1, a.u, a.hh, a.z2, a.m2, a.r2, h->xe[l + 1], Me, h->drop_site(11 + 2 * l, train),
+                     h->act_drop_site(0, l, train), s));
   }
   return 0;
 }
@@ -1008,6 +1035,8 @@ int kmb_create(const kmb_config* cfg, kmb_handle** out) {
   h->attn_used[0].assign(cfg->encoder_layers, KmbDrop{0u, 0u, 1.f});
   h->attn_used[1].assign(cfg->decoder_layers, KmbDrop{0u, 0u, 1.f});
   h->attn_used[2].assign(cfg->decoder_layers, KmbDrop{0u, 0u, 1.f});
+  h->act_used[0].assign(cfg->encoder_layers, KmbDrop{0u, 0u, 1.f});
+  h->act_used[1].assign(cfg->decoder_layers, KmbDrop{0u, 0u, 1.f});
   h->enc.resize(cfg->encoder_layers);
   for (int l = 0; l < cfg->encoder_layers; ++l) {
     marks.push_back(align_up(h->arena, 64));
@@ -1152,6 +1181,22 @@ int kmb_attention_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr
   return 0;
 }
 
+int kmb_set_activation_dropout(kmb_handle* h, float p) {
+  if (!h) return fail("kmb_set_activation_dropout: null handle");
+  if (!(p >= 0.f && p < 1.f)) return fail("kmb_set_activation_dropout: the probability must be in [0, 1), got %g", (double)p);   // (NaN fails both)
+  h->act_p = p;
+  return 0;
+}
+
+int kmb_activation_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed) {
+  if (!h || !thr16 || !seed) return fail("kmb_activation_dropout_site: null argument");
+  if (kind < 0 || kind > 1) return fail("kmb_activation_dropout_site: kind must be 0 (encoder FFN) or 1 (decoder FFN)");
+  if (layer < 0 || layer >= (int)h->act_used[kind].size()) return fail("kmb_activation_dropout_site: no layer %d", layer);
+  const KmbDrop& dr = h->act_used[kind][layer];
+  *thr16 = dr.thr16; *seed = dr.thr16 ? dr.seed : 0u;
+  return 0;
+}
+
 int kmb_abi_sizeof_attn(void) { return (int)sizeof(KmbAttn); }
 
 int kmb_sync_params(kmb_handle* h, void* stream) {
@@ -1251,6 +1296,7 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
   if (train) {
     h->step += 1;
     for (auto& v : h->attn_used) std::fill(v.begin(), v.end(), KmbDrop{0u, 0u, 1.f});   // what THIS training forward uses is recorded as it goes
+    for (auto& v : h->act_used) std::fill(v.begin(), v.end(), KmbDrop{0u, 0u, 1.f});
   }
   const bool tr = train != 0;
   const float eps = h->cfg.layer_norm_eps;
@@ -1291,7 +1337,8 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
     g.residual = a.y1; g.ld_res = d; g.out_bf16 = a.z2; g.ld_out_bf16 = d;
     KCHK(run_gemm(g, s));
     KCHK(ln_forward(a.z2, h->pf(L.ca.ln_g), h->pf(L.ca.ln_b), a.y2, a.m2, a.r2, Md, d, eps, s));
-    KCHK(ffn_forward(h, L, h->Fd, a.y2, a.u, a.hh, a.z3, a.m3, a.r3, h->xd[l + 1], Md, h->drop_site(102 + 3 * l, tr), s));
+    KCHK(ffn_forward(h, L, h->Fd, a.y2, a.u, a.hh, a.z3, a.m3, a.r3, h->xd[l + 1], Md, h->drop_site(102 + 3 * l, tr),
+                     h->act_drop_site(1, l, tr), s));
   }
   const bf16_t* hdec = h->xd[h->cfg.decoder_layers];
   h->have_hdec = true;

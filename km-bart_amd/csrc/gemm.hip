@@ -254,6 +254,14 @@ __device__ __forceinline__ void gemm_epilogue_body(const KmbGemm& p, const float
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (v[e] + bias8[e]) * scale8[e];
     if (act == 1) {
+      // with dropout (activation dropout): m = keep ? drop_scale : 0 goes into the output AND the stored derivative -- what
+      // backward multiplies by (act 2) is then d/da of m * GeLU(a).  The output gets it from the dropout block below, as it always
+      // has; the derivative here.  Only the run-time class (ACT < 0) of the 128 x 128 kernels carries this (variants 1, 5, 7:
+      // gemm_epilogue_phase2 sends act 1 + dropout there).  Every other instantiation stays the code it was -- the hoisted
+      // ACT = 1 one, the 256 x 256 kernel's (variant 8: with the mask it needed scratch) and the persistent kernels' general
+      // path (WAVE: with it the eight-wave kernels spilled inside their K loops); gelu_drop_ok() keeps the class off those.
+      constexpr bool GDROP_BODY = ACT < 0 && !WAVE && NT == 256;
+      const bool gdrop = GDROP_BODY && drop;
       if (p.preact != nullptr) {   // GeLU and GeLU' from one evaluation; the DERIVATIVE is what backward needs (act 2)
         float dv[8];
 #pragma unroll
@@ -262,6 +270,16 @@ __device__ __forceinline__ void gemm_epilogue_body(const KmbGemm& p, const float
           gelu_both2(kmb_f32x2{v[e], v[e + 1]}, y, dy);
           v[e] = y[0]; v[e + 1] = y[1];
           dv[e] = dy[0]; dv[e + 1] = dy[1];
+        }
+        if (gdrop) {   // four hashes for the lane's eight columns, taken behind the GeLU arithmetic
+          const uint32_t rowterm = (uint32_t)grow * 0x9E3779B1u;
+#pragma unroll
+          for (int e = 0; e < 8; e += 2) {
+            bool k0, k1;
+            drop_keep_pair(p.drop_seed, rowterm, drop_colterm((uint32_t)(gcol + e)), p.drop_thr16, k0, k1);
+            dv[e] = k0 ? dv[e] * p.drop_scale : 0.f;
+            dv[e + 1] = k1 ? dv[e + 1] * p.drop_scale : 0.f;
+          }
         }
         if (full8) {
           *reinterpret_cast<u32x4*>(p.preact + (size_t)grow * p.ld_preact + gcol) = pack8(dv);
@@ -412,7 +430,7 @@ __device__ __forceinline__ void gemm_epilogue_phase2(const KmbGemm& p, const flo
     else if (res && !csf) KMB_EPI(0, true, false);
     else if (!res) KMB_EPI(0, false, true);
     else KMB_EPI(0, true, true);
-  } else if (p.act == 1 && !res && !csf) {
+  } else if (p.act == 1 && !res && !csf && (NT != 256 || p.drop_thr16 == 0u)) {   // (128 x 128 kernels, GeLU with dropout: the run-time class below)
     KMB_EPI(1, false, false);
   } else if (p.act == 2 && !res) {
     if (csf) KMB_EPI(2, false, true);
@@ -2011,8 +2029,15 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       } else if (lean_ok && p.act == 0 && !hb && !hd && !hc && !hs) {
         if (hr) KMB_LEAN(false, false, 0, true, false, false);
         else KMB_LEAN(false, false, 0, false, false, false);
-      } else if (lean_ok && p.act == 1 && hb && !hr && !hd && !hc && !hs) {
-        KMB_LEAN(true, false, 1, false, false, false);
+      } else if (lean_ok && p.act == 1 && hb && !hr && (NW == 4 || !hd) && !hc && !hs) {
+        // GeLU with dropout (activation dropout): the four-wave kernels only, and only launches of whole tiles (gelu_drop_ok):
+        // the general path below does not mask the stored derivative
+        if constexpr (NW == 4) {
+          if (hd) KMB_LEAN(true, false, 1, false, true, false);
+          else KMB_LEAN(true, false, 1, false, false, false);
+        } else {
+          KMB_LEAN(true, false, 1, false, false, false);
+        }
       } else if (lean_ok && p.act == 2 && !hb && !hr && !hd && hc && !hs) {
         KMB_LEAN(false, false, 2, false, false, true);
       } else if (lean_ok && p.act == 5 && hb && !hr && !hd && !hc && !hs && (WCOLS == 64 || WCOLS == 128)) {
@@ -2279,10 +2304,13 @@ uint32_t* v11_sched_slot(hipStream_t stream) {
   return it->second.base + (size_t)(it->second.seq++ % NSLOT) * 16;
 }
 
+// gdrop: GeLU with dropout (act 1 + drop_thr16, activation dropout) is tuned apart from the same shape without it: not every variant
+// carries that class (gelu_drop_ok), so the winner of the launch without dropout may not run it.  (Not in the tune file, whose lines
+// keep their eight fields and describe launches without it.)
 struct TuneKey {
-  int akc, bkc, M, N, K, split, act;
+  int akc, bkc, M, N, K, split, act, gdrop = 0;
   bool operator<(const TuneKey& o) const {
-    return std::tie(akc, bkc, M, N, K, split, act) < std::tie(o.akc, o.bkc, o.M, o.N, o.K, o.split, o.act);
+    return std::tie(akc, bkc, M, N, K, split, act, gdrop) < std::tie(o.akc, o.bkc, o.M, o.N, o.K, o.split, o.act, o.gdrop);
   }
 };
 std::map<TuneKey, int> g_best;
@@ -2328,11 +2356,26 @@ bool writes_an_input(const KmbGemm& p) {
   return p.beta != 0.f;
 }
 
+// GeLU with dropout (act 1 + drop_thr16: activation dropout, the mask goes into the stored derivative too).  The class lives in the
+// general epilogue of the 128 x 128 kernels (variants 1, 5, 7), in the lean epilogue of the four-wave persistent kernels (11, 12, 13;
+// bn > 0: whole tiles of 256 x bn and exactly that epilogue's options, since their general path does not carry it) and in kernels of
+// their own of variants 6 and 9.  Variants 8, 14 and 15 do not take it (bn = 0): with it the 256 x 256 kernel needed scratch and the
+// eight-wave kernels spilled inside their K loops; a forced launch falls back (14, 15 -> 8 -> 7).
+bool gelu_drop(const KmbGemm& p) { return p.act == 1 && p.drop_thr16 != 0u; }
+bool gelu_drop_ok(const KmbGemm& p, int bn) {
+  if (!gelu_drop(p)) return true;
+  return bn > 0 && (p.M % BM4) == 0 && (p.N % bn) == 0 && p.out_bf16 != nullptr && p.out_f32 == nullptr && p.bias != nullptr &&
+         p.residual == nullptr && p.colsum == nullptr && p.col_scale_n <= 0;
+}
+
 template <int BNT>
-bool v11_ok_bn(const KmbGemm& p) { return v11_ok(p, BNT); }
+bool v11_ok_bn(const KmbGemm& p) { return v11_ok(p, BNT) && gelu_drop_ok(p, BNT); }
+template <int BNT>
+bool v11_ok_8w(const KmbGemm& p) { return v11_ok(p, BNT) && gelu_drop_ok(p, 0); }
 
 // v8 (256x256 tiles): more than one 128x128 tile each way.  Smaller problems never reach the tuner either: they run variant 7.
 bool v8_ok(const KmbGemm& p) { return p.M > 128 && p.N > 128; }
+bool v8_row_ok(const KmbGemm& p) { return v8_ok(p) && gelu_drop_ok(p, 0); }
 
 bool never_ok(const KmbGemm&) { return false; }
 
@@ -2369,9 +2412,9 @@ const Variant g_rows[] = {
     {11, KMB_LAYOUTS_V11(256), nullptr, BM4, 256, 256, LDS11, true, true, v11_ok_bn<256>, 8},
     {12, KMB_LAYOUTS_V11(128), nullptr, BM4, 128, 256, LDS12, true, true, v11_ok_bn<128>, 8},
     {13, KMB_LAYOUTS_V11(192), nullptr, BM4, 192, 256, LDS11, true, false, v11_ok_bn<192>, 8},
-    {14, KMB_LAYOUTS_V11(256, 8), nullptr, BM4, 256, 512, LDS11, true, true, v11_ok_bn<256>, 8},
-    {15, KMB_LAYOUTS_V11(192, 8), nullptr, BM4, 192, 512, LDS11, true, false, v11_ok_bn<192>, 8},
-    {8, KMB_LAYOUTS(gemm_kernel_v8), nullptr, BM4, BN4, 512, LDS4, false, false, v8_ok, 7},
+    {14, KMB_LAYOUTS_V11(256, 8), nullptr, BM4, 256, 512, LDS11, true, true, v11_ok_8w<256>, 8},
+    {15, KMB_LAYOUTS_V11(192, 8), nullptr, BM4, 192, 512, LDS11, true, false, v11_ok_8w<192>, 8},
+    {8, KMB_LAYOUTS(gemm_kernel_v8), nullptr, BM4, BN4, 512, LDS4, false, false, v8_row_ok, 7},
     {5, KMB_LAYOUTS(gemm_kernel_v7d), nullptr, BM, BN, 256, LDS_DEEP, false, false, v7d_ok, 7},
     {7, KMB_LAYOUTS(gemm_kernel_v7), nullptr, BM, BN, 256, LDS_BYTES, false, false, nullptr, 7},
     {1, KMB_LAYOUTS(gemm_kernel), nullptr, BM, BN, 256, LDS_BYTES, false, false, nullptr, 7},
@@ -2510,6 +2553,8 @@ int kernel_variant(int v) { return v == 9 && g_shared_device ? 12 : v; }
 hipError_t launch_variant(int variant, const KmbGemm& p, hipStream_t stream) {
   const Variant* row = variant_row(kernel_variant(variant));
   if (!row) return hipErrorInvalidValue;
+  // GeLU with dropout reaches only kernels that mask the stored derivative too: anything else is an error, never a silent launch
+  if (gelu_drop(p) && !eligible(kernel_variant(variant), p)) return hipErrorInvalidValue;
   if (row->launcher) return row->launcher(p, stream);
   const void* kernel = row->kernel[p.a_kc && p.b_kc ? 0 : p.a_kc ? 1 : 2];
   if (!kernel) return hipErrorInvalidValue;
@@ -2657,6 +2702,8 @@ struct Route {
   bool tune;
   int cfg, tile_order;
 };
+TuneKey tune_key(const KmbGemm& p) { return TuneKey{p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act, gelu_drop(p) ? 1 : 0}; }
+
 Route gemm_route(const KmbGemm& p, int forced) {
   if ((p.K % BK) != 0) return {false, 1, p.tile_order};   // LDS-DMA variants have no K-edge zero fill
   if (!forced && narrow_ok(p)) return {false, 0, p.tile_order};
@@ -2664,8 +2711,13 @@ Route gemm_route(const KmbGemm& p, int forced) {
   if (forced) return {false, forced_variant(forced, p), p.tile_order | (prefetch_a(p) ? 2 : 0)};
   if (!v8_ok(p)) return {false, 7, p.tile_order};
   const TuneEnv& env = tune_env();
-  auto it = g_best.find(TuneKey{p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act});
-  if (it != g_best.end()) return {false, it->second, config_tile_order(p, it->second)};
+  auto it = g_best.find(tune_key(p));
+  if (it != g_best.end()) {
+    // The key holds the shape, not every epilogue option: a cached choice is used only if it may run THIS launch (an fp32 output or a
+    // missing bias under GeLU with dropout, say, is not the persistent kernels' lean class); otherwise down its fallbacks, as a forced one
+    const int cfg = eligible(it->second & 15, p) ? it->second : forced_variant(it->second & 15, p);
+    return {false, cfg, config_tile_order(p, cfg)};
+  }
   if (!env.autotune || writes_an_input(p)) return p.act == 5 ? Route{false, 11, config_tile_order(p, 11)} : Route{false, 7, p.tile_order};
   return {true, 0, 0};
 }
@@ -2724,9 +2776,9 @@ hipError_t kmb_gemm_launch(const KmbGemm& p, hipStream_t stream) {
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    const TuneKey key{p.a_kc, p.b_kc, p.M, p.N, p.K, p.split_k, p.act};
+    const TuneKey key = tune_key(p);
     g_best.emplace(key, best);
-    if (env.tune_file) {
+    if (env.tune_file && !key.gdrop) {
       if (FILE* f = fopen(env.tune_file, "a")) {
         fprintf(f, "%d %d %d %d %d %d %d %d\n", key.akc, key.bkc, key.M, key.N, key.K, key.split, key.act, best);
         fclose(f);

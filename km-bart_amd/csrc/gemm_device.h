@@ -149,7 +149,8 @@ __device__ __forceinline__ void dma_offsets256w4(uint32_t (&off)[NP], int ld, in
 // per 16-row chunk = 7 us per 256x256 tile (in-kernel stamps), as long as the tile's MFMAs at K = 256.  Interior wave
 // blocks with a bf16 output only; same operation order as gemm_epilogue_body (bit-identical results).
 //   BIAS: + bias[col];  SCALE: * col_scale (the whole wave block lies in the scaled columns);  ACT 1: GeLU (+ optional
-//   pre-activation store), 2: * GeLU'(aux);  DROP: dropout mask;  RES: + residual;  CS: column sums.
+//   pre-activation store), 2: * GeLU'(aux);  DROP: dropout mask (with ACT 1 also on the stored derivative);  RES: + residual;
+//   CS: column sums.
 template <bool BIAS, bool SCALE, int ACT, bool RES, bool DROP, bool CS, int WROWS, bool F32 = false, int NJ = 8>
 __device__ __forceinline__ void v11_epilogue_lean(const KmbGemm& p, f32x4 (&acc)[8][NJ], float* ef, int lane, int r, int g,
                                                   int row0w, int col0w) {
@@ -325,6 +326,20 @@ __device__ __forceinline__ void v11_epilogue_lean(const KmbGemm& p, f32x4 (&acc)
           if (WCOLS == 128) slot[1] = 0.f;
         }
       } else if (ACT == 1) {
+        // DROP (activation dropout): m = keep ? drop_scale : 0 goes into the output AND the stored derivative, so that what
+        // backward multiplies by (ACT 2) is d/da of m * GeLU(a).  One hash per column pair decides both.  The hashes are taken
+        // behind the GeLU arithmetic, when the derivative is already packed to bf16 (its eight registers are four by then: the
+        // epilogue's register peak stays the GeLU evaluation's), and a dropped derivative is cleared in its packed word.
+        // (gcol is a multiple of 8: a pair's column term is drop_colterm(gcol) + e * the term's multiplier.)
+        [[maybe_unused]] uint32_t hsh[4];
+        [[maybe_unused]] auto draw = [&]() {
+          uint32_t rw = (uint32_t)(row0w + lr + 16 * i + RPI * it), cw = (uint32_t)gcol;
+          asm volatile("" : "+v"(rw), "+v"(cw));   // nothing of the hashes is hoisted out of the tile loop into registers that live across the K loop
+          const uint32_t rowterm = rw * 0x9E3779B1u;
+          const uint32_t ct0 = drop_colterm(cw);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) hsh[e] = kmb_hash32(rowterm ^ (ct0 + (uint32_t)e * 0x85EBCA77u) ^ p.drop_seed);
+        };
         if (pre != nullptr) {   // GeLU and GeLU' from one evaluation; the derivative is stored for backward (ACT 2)
           kmb_f32x2 dv[4];
 #pragma unroll
@@ -332,18 +347,33 @@ __device__ __forceinline__ void v11_epilogue_lean(const KmbGemm& p, f32x4 (&acc)
             kmb_f32x2 y;
             gelu_both2(v[e], y, dv[e]);
             v[e] = y;
+            if constexpr (DROP) dv[e] = dv[e] * dscale2;
           }
-          const u32x4 pk = {pack2bf(dv[0][0], dv[0][1]), pack2bf(dv[1][0], dv[1][1]), pack2bf(dv[2][0], dv[2][1]), pack2bf(dv[3][0], dv[3][1])};
+          u32x4 pk = {pack2bf(dv[0][0], dv[0][1]), pack2bf(dv[1][0], dv[1][1]), pack2bf(dv[2][0], dv[2][1]), pack2bf(dv[3][0], dv[3][1])};
+          if constexpr (DROP) {
+            draw();
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              pk[e] = ((hsh[e] & 0xffffu) >= p.drop_thr16 ? pk[e] & 0xffffu : 0u) | ((hsh[e] >> 16) >= p.drop_thr16 ? pk[e] & 0xffff0000u : 0u);
+          }
           KMB_NT_STORE(pk, reinterpret_cast<u32x4*>(pre + roff * p.ld_preact));
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = gelu2(v[e]);
+          if constexpr (DROP) draw();
+        }
+        if constexpr (DROP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const kmb_f32x2 kept = v[e] * dscale2;
+            v[e] = kmb_f32x2{(hsh[e] & 0xffffu) >= p.drop_thr16 ? kept[0] : 0.f, (hsh[e] >> 16) >= p.drop_thr16 ? kept[1] : 0.f};
+          }
         }
       } else if (ACT == 2) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] * kmb_f32x2{su[it][2 * e], su[it][2 * e + 1]};
       }
-      if (DROP) {
+      if (DROP && ACT != 1) {   // (ACT 1 has drawn above: never a second time)
         const uint32_t grow = (uint32_t)(row0w + lr + 16 * i + RPI * it);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {

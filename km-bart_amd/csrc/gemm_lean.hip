@@ -76,8 +76,16 @@ __device__ __forceinline__ void ln_epilogue_score(const KmbGemm& p, const f32x4 
   }
 }
 
-template <bool B_KC, int EC>
+// LN_GDROP, a flag on the class number: the LN_GELU class with dropout in its epilogue (activation dropout: mask on the GeLU output and on the
+// stored GeLU').  A kernel of its own, gemm_kernel_lean<true, LN_GELU | LN_GDROP>, not a run-time branch inside the LN_GELU kernel as LN_BIAS_RES
+// has it: both epilogues in one kernel cost the GeLU kernel registers (the weight-gradient-layout instance went from 32 to 52 bytes of
+// scratch), and the kernel without dropout is the benchmark's fc1 launch.  Not an epilogue class: ln_class() answers LN_GELU with or without
+// dropout, the launcher adds the flag.
+constexpr int LN_GDROP = 64;
+template <bool B_KC, int EC_>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_kernel_lean(const KmbGemm p, uint32_t* sched, int dyn_first) {
+  constexpr int EC = EC_ & (LN_GDROP - 1);
+  constexpr bool GDROP = (EC_ & LN_GDROP) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -370,7 +378,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if constexpr (EC == LN_BIAS) { if (hs) KMB_LN_LEAN(true, true, 0, false, false, false); else KMB_LN_LEAN(true, false, 0, false, false, false); }
       if constexpr (EC == LN_BIAS_RES) { if (hd) KMB_LN_LEAN(true, false, 0, true, true, false); else KMB_LN_LEAN(true, false, 0, true, false, false); }
       if constexpr (EC == LN_PLAIN) { if (hr) KMB_LN_LEAN(false, false, 0, true, false, false); else KMB_LN_LEAN(false, false, 0, false, false, false); }
-      if constexpr (EC == LN_GELU) KMB_LN_LEAN(true, false, 1, false, false, false);
+      if constexpr (EC == LN_GELU) { if constexpr (GDROP) KMB_LN_LEAN(true, false, 1, false, true, false); else KMB_LN_LEAN(true, false, 1, false, false, false); }
       if constexpr (EC == LN_DGELU_CS) KMB_LN_LEAN(false, false, 2, false, false, true);
       if constexpr (EC == LN_CE) KMB_LN_LEAN(true, false, 5, false, false, false);
       if constexpr (EC == LN_SCORE) ln_epilogue_score<NJ>(p, acc, r, g, row0w, col0w);
@@ -392,7 +400,7 @@ int ln_class(const KmbGemm& p) {
   if (p.act == 0 && hb && !hr && !hd && !hc) return LN_BIAS;
   if (p.act == 0 && hb && hr && !hc && !hs) return LN_BIAS_RES;
   if (p.act == 0 && !hb && !hd && !hc && !hs) return LN_PLAIN;
-  if (p.act == 1 && hb && !hr && !hd && !hc && !hs) return LN_GELU;
+  if (p.act == 1 && hb && !hr && !hc && !hs) return LN_GELU;   // with or without (activation) dropout
   if (p.act == 2 && !hb && !hr && !hd && hc && !hs) return LN_DGELU_CS;
   if (p.act == 5 && hb && !hr && !hd && !hc && !hs) return LN_CE;
   return -1;
@@ -400,6 +408,17 @@ int ln_class(const KmbGemm& p) {
 
 template <bool B_KC>
 hipError_t ln_launch_layout(int ec, const KmbGemm& p, dim3 grid, hipStream_t stream, uint32_t* sched, int dyn_first) {
+  if (ec == LN_GELU && p.drop_thr16 != 0u) {   // GeLU with dropout: the GDROP kernel (forward layout only, kmb_gemm_lean_ok)
+    if constexpr (!B_KC) return hipErrorInvalidValue;
+    static bool attr = false;
+    if (!attr) {
+      hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel_lean<true, LN_GELU | LN_GDROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LN_LDS);
+      if (e != hipSuccess) return e;
+      attr = true;
+    }
+    hipLaunchKernelGGL((gemm_kernel_lean<true, LN_GELU | LN_GDROP>), grid, dim3(512), LN_LDS, stream, p, sched, dyn_first);
+    return hipGetLastError();
+  }
 #define KMB_LN_CASE(E)                                                                                                          \
   case E: {                                                                                                                     \
     static bool attr = false;                                                                                                   \
@@ -433,6 +452,9 @@ bool kmb_gemm_lean_ok(const KmbGemm& p) {
   if (p.out_bf16 == nullptr || p.out_f32 != nullptr || p.beta != 0.f) return false;
   if (p.col_scale_n > 0 && (p.col_scale_n % 64) != 0) return false;
   if (p.act == 5 && (p.row_shift == nullptr || p.row_sums == nullptr)) return false;
+  // GeLU with dropout: the forward layout only (the fc1 launch).  With a token-major B the kernel needs scratch, with or without the
+  // mask (32 bytes); nothing launches that layout with GeLU, and no second kernel that spills is built for it.
+  if (p.act == 1 && p.drop_thr16 != 0u && !p.b_kc) return false;
   if ((long)p.lda * 2 * 256 >= (1L << 31) || (long)p.ldb * 2 * 256 >= (1L << 31)) return false;   // 32-bit piece offsets
   return ln_class(p) >= 0;
 }

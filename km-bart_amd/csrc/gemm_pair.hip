@@ -48,8 +48,14 @@ __device__ __forceinline__ const char* pr_uniform(const char* ptr) {
   return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
 }
 
-template <int EC>
+// PR_GDROP, a flag on the class number: the PR_GELU class with dropout in its epilogue (activation dropout), a kernel of its own,
+// gemm_kernel_pair<PR_GELU | PR_GDROP>: with both epilogues behind a run-time branch the GeLU kernel, which runs without scratch, needed 12
+// bytes of it.  Not an epilogue class: pr_class() answers PR_GELU with or without dropout, the launcher adds the flag.
+constexpr int PR_GDROP = 64;
+template <int EC_>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) __attribute__((amdgpu_num_vgpr(255))) void gemm_kernel_pair(const KmbGemm p) {
+  constexpr int EC = EC_ & (PR_GDROP - 1);
+  constexpr bool GDROP = (EC_ & PR_GDROP) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -296,7 +302,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) __a
       if constexpr (EC == PR_BIAS) { if (hs) KMB_PR_LEAN(true, true, 0, false, false, false); else KMB_PR_LEAN(true, false, 0, false, false, false); }
       if constexpr (EC == PR_BIAS_RES) { if (hd) KMB_PR_LEAN(true, false, 0, true, true, false); else KMB_PR_LEAN(true, false, 0, true, false, false); }
       if constexpr (EC == PR_PLAIN) { if (hr) KMB_PR_LEAN(false, false, 0, true, false, false); else KMB_PR_LEAN(false, false, 0, false, false, false); }
-      if constexpr (EC == PR_GELU) KMB_PR_LEAN(true, false, 1, false, false, false);
+      if constexpr (EC == PR_GELU) { if constexpr (GDROP) KMB_PR_LEAN(true, false, 1, false, true, false); else KMB_PR_LEAN(true, false, 1, false, false, false); }
       if constexpr (EC == PR_DGELU_CS) KMB_PR_LEAN(false, false, 2, false, false, true);
       if constexpr (EC == PR_CE) KMB_PR_LEAN(true, false, 5, false, false, false);
 #undef KMB_PR_LEAN
@@ -322,7 +328,7 @@ int pr_class(const KmbGemm& p) {
   if (p.act == 0 && hb && !hr && !hd && !hc) return PR_BIAS;
   if (p.act == 0 && hb && hr && !hc && !hs) return PR_BIAS_RES;
   if (p.act == 0 && !hb && !hd && !hc && !hs) return PR_PLAIN;
-  if (p.act == 1 && hb && !hr && !hd && !hc && !hs) return PR_GELU;
+  if (p.act == 1 && hb && !hr && !hc && !hs) return PR_GELU;   // with or without (activation) dropout
   if (p.act == 2 && !hb && !hr && !hd && hc && !hs) return PR_DGELU_CS;
   if (p.act == 5 && hb && !hr && !hd && !hc && !hs) return PR_CE;
   return -1;
@@ -355,6 +361,16 @@ hipError_t kmb_gemm_pair_launch(const KmbGemm& p, hipStream_t stream) {
     }                                                                                                                         \
     hipLaunchKernelGGL((gemm_kernel_pair<E>), grid, dim3(256), PR_LDS + 1024, stream, p);                                             \
     break;                                                                                                                    \
+  }
+  if (pr_class(p) == PR_GELU && p.drop_thr16 != 0u) {   // GeLU with dropout: the GDROP kernel
+    static bool attr = false;
+    if (!attr) {
+      hipError_t e = hipFuncSetAttribute((const void*)gemm_kernel_pair<PR_GELU | PR_GDROP>, hipFuncAttributeMaxDynamicSharedMemorySize, PR_LDS + 1024);
+      if (e != hipSuccess) return e;
+      attr = true;
+    }
+    hipLaunchKernelGGL((gemm_kernel_pair<PR_GELU | PR_GDROP>), grid, dim3(256), PR_LDS + 1024, stream, p);
+    return hipGetLastError();
   }
   switch (pr_class(p)) {
     KMB_PR_CASE(PR_BIAS)

@@ -108,6 +108,8 @@ PROTOTYPES = {
     "kmb_set_seed": (C.c_int, [c_p, C.c_uint64]),
     "kmb_set_attention_dropout": (C.c_int, [c_p, f32]),
     "kmb_attention_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
+    "kmb_set_activation_dropout": (C.c_int, [c_p, f32]),
+    "kmb_activation_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
     "kmb_abi_sizeof_attn": (C.c_int, []),
     "kmb_bucket_count": (C.c_int, [c_p]),
     "kmb_bucket_range": (C.c_int, [c_p, C.c_int, C.POINTER(i64), C.POINTER(i64)]),

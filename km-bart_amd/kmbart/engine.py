@@ -69,7 +69,7 @@ class Engine:
         c.scale_embedding = 1 if getattr(config, "scale_embedding", False) else 0
         c.dropout = float(config.dropout)
         c.attention_dropout = 0.0   # a run-time setting of the handle (set_attention_dropout below); the creation struct refuses it
-        c.activation_dropout = float(config.activation_dropout)
+        c.activation_dropout = 0.0   # likewise (set_activation_dropout)
         c.layer_norm_eps = 1e-5
         if with_heads:  # MultiModalBartForPreTraining (reference src/model/model.py:133-158)
             if float(getattr(config, "classif_dropout", 0.0)) != 0.0:
@@ -82,6 +82,7 @@ class Engine:
         check(self.lib.kmb_create(C.byref(c), C.byref(h)))
         self.h = h
         self.set_attention_dropout(float(getattr(config, "attention_dropout", 0.0)))
+        self.set_activation_dropout(float(getattr(config, "activation_dropout", 0.0)))
         with torch.cuda.device(self.device):
             n = self.lib.kmb_arena_elems(h)
             nb = self.lib.kmb_bf16_arena_elems(h)
@@ -155,6 +156,19 @@ class Engine:
         cross); (0, 0) when it ran without dropout.  kmb_op_dropout_mask(seed, thr16 / 65536, B * H * Tq, Tk) rebuilds the mask."""
         thr, seed = C.c_uint32(0), C.c_uint32(0)
         check(self.lib.kmb_attention_dropout_site(self.h, int(kind), int(layer), C.byref(thr), C.byref(seed)))
+        return int(thr.value), int(seed.value)
+
+    def set_activation_dropout(self, p):
+        """Dropout probability of the FFN's hidden activations (config.activation_dropout), from the next training-mode forward
+        on; eval forwards, score() and generation never drop."""
+        check(self.lib.kmb_set_activation_dropout(self.h, C.c_float(float(p))))
+        self.activation_dropout = float(p)
+
+    def activation_dropout_site(self, kind, layer):
+        """(thr16, seed) the last training forward used at an FFN site (kind 0 encoder, 1 decoder); (0, 0) when it ran without
+        dropout.  kmb_op_dropout_mask(seed, thr16 / 65536, rows, F) rebuilds the mask (rows = B * S encoder, B * T decoder)."""
+        thr, seed = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.kmb_activation_dropout_site(self.h, int(kind), int(layer), C.byref(thr), C.byref(seed)))
         return int(thr.value), int(seed.value)
 
     # ---- workspace --------------------------------------------------------------------------
