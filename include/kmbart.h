@@ -614,6 +614,38 @@ int kmb_op_embed_bwd(const kmb_bf16* dz, const int64_t* ids, const int32_t* img_
 int kmb_op_pos_bwd(const kmb_bf16* dz, int B, int S, int D, float* dP, int pos_base, int P_rows, void* stream);
 int kmb_op_ce(const float* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale,
               float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, void* stream);
+/* the same on bf16 logits (the training head; ldv % 8 == 0, ldv <= 65536): dlogits may be NULL or equal to logits (the gradient then
+ * replaces the logits in place); status (optional, device int32): bit 1 is set when a label is neither -100 nor in [0, V) */
+int kmb_op_ce_bf16(const kmb_bf16* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float* loss_rows,
+                   kmb_bf16* dlogits, int32_t* count, float* loss, int32_t* status, void* stream);
+/* count[0] = number of labels in [0, V); status as above */
+int kmb_op_count_valid(const int64_t* labels, int n, int V, int32_t* count, int32_t* status, void* stream);
+/* loss[0] = sum(loss_rows[0, rows)) / count[0], NaN when count[0] == 0 (torch's mean over no targets) */
+int kmb_op_loss_finish(const float* loss_rows, int rows, const int32_t* count, float* loss, void* stream);
+/* The tied head's cross-entropy without a pass over the logits (KmbGemm act 5), piece by piece.
+ * shift[r] = H[r] . E[labels[r]] + bias[labels[r]] (1e30 where the label is -100 or out of range); bias_pad[0, V) = bias, [V, Vpad) = -1e30 */
+int kmb_op_ce_label_logit(const kmb_bf16* H, int ldh, const kmb_bf16* E, int lde, const float* bias, const int64_t* labels, int rows,
+                          int d, int V, int Vpad, float* shift, float* bias_pad, void* stream);
+/* per row, from the act 5 GEMM's row_sums: srow = S, loss_rows = log S - pick (pick NULL: 0), alpha = lm_factor / (count[0] S),
+ * ah = bf16(alpha H) (optional, [rows, d]), P[r][label] := bf16(exp(pick) - S) (P optional); ignored rows: all zero */
+int kmb_op_ce_rows_finish(const float* row_sums, int ld_sums, int nparts, const float* pick, const int64_t* labels, const int32_t* count,
+                          float lm_factor, int rows, int d, int V, const kmb_bf16* H, int ldh, float* loss_rows, float* srow,
+                          float* alpha, kmb_bf16* ah, kmb_bf16* P, int ldp, void* stream);
+/* out[r] = bf16(alpha[r] * sum over s < nslabs of slab[s * stride + r * d ...]) */
+int kmb_op_ce_dgrad_finish(const float* slab, int nslabs, int64_t stride, const float* alpha, kmb_bf16* out, int rows, int d, void* stream);
+/* pre-training heads (csrc/heads.hip).  loss_rows[r] = KL(target[r] || softmax(logits[r, :C])); dlogits (optional, bf16, row stride
+ * ldd, columns C..ldd-1 zeroed) = (sum(target[r]) softmax - target[r]) grad_scale / rows */
+int kmb_op_kl_div(const float* logits, int ld, int C, const float* target, int ldt, int rows, float grad_scale, float* loss_rows,
+                  kmb_bf16* dlogits, int ldd, void* stream);
+/* dst[i][0, cols) = src[idx[i]][0, cols); cols, src_ld, dst_ld multiples of 8 */
+int kmb_op_gather_rows_bf16(const kmb_bf16* src, int src_ld, const int32_t* idx, kmb_bf16* dst, int dst_ld, int rows, int cols,
+                            void* stream);
+/* acc[idx[i]][0, cols) += src[i][0, cols)  (fp32 atomics; acc rows are cols wide) */
+int kmb_op_scatter_add_rows(const kmb_bf16* src, int src_ld, const int32_t* idx, float* acc, int rows, int cols, void* stream);
+/* y = bf16(float(y) + a), n % 8 == 0 */
+int kmb_op_add_f32_into_bf16(kmb_bf16* y, const float* a, int64_t n, void* stream);
+/* out[0] = factor * sum(rows[0, n)) / denom */
+int kmb_op_mean_rows(const float* rows, int n, float factor, float denom, float* out, void* stream);
 int kmb_op_adamw(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16, int64_t n, const KmbAdamW* hp,
                  void* stream);
 int kmb_op_cast_bf16(const float* x, kmb_bf16* y, int64_t n, void* stream);

@@ -189,6 +189,77 @@ int kmb_op_ce(const float* logits, int ldv, int V, const int64_t* labels, int ro
   if (rc) return rc;
   return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, s), "loss_finish");
 }
+// the training head's bf16 form (ce_kernel_reg_bf16): dlogits may be null or equal to logits; status (optional) as kmb_op_count_valid
+int kmb_op_ce_bf16(const kmb_bf16* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float* loss_rows,
+                   kmb_bf16* dlogits, int32_t* count, float* loss, int32_t* status, void* stream) {
+  if (!logits || !labels || !loss_rows || !count || !loss || rows <= 0 || V <= 0 || ldv < V)
+    return kmb_set_error("kmb_op_ce_bf16: bad arguments");
+  if ((ldv & 7) || ldv > 65536) return kmb_set_error("kmb_op_ce_bf16: ldv must be a multiple of 8 and at most 65536");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = hipfail(kmb_count_valid_launch(labels, rows, V, count, status, s), "count_valid");
+  if (rc) return rc;
+  rc = hipfail(kmb_ce_bf16_launch(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, s), "ce_bf16");
+  if (rc) return rc;
+  return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, s), "loss_finish");
+}
+int kmb_op_count_valid(const int64_t* labels, int n, int V, int32_t* count, int32_t* status, void* stream) {
+  if (!labels || !count || n < 0) return kmb_set_error("kmb_op_count_valid: bad arguments");
+  return hipfail(kmb_count_valid_launch(labels, n, V, count, status, (hipStream_t)stream), "count_valid");
+}
+int kmb_op_loss_finish(const float* loss_rows, int rows, const int32_t* count, float* loss, void* stream) {
+  if (!loss_rows || !count || !loss || rows <= 0) return kmb_set_error("kmb_op_loss_finish: bad arguments");
+  return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, (hipStream_t)stream), "loss_finish");
+}
+int kmb_op_ce_label_logit(const kmb_bf16* H, int ldh, const kmb_bf16* E, int lde, const float* bias, const int64_t* labels, int rows,
+                          int d, int V, int Vpad, float* shift, float* bias_pad, void* stream) {
+  if (!H || !E || !bias || !labels || !shift || !bias_pad || rows <= 0 || d <= 0 || V <= 0 || Vpad < V || ldh < d || lde < d)
+    return kmb_set_error("kmb_op_ce_label_logit: bad arguments");
+  if ((d & 7) || (ldh & 7) || (lde & 7)) return kmb_set_error("kmb_op_ce_label_logit: d, ldh and lde must be multiples of 8");
+  const int rc = hipfail(kmb_ce_label_logit_launch(H, ldh, E, lde, bias, labels, rows, d, V, shift, (hipStream_t)stream), "ce_label_logit");
+  if (rc) return rc;
+  return hipfail(kmb_ce_pad_bias_launch(bias, V, Vpad, bias_pad, (hipStream_t)stream), "ce_pad_bias");
+}
+int kmb_op_ce_rows_finish(const float* row_sums, int ld_sums, int nparts, const float* pick, const int64_t* labels, const int32_t* count,
+                          float lm_factor, int rows, int d, int V, const kmb_bf16* H, int ldh, float* loss_rows, float* srow,
+                          float* alpha, kmb_bf16* ah, kmb_bf16* P, int ldp, void* stream) {
+  if (!row_sums || !labels || !count || !loss_rows || !srow || !alpha || rows <= 0 || nparts <= 0 || ld_sums < nparts || V <= 0 ||
+      (ah && !H) || (P && ldp < V))
+    return kmb_set_error("kmb_op_ce_rows_finish: bad arguments");
+  if (ah && (d <= 0 || (d & 7) || (ldh & 7) || ldh < d)) return kmb_set_error("kmb_op_ce_rows_finish: d and ldh must be multiples of 8, ldh >= d");
+  return hipfail(kmb_ce_rows_finish_launch(row_sums, ld_sums, nparts, pick, labels, count, lm_factor, rows, ah ? d : 0, V, H, ldh, loss_rows,
+                                           srow, alpha, ah, P, ldp, (hipStream_t)stream), "ce_rows_finish");
+}
+int kmb_op_ce_dgrad_finish(const float* slab, int nslabs, int64_t stride, const float* alpha, kmb_bf16* out, int rows, int d, void* stream) {
+  if (!slab || !alpha || !out || rows <= 0 || nslabs < 1 || d <= 0 || stride < 0) return kmb_set_error("kmb_op_ce_dgrad_finish: bad arguments");
+  if ((d & 7) || (stride & 3)) return kmb_set_error("kmb_op_ce_dgrad_finish: d must be a multiple of 8, stride of 4");
+  return hipfail(kmb_ce_dgrad_finish_launch(slab, nslabs, (size_t)stride, alpha, out, rows, d, (hipStream_t)stream), "ce_dgrad_finish");
+}
+int kmb_op_kl_div(const float* logits, int ld, int C, const float* target, int ldt, int rows, float grad_scale, float* loss_rows,
+                  kmb_bf16* dlogits, int ldd, void* stream) {
+  if (!logits || !target || !loss_rows || rows <= 0 || C <= 0 || ld < C || ldt < C || (dlogits && ldd < C))
+    return kmb_set_error("kmb_op_kl_div: bad arguments");
+  return hipfail(kmb_kl_div_launch(logits, ld, C, target, ldt, rows, grad_scale, loss_rows, dlogits, dlogits ? ldd : C, (hipStream_t)stream),
+                 "kl_div");
+}
+int kmb_op_gather_rows_bf16(const kmb_bf16* src, int src_ld, const int32_t* idx, kmb_bf16* dst, int dst_ld, int rows, int cols,
+                            void* stream) {
+  if (!src || !idx || !dst || rows <= 0 || cols <= 0 || src_ld < cols || dst_ld < cols) return kmb_set_error("kmb_op_gather_rows_bf16: bad arguments");
+  if ((cols & 7) || (src_ld & 7) || (dst_ld & 7)) return kmb_set_error("kmb_op_gather_rows_bf16: cols, src_ld and dst_ld must be multiples of 8");
+  return hipfail(kmb_gather_rows_bf16_launch(src, src_ld, idx, dst, dst_ld, rows, cols, (hipStream_t)stream), "gather_rows_bf16");
+}
+int kmb_op_scatter_add_rows(const kmb_bf16* src, int src_ld, const int32_t* idx, float* acc, int rows, int cols, void* stream) {
+  if (!src || !idx || !acc || rows <= 0 || cols <= 0 || src_ld < cols) return kmb_set_error("kmb_op_scatter_add_rows: bad arguments");
+  return hipfail(kmb_scatter_add_rows_launch(src, src_ld, idx, acc, rows, cols, (hipStream_t)stream), "scatter_add_rows");
+}
+int kmb_op_add_f32_into_bf16(kmb_bf16* y, const float* a, int64_t n, void* stream) {
+  if (!y || !a || n <= 0) return kmb_set_error("kmb_op_add_f32_into_bf16: bad arguments");
+  if (n & 7) return kmb_set_error("kmb_op_add_f32_into_bf16: n must be a multiple of 8");
+  return hipfail(kmb_add_f32_into_bf16_launch(y, a, (size_t)n, (hipStream_t)stream), "add_f32_into_bf16");
+}
+int kmb_op_mean_rows(const float* rows, int n, float factor, float denom, float* out, void* stream) {
+  if (!rows || !out || n <= 0) return kmb_set_error("kmb_op_mean_rows: bad arguments");
+  return hipfail(kmb_mean_rows_launch(rows, n, factor, denom, out, (hipStream_t)stream), "mean_rows");
+}
 int kmb_op_adamw(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16, int64_t n, const KmbAdamW* hp,
                  void* stream) {
   return hipfail(kmb_adamw_launch(p, g, m, v, p_bf16, (size_t)n, *hp, (hipStream_t)stream), "adamw");

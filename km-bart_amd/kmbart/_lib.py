@@ -214,6 +214,18 @@ PROTOTYPES = {
     "kmb_op_embed_bwd": (C.c_int, [c_p, c_p, c_p, f32, c_p, c_p, i64, C.c_int, C.c_int, c_p]),
     "kmb_op_pos_bwd": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, C.c_int, c_p]),
     "kmb_op_ce": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, f32, c_p, c_p, c_p, c_p, c_p]),
+    "kmb_op_ce_bf16": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, f32, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "kmb_op_count_valid": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p, c_p]),
+    "kmb_op_loss_finish": (C.c_int, [c_p, C.c_int, c_p, c_p, c_p]),
+    "kmb_op_ce_label_logit": (C.c_int, [c_p, C.c_int, c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p]),
+    "kmb_op_ce_rows_finish": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p, c_p, f32, C.c_int, C.c_int, C.c_int, c_p, C.c_int, c_p, c_p,
+                                        c_p, c_p, c_p, C.c_int, c_p]),
+    "kmb_op_ce_dgrad_finish": (C.c_int, [c_p, C.c_int, i64, c_p, c_p, C.c_int, C.c_int, c_p]),
+    "kmb_op_kl_div": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, c_p, c_p, C.c_int, c_p]),
+    "kmb_op_gather_rows_bf16": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p]),
+    "kmb_op_scatter_add_rows": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, c_p]),
+    "kmb_op_add_f32_into_bf16": (C.c_int, [c_p, c_p, i64, c_p]),
+    "kmb_op_mean_rows": (C.c_int, [c_p, C.c_int, f32, f32, c_p, c_p]),
     "kmb_op_adamw": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, C.POINTER(KmbAdamW), c_p]),
     "kmb_op_cast_bf16": (C.c_int, [c_p, c_p, i64, c_p]),
     "kmb_op_dropout_mask": (C.c_int, [u32, f32, C.c_int, C.c_int, c_p, c_p]),

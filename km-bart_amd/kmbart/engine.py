@@ -52,6 +52,19 @@ def pack_features(image_features, feat_dim, device):
     return packed, offsets, offs[-1]
 
 
+def refuse_ignored_head_labels(head, labels):
+    """The attribute and relation heads take class ids only.  The reference's collator builds their labels from the dataset's
+    attribute_ids / predicate_id (src/data/collation.py:149-190) and never writes -100 there -- only the LM labels are masked
+    (:192-195) -- so an ignored label cannot reach these heads on the reference's data path.  The engine's head loss divides by the
+    number of rows while its gradient divides by the number of valid labels (csrc/engine.cpp head_run): with a -100 the two would
+    disagree with each other and with CrossEntropyLoss().  Refused here instead of being averaged one way or the other."""
+    if labels is None or labels.numel() == 0:
+        return
+    if bool((labels == -100).any()):
+        raise ValueError("%s labels hold -100: the %s head takes class ids only (the reference's collator never emits an ignored "
+                         "label for it); drop those rows from the head's row list instead" % (head, head))
+
+
 class Engine:
     """One model replica on one GPU."""
 
@@ -340,6 +353,8 @@ class Engine:
         labels).  Returns (losses fp32 [5] = total, lm, mrm, attribute, relation; logits or None) -- plus the encoder states
         with want_encoder.  `encoder_states` [B,S,D] skips the encoder (reference src/model/model.py:225-242 passes
         `encoder_outputs` through to self.model)."""
+        refuse_ignored_head_labels("attribute", None if attr is None else attr[1])
+        refuse_ignored_head_labels("relation", None if rel is None else rel[2])
         with torch.cuda.device(self.device):
             b, keep, (B, S, T, ntot) = self._batch(input_ids, image_features if encoder_states is None else [], attention_mask,
                                                    decoder_input_ids, decoder_attention_mask, labels)

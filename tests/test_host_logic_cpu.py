@@ -3,6 +3,7 @@ fine_tune loop order and log format, generate_text record schema)."""
 import json
 import types
 
+import pytest
 import torch
 
 from src.data.synthetic import IMG_FEAT, make_batch
@@ -250,3 +251,20 @@ def test_validate_generation_score_is_importable_and_says_what_it_needs():
     with pytest.raises(NotImplementedError) as e:
         validate_generation_score(0, object(), [], [], None, "cpu", types.SimpleNamespace(cpu=True))
     assert "evaluation" in str(e.value)
+
+
+def test_forward_pretrain_refuses_ignored_labels_for_the_hard_label_heads():
+    """-100 never reaches the attribute / relation heads on the reference's data path (its collator writes class ids there and masks
+    only the LM labels); the engine's head loss and gradient would average such a batch differently, so forward_pretrain refuses it
+    before anything is sent to the device (no engine state is touched: an unconstructed Engine is enough to show that)."""
+    from kmbart.engine import Engine, refuse_ignored_head_labels
+    rows = torch.arange(3, dtype=torch.int32)
+    good, bad = torch.tensor([4, 0, 7]), torch.tensor([4, -100, 7])
+    refuse_ignored_head_labels("attribute", good)
+    refuse_ignored_head_labels("relation", None)
+    refuse_ignored_head_labels("relation", torch.zeros(0, dtype=torch.int64))
+    eng = object.__new__(Engine)
+    with pytest.raises(ValueError, match="attribute labels hold -100"):
+        Engine.forward_pretrain(eng, None, None, None, None, None, None, attr=(rows, bad))
+    with pytest.raises(ValueError, match="relation labels hold -100"):
+        Engine.forward_pretrain(eng, None, None, None, None, None, None, attr=(rows, good), rel=(rows, rows, bad))
