@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libkmbart_hip.so")
-SOURCES = ["gemm.hip", "gemm_pair.hip", "gemm_lean.hip", "attention.hip", "norm.hip", "embed.hip", "loss.hip", "optim.hip", "heads.hip", "fp32_validate.hip", "decode.hip", "sample.hip", "beam_sample.hip", "greedy.hip", "engine.cpp", "capi_ops.cpp"]
+SOURCES = ["gemm.hip", "gemm_pair.hip", "gemm_lean.hip", "attention.hip", "norm.hip", "embed.hip", "loss.hip", "optim.hip", "heads.hip", "fp32_validate.hip", "decode.hip", "sample.hip", "beam_sample.hip", "greedy.hip", "engine.cpp", "engine_train.cpp", "engine_comm.cpp", "engine_gen.cpp",
+           "capi_ops.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
 # -fno-slp-vectorize: with SLP-packed fp32 math (v_pk_add_f32 / v_pk_mul_f32 with op_sel / neg modifiers on register pairs
 # assembled by v_mov) hipcc 7.2 produced an ln_bwd_kernel whose dz output is wrong in a few elements per launch (lanes 48-63,
@@ -20,7 +21,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-f
 # -O2 / -O3, also with the SDWA peephole or early if-conversion off or the division replaced; 0 of 20 at -O1 and at -O3
 # without the SLP vectoriser).  Explicit two-wide vector code (kmb_f32x2) is not affected.  DESIGN.md section 5.
 FILE_FLAGS = {}
-# the gradient exchange (kmb_allreduce_grads, csrc/engine.cpp) calls RCCL directly
+# the gradient exchange (kmb_allreduce_grads, csrc/engine_comm.cpp) calls RCCL directly
 RCCL_LINK = ["-L/opt/rocm/lib", "-lrccl"]
 
 
@@ -106,7 +107,7 @@ if __name__ == "__main__":
         i = sys.argv.index("--variant")
         defs = sys.argv[i + 2:]
         # KMB_DIAG (csrc/diag.h) switches the A/B environment knobs and ablation bits on in every file that has them
-        srcs = ("gemm.hip", "gemm_lean.hip", "engine.cpp", "attention.hip", "optim.hip") if "KMB_DIAG" in defs else ("gemm.hip",)
+        srcs = ("gemm.hip", "gemm_lean.hip", "engine.cpp", "engine_train.cpp", "engine_gen.cpp", "attention.hip", "optim.hip") if "KMB_DIAG" in defs else ("gemm.hip",)
         extra = ()
         if sys.argv[i + 1].startswith("rolesplit") or any(d.startswith("KMB_RS_") for d in defs):
             # the role-split GEMM (variant 10, tools/experiments/gemm_rolesplit.hip): `--variant rolesplit` (+ KMB_RS_NOEPI ...

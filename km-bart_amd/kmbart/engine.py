@@ -56,7 +56,7 @@ def refuse_ignored_head_labels(head, labels):
     """The attribute and relation heads take class ids only.  The reference's collator builds their labels from the dataset's
     attribute_ids / predicate_id (src/data/collation.py:149-190) and never writes -100 there -- only the LM labels are masked
     (:192-195) -- so an ignored label cannot reach these heads on the reference's data path.  The engine's head loss divides by the
-    number of rows while its gradient divides by the number of valid labels (csrc/engine.cpp head_run): with a -100 the two would
+    number of rows while its gradient divides by the number of valid labels (csrc/engine_train.cpp head_run): with a -100 the two would
     disagree with each other and with CrossEntropyLoss().  Refused here instead of being averaged one way or the other."""
     if labels is None or labels.numel() == 0:
         return

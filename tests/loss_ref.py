@@ -231,7 +231,7 @@ def head_ref(k):
 
 
 def emu_head(k):
-    """engine.cpp head_run's roundings on float64 arithmetic: y = bf16(tanh); logits fp32; dlogits = bf16; dy = bf16((dlogits Wo)(1 - y^2));
+    """engine_train.cpp head_run's roundings on float64 arithmetic: y = bf16(tanh); logits fp32; dlogits = bf16; dy = bf16((dlogits Wo)(1 - y^2));
     dx = bf16(dy Wd); scatter-add in fp32; states gradient = bf16(upstream + sum)"""
     n, C, f = HEAD["n"], HEAD["C"], HEAD["factor"]
     x = f64(k["hdec"])[k["rows"].long()]

@@ -144,7 +144,7 @@ def test_chunk_zero_against_the_oracle(setup):
 
 @pytest.mark.parametrize("bsz", [64, 512])
 def test_cross_entropy_fused_into_the_head_gemm_vs_the_two_kernel_path(setup, bsz):
-    """The tied head's loss two ways (engine.cpp forward_impl): the head GEMM's epilogue storing exp(logit - label logit)
+    """The tied head's loss two ways (engine_train.cpp lm_head): the head GEMM's epilogue storing exp(logit - label logit)
     plus row sums (no pass over the logits), against bf16 logits + the softmax kernel (KMB_FUSED_CE=0).  Same mathematics
     (reference src/model/model.py:398-402), other roundings: the probabilities are bf16 of exp(v - c) instead of bf16 of
     the scaled difference, the per-row factor multiplies H (bf16) for the weight gradient and the fp32 sum for dH."""

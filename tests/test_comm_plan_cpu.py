@@ -1,7 +1,7 @@
 """CPU: the partition of the native RCCL gradient exchange for world sizes that have never run on hardware.
 
 `kmb_allreduce_grads` (reduce-scatter -> sharded AdamW -> all-gather) and `kmb_comm_gather_moments` take every offset from
-`kmb_comm_plan` (csrc/engine.cpp::comm_plan_piece), a pure host function of the arena layout.  With one rank every collective
+`kmb_comm_plan` (csrc/engine_comm.cpp::comm_plan_piece), a pure host function of the arena layout.  With one rank every collective
 is the identity and `mine == offset`, so the one-GPU tests (tests/test_dp_rccl_gpu.py) say nothing about the world > 1
 arithmetic; this test pins it without a GPU: for W in {2, 4, 8} and both piece caps the shards of all ranks tile [0, arena)
 exactly once, every shard is 8-element aligned (the fused optimizer's vector width), pieces stay inside their bucket, and the

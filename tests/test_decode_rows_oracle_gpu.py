@@ -1,7 +1,7 @@
 """GPU: the decode step at the row counts where its dispatch changes, against the CPU oracle -- not against another product path.
 
 At 64 items x 5 beams (the benchmarked generation, 320 rows) the step runs code no other shape reaches: the all-rows vocabulary GEMM with
-its per-block (max, sum-exp) statistics (257-320 rows, engine.cpp run_vocab_gemm), the one-launch beam step that selects from those
+its per-block (max, sum-exp) statistics (257-320 rows, engine_train.cpp run_vocab_gemm), the one-launch beam step that selects from those
 statistics, and the beam step's folded reorder + next-step embedding.  Here:
 
   * teacher-forced step logits of Engine.gen_step vs oracle.forward over the same R = B x nb sequences (every row its own tokens), per row

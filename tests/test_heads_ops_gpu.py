@@ -4,7 +4,7 @@ against float64 at the real class counts (1601 region classes, 129 here for the 
 kl_div, gather_rows_bf16, scatter_add_rows, add_f32_into_bf16, mean_rows; KmbGemm act 3 (tanh) and act 4 (times 1 - aux^2); forward
 GEMMs with N = 1601 / 129 into fp32 rows of 1608 / 136; the weight gradient with 1601 / 129 output rows; the data gradient that reduces
 over the padded class dimension; kmb_op_colsum over 1601 of 1608 columns; and one whole MRM head composed from these calls as
-engine.cpp head_run composes it, against float64 autograd of the same head (reference src/model/model.py:133-158, :248-258).
+engine_train.cpp head_run composes it, against float64 autograd of the same head (reference src/model/model.py:133-158, :248-258).
 
 Bounds: F32_TOL / BF_TOL of test_ops_gpu.py; for bf16 outputs additionally every element within one bf16 rounding (2^-8 + 2^-15 of the
 float64 value) plus the worst-case fp32 accumulation error of its own dot product, K * 2^-24 * sum |a| |b|; for the KL gradient the same
