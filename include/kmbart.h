@@ -203,6 +203,17 @@ int kmb_attention_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr
  * width) was kept where kmb_op_dropout_mask(seed, thr16 / 65536, rows, F) keeps it. */
 int kmb_set_activation_dropout(kmb_handle* h, float p);
 int kmb_activation_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed);
+/* Classification-head dropout (the reference's config.classif_dropout: HF 3.0.2 BartClassificationHead drops its input and its tanh output,
+ * two independent F.dropout calls per head, src/model/model.py:133-158).  A run-time setting of the handle like the two above -- kmb_config
+ * keeps its layout and kmb_create does not learn it -- that takes effect from the next training-mode forward; p in [0, 1).  Only
+ * kmb_forward_pretrain* with train = 1 draws masks: eval forwards, kmb_score and generation run without, and a model without heads has
+ * nothing to drop.  kmb_classif_dropout_site reports what the LAST training forward used at a site (head 0 masked-region, 1 attribute,
+ * 2 relation; which 0 the head's input, 1 its hidden tanh output; zeros when that forward ran without, when the head had no rows, or when
+ * the model has no such head): element (row, col) of the head's gathered input [n, d_in] (d_in = d_model, 2 d_model = object | subject for
+ * the relation head) or of its hidden activations [n, d_model] was kept where kmb_op_dropout_mask(seed, thr16 / 65536, n, d_in or d_model)
+ * keeps it; kept elements are multiplied by 1 / (1 - thr16 / 65536). */
+int kmb_set_classif_dropout(kmb_handle* h, float p);
+int kmb_classif_dropout_site(kmb_handle* h, int head, int which, uint32_t* thr16, uint32_t* seed);
 int kmb_abi_sizeof_attn(void);   /* sizeof(KmbAttn) as the library was compiled: a binding checks its own layout against it */
 
 /* gradient buckets for data-parallel overlap (DDP reducer, vcg_train.py:98): bucket i is complete
@@ -640,6 +651,14 @@ int kmb_op_kl_div(const float* logits, int ld, int C, const float* target, int l
 /* dst[i][0, cols) = src[idx[i]][0, cols); cols, src_ld, dst_ld multiples of 8 */
 int kmb_op_gather_rows_bf16(const kmb_bf16* src, int src_ld, const int32_t* idx, kmb_bf16* dst, int dst_ld, int rows, int cols,
                             void* stream);
+/* The gather with a dropout mask (the two F.dropout calls of a classification head, kmb_set_classif_dropout):
+ * dst[i][c] = m(i, c) src[idx_a[i]][c] for c < cols, and, with idx_b != NULL, dst[i][cols + c] = m(i, cols + c) src[idx_b[i]][c] in the same
+ * launch (the relation head's object | subject rows).  idx_a == NULL: identity rows -- a matrix masked into another buffer, or in place; idx_b
+ * must then be NULL too.  dst == src is refused with an index array (a gather in place would race); otherwise the two must not overlap.  m(row, col) = drop->scale where kmb_op_dropout_mask(drop->seed, drop->thr16 / 65536, rows, written columns) keeps
+ * (row, col), +0 elsewhere: the coordinate is the DESTINATION's.  Kept values are multiplied in fp32 and rounded once to bf16.  drop NULL or
+ * thr16 == 0: the bits of kmb_op_gather_rows_bf16.  cols, src_ld, dst_ld multiples of 8; dst_ld >= the written columns. */
+int kmb_op_gather_rows_drop_bf16(const kmb_bf16* src, int src_ld, const int32_t* idx_a, const int32_t* idx_b, kmb_bf16* dst, int dst_ld,
+                                 int rows, int cols, const KmbDrop* drop, void* stream);
 /* acc[idx[i]][0, cols) += src[i][0, cols)  (fp32 atomics; acc rows are cols wide) */
 int kmb_op_scatter_add_rows(const kmb_bf16* src, int src_ld, const int32_t* idx, float* acc, int rows, int cols, void* stream);
 /* y = bf16(float(y) + a), n % 8 == 0 */

@@ -247,6 +247,21 @@ int kmb_op_gather_rows_bf16(const kmb_bf16* src, int src_ld, const int32_t* idx,
   if ((cols & 7) || (src_ld & 7) || (dst_ld & 7)) return kmb_set_error("kmb_op_gather_rows_bf16: cols, src_ld and dst_ld must be multiples of 8");
   return hipfail(kmb_gather_rows_bf16_launch(src, src_ld, idx, dst, dst_ld, rows, cols, (hipStream_t)stream), "gather_rows_bf16");
 }
+int kmb_op_gather_rows_drop_bf16(const kmb_bf16* src, int src_ld, const int32_t* idx_a, const int32_t* idx_b, kmb_bf16* dst, int dst_ld,
+                                 int rows, int cols, const KmbDrop* drop, void* stream) {
+  const int halves = idx_b ? 2 : 1;
+  if (!src || !dst || rows <= 0 || cols <= 0 || src_ld < cols || dst_ld / halves < cols)
+    return kmb_set_error("kmb_op_gather_rows_drop_bf16: bad arguments");
+  if ((cols & 7) || (src_ld & 7) || (dst_ld & 7))
+    return kmb_set_error("kmb_op_gather_rows_drop_bf16: cols, src_ld and dst_ld must be multiples of 8");
+  if (!idx_a && idx_b) return kmb_set_error("kmb_op_gather_rows_drop_bf16: idx_b needs idx_a (identity rows take no second half)");
+  if (dst == src && idx_a) return kmb_set_error("kmb_op_gather_rows_drop_bf16: dst may be src with identity rows only (a gather in place would race)");
+  const KmbDrop dr = drop ? *drop : KmbDrop{0u, 0u, 1.f};
+  if (dr.thr16 > 65535u || (dr.thr16 != 0u && !(dr.scale > 0.f && dr.scale <= 3.4028234e38f)))
+    return kmb_set_error("kmb_op_gather_rows_drop_bf16: thr16 must be at most 65535 and the scale finite and positive");
+  return hipfail(kmb_gather_rows_drop_bf16_launch(src, src_ld, idx_a, idx_b, dst, dst_ld, rows, cols, dr, (hipStream_t)stream),
+                 "gather_rows_drop_bf16");
+}
 int kmb_op_scatter_add_rows(const kmb_bf16* src, int src_ld, const int32_t* idx, float* acc, int rows, int cols, void* stream) {
   if (!src || !idx || !acc || rows <= 0 || cols <= 0 || src_ld < cols) return kmb_set_error("kmb_op_scatter_add_rows: bad arguments");
   return hipfail(kmb_scatter_add_rows_launch(src, src_ld, idx, acc, rows, cols, (hipStream_t)stream), "scatter_add_rows");

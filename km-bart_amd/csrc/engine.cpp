@@ -620,6 +620,22 @@ int kmb_activation_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* th
   return 0;
 }
 
+int kmb_set_classif_dropout(kmb_handle* h, float p) {
+  if (!h) return fail("kmb_set_classif_dropout: null handle");
+  if (!(p >= 0.f && p < 1.f)) return fail("kmb_set_classif_dropout: the probability must be in [0, 1), got %g", (double)p);   // (NaN fails both)
+  h->cls_p = p;
+  return 0;
+}
+
+int kmb_classif_dropout_site(kmb_handle* h, int head, int which, uint32_t* thr16, uint32_t* seed) {
+  if (!h || !thr16 || !seed) return fail("kmb_classif_dropout_site: null argument");
+  if (head < 0 || head > 2) return fail("kmb_classif_dropout_site: head must be 0 (masked-region), 1 (attribute) or 2 (relation)");
+  if (which < 0 || which > 1) return fail("kmb_classif_dropout_site: which must be 0 (the head's input) or 1 (its hidden activations)");
+  const KmbDrop& dr = h->cls_used[head][which];
+  *thr16 = dr.thr16; *seed = dr.thr16 ? dr.seed : 0u;
+  return 0;
+}
+
 int kmb_abi_sizeof_attn(void) { return (int)sizeof(KmbAttn); }
 
 int kmb_sync_params(kmb_handle* h, void* stream) {

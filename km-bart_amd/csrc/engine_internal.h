@@ -131,6 +131,7 @@ struct TrainLayout {
   float* losses5 = nullptr;
   // pre-training head scratch (null unless heads exist and rows were reserved)
   bf16_t *hx = nullptr, *hy = nullptr, *hdy = nullptr, *hdx = nullptr, *hdlg = nullptr; float *hlg = nullptr, *hloss = nullptr, *dhead = nullptr;
+  bf16_t* hyd = nullptr;   // [n, d]: the hidden activations hy under their classif_dropout mask (what out_proj and its weight gradient read)
   float* head_slab = nullptr; size_t head_slab_floats = 0;  // split-K partials of the pre-training heads' weight gradients (caller's stream)
   EncoderBufs encoder() const { return {status, xf, img_emb, img_src, ze0, me0, re0, xe.data(), ea.data(), false}; }
 };
@@ -230,6 +231,12 @@ struct kmb_handle {
   // carries the word (t + 24576) * 0x10001 - 24576 + 2 l + k.  It equals a hidden site's word (t' * 0x10001 + c) only if 2 l + k - 24576 - c is a
   // multiple of 0x10001 = 65537, and an attention site's (c = 0x40000000 + 3 l' + k' = 16384 * 0x10001 - 16384 + 3 l' + k') only if
   // 2 l + k - 8192 - 3 l' - k' is: for layer counts below 4096 both differences lie strictly between -65537 and 0.
+  //   classification-head dropout (cls_drop_site): CLS_SITE_BASE + 2 * head + which (head 0 mrm, 1 attribute, 2 relation; which 0 input, 1 hidden)
+  // CLS_SITE_BASE = 0x50000000 = 20480 * 0x10001 - 20480, so a head site of step t carries the word (t + 20480) * 0x10001 - 20480 + s with
+  // s = 2 head + which in 0 .. 5.  It equals a hidden site's word only if s - 20480 - c is a multiple of 65537 (c <= 102 + 3 l: the difference lies
+  // strictly between -65537 and 0 while l < 14985), an attention site's only if s - 4096 - 3 l' - k' is (between -65537 and 0 while l' < 20479), and an
+  // activation site's only if s + 4096 - 2 l'' - k'' is: that one is positive and at most 4101 while 2 l'' + k'' < 4096, and reaches 0 at layer 2048.
+  // So no word of the family meets another at any step for layer counts below 2048 -- the bound of the four families together.
   // zero_off: a probability that rounds to threshold 0 is no dropout at all (seed 0 as well).  The two run-time families have it; drop_site never
   // had and keeps its seed there -- kmb_create does not validate cfg.dropout, so a probability below 2^-17 can reach it.
   KmbDrop site_drop(float p, uint64_t word, bool train, bool zero_off) const {
@@ -266,6 +273,18 @@ struct kmb_handle {
   KmbDrop act_drop_site(int kind, int layer, bool train) {
     const KmbDrop dr = site_drop(act_p, ACT_SITE_BASE + (uint64_t)(2 * layer + kind), train, true);
     if (dr.thr16) act_used[kind][layer] = dr;
+    return dr;
+  }
+  // Classification-head dropout (the two F.dropout calls of HF 3.0.2 BartClassificationHead: on the head's input and on its tanh output): the third
+  // run-time setting (kmb_set_classif_dropout; kmb_config does not carry it).  head_run masks the gathered input and a copy of the hidden
+  // activations with the row kernel of heads.hip and hands the same KmbDrop to the two data-gradient GEMMs' epilogues, so backward redraws nothing.
+  // cls_used[head][which]: what the LAST training forward launched with (zeros: none, or the head had no rows), for kmb_classif_dropout_site.
+  static constexpr uint64_t CLS_SITE_BASE = 0x50000000ull;
+  float cls_p = 0.f;
+  KmbDrop cls_used[3][2] = {{{0u, 0u, 1.f}, {0u, 0u, 1.f}}, {{0u, 0u, 1.f}, {0u, 0u, 1.f}}, {{0u, 0u, 1.f}, {0u, 0u, 1.f}}};
+  KmbDrop cls_drop_site(int head, int which, bool train) {
+    const KmbDrop dr = site_drop(cls_p, CLS_SITE_BASE + (uint64_t)(2 * head + which), train, true);
+    if (dr.thr16) cls_used[head][which] = dr;
     return dr;
   }
   bf16_t* wb(size_t off) const { return kmbi::g_f32 ? reinterpret_cast<bf16_t*>(P + off) : PB + off; }   // GEMM B operand: bf16 mirror (fp32 master in validation mode)

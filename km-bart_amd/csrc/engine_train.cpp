@@ -139,6 +139,7 @@ size_t layout_train(const kmb_handle* h, char* base, size_t cap, int B, int S, i
     // run_wgrad picks S <= 512 / tiles128 slices: S x M x N stays under 512 x 128 x 128 floats (+ edge-tile slack)
     L.head_slab_floats = (size_t)9 << 20;
     L.head_slab = bp.take<float>(L.head_slab_floats);
+    L.hyd = bp.act(n * d);   // (carved last: every other buffer stays where it was)
   }
   if (out) *out = std::move(L);
   return bp.used();
@@ -251,11 +252,16 @@ int self_attn_backward(kmb_handle* h, const AttnP& A, int H, const bf16_t* x, bf
 }
 
 
-// One BartClassificationHead (dense -> tanh -> out_proj, classif_dropout = 0) on gathered decoder rows, its loss
-// and, with need_grad, all of its gradients: parameter gradients go to the arena, the gradient wrt the decoder
-// states is scatter-added (fp32) into h->tl.dhead.  Reference src/model/model.py:133-158, :248-289.
+// One BartClassificationHead (dropout -> dense -> tanh -> dropout -> out_proj) on gathered decoder rows, its loss and, with need_grad, all of
+// its gradients: parameter gradients go to the arena, the gradient wrt the decoder states is scatter-added (fp32) into h->tl.dhead.
+// Reference src/model/model.py:133-158, :248-289.
+// classif_dropout (train, kmb_set_classif_dropout): with m_in [n, d_in] and m_h [n, d] holding keep * scale or 0, logits = out_proj(m_h . t),
+// t = tanh(dense(m_in . x)).  hx holds m_in . x (the gather applies the mask; one launch for the relation head's two halves), hy the unmasked t,
+// hyd = m_h . t.  Backward: d_out_w = dlogits^T hyd; d_pre = m_h . (dlogits W_o) . (1 - t^2) -- the act 4 epilogue multiplies by 1 - hy^2 and
+// then applies the hidden site's mask; d_dense_w = d_pre^T hx; d_x = m_in . (d_pre W_d) -- the input site's mask in that GEMM's epilogue.
+// Without it (both thresholds zero) the launches are exactly the ones of a build that never had the setting.
 int head_run(kmb_handle* h, int k, const bf16_t* hdec, int n, const int32_t* rows_a, const int32_t* rows_b,
-             const float* soft_targets, const int64_t* labels, float factor, bool need_grad, float* loss_out,
+             const float* soft_targets, const int64_t* labels, float factor, bool train, bool need_grad, float* loss_out,
              hipStream_t s) {
   const HeadP& H = h->head[k];
   const int d = h->d, din = H.d_in, C = H.C;
@@ -266,13 +272,23 @@ int head_run(kmb_handle* h, int k, const bf16_t* hdec, int n, const int32_t* row
     return 0;
   }
   if (n > h->head_rows_cap || h->tl.hx == nullptr) return fail("head rows %d exceed the reserved %d (kmb_reserve_head_rows)", n, h->head_rows_cap);
+  const KmbDrop din_dr = h->cls_drop_site(k, 0, train), dh_dr = h->cls_drop_site(k, 1, train);
   // gather: [n, d] (or [n, 2d] = object | subject for the relation head)
-  HIPCHK(kmb_gather_rows_bf16_launch(hdec, d, rows_a, h->tl.hx, din, n, d, s));
-  if (rows_b) HIPCHK(kmb_gather_rows_bf16_launch(hdec, d, rows_b, h->tl.hx + d, din, n, d, s));
+  if (din_dr.thr16) {
+    HIPCHK(kmb_gather_rows_drop_bf16_launch(hdec, d, rows_a, rows_b, h->tl.hx, din, n, d, din_dr, s));
+  } else {
+    HIPCHK(kmb_gather_rows_bf16_launch(hdec, d, rows_a, h->tl.hx, din, n, d, s));
+    if (rows_b) HIPCHK(kmb_gather_rows_bf16_launch(hdec, d, rows_b, h->tl.hx + d, din, n, d, s));
+  }
   KmbGemm g = lin_fwd(h->tl.hx, din, h->wb(H.dw), h->pf(H.db), n, d, din);
   g.act = 3; g.out_bf16 = h->tl.hy; g.ld_out_bf16 = d;
   KCHK(run_gemm(g, s));
-  g = lin_fwd(h->tl.hy, d, h->wb(H.ow), h->pf(H.ob), n, C, d);
+  const bf16_t* hyo = h->tl.hy;   // what out_proj reads
+  if (dh_dr.thr16) {
+    HIPCHK(kmb_gather_rows_drop_bf16_launch(h->tl.hy, d, nullptr, nullptr, h->tl.hyd, d, n, d, dh_dr, s));
+    hyo = h->tl.hyd;
+  }
+  g = lin_fwd(hyo, d, h->wb(H.ow), h->pf(H.ob), n, C, d);
   g.out_f32 = h->tl.hlg; g.ld_out_f32 = Cpad;
   KCHK(run_gemm(g, s));
   if (soft_targets) {  // F.kl_div(log_softmax(pred), target, reduction='batchmean') * factor
@@ -286,15 +302,17 @@ int head_run(kmb_handle* h, int k, const bf16_t* hdec, int n, const int32_t* row
   if (!need_grad) return 0;
   // out_proj
   KCHK(bias_grad(h, h->tl.hdlg, Cpad, n, C, h->gf(H.ob), s));
-  KCHK(run_wgrad(h, lin_wgrad(h->tl.hdlg, Cpad, h->tl.hy, d, h->gf(H.ow), n, C, d, 0.f), s, h->tl.head_slab, h->tl.head_slab_floats));
+  KCHK(run_wgrad(h, lin_wgrad(h->tl.hdlg, Cpad, hyo, d, h->gf(H.ow), n, C, d, 0.f), s, h->tl.head_slab, h->tl.head_slab_floats));
   g = lin_dgrad(h->tl.hdlg, Cpad, h->wb(H.ow), n, Cpad, d);   // reduction over the padded class dim (pad columns are zero)
   g.N = d; g.K = Cpad; g.act = 4; g.aux = h->tl.hy; g.ld_aux = d; g.out_bf16 = h->tl.hdy; g.ld_out_bf16 = d;
+  if (dh_dr.thr16) { g.drop_thr16 = dh_dr.thr16; g.drop_seed = dh_dr.seed; g.drop_scale = dh_dr.scale; }   // behind the 1 - aux^2 multiply
   KCHK(run_gemm(g, s));
   // dense
   KCHK(bias_grad(h, h->tl.hdy, d, n, d, h->gf(H.db), s));
   KCHK(run_wgrad(h, lin_wgrad(h->tl.hdy, d, h->tl.hx, din, h->gf(H.dw), n, d, din, 0.f), s, h->tl.head_slab, h->tl.head_slab_floats));
   g = lin_dgrad(h->tl.hdy, d, h->wb(H.dw), n, d, din);
   g.out_bf16 = h->tl.hdx; g.ld_out_bf16 = din;
+  if (din_dr.thr16) { g.drop_thr16 = din_dr.thr16; g.drop_seed = din_dr.seed; g.drop_scale = din_dr.scale; }
   KCHK(run_gemm(g, s));
   HIPCHK(kmb_scatter_add_rows_launch(h->tl.hdx, din, rows_a, h->tl.dhead, n, d, s));
   if (rows_b) HIPCHK(kmb_scatter_add_rows_launch(h->tl.hdx + d, din, rows_b, h->tl.dhead, n, d, s));
@@ -544,6 +562,7 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
     h->step += 1;
     for (auto& v : h->attn_used) std::fill(v.begin(), v.end(), KmbDrop{0u, 0u, 1.f});   // what THIS training forward uses is recorded as it goes
     for (auto& v : h->act_used) std::fill(v.begin(), v.end(), KmbDrop{0u, 0u, 1.f});
+    for (auto& hd : h->cls_used) for (KmbDrop& u : hd) u = KmbDrop{0u, 0u, 1.f};
   }
   const bool tr = train != 0;
   const float eps = h->cfg.layer_norm_eps;
@@ -612,13 +631,13 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
     if (bt.labels) HIPCHK(kmb_mean_rows_launch(h->tl.loss_dev, 1, extra->lm_factor, 1.f, h->tl.losses5 + 1, s));
     if (h->head[0].on)
       KCHK(head_run(h, 0, hdec, extra->n_mrm, extra->mrm_rows, nullptr, extra->mrm_targets, nullptr, extra->mrm_factor,
-                    need_grad != 0, h->tl.losses5 + 2, s));
+                    tr, need_grad != 0, h->tl.losses5 + 2, s));
     if (h->head[1].on)
       KCHK(head_run(h, 1, hdec, extra->n_attr, extra->attr_rows, nullptr, nullptr, extra->attr_labels,
-                    extra->attr_factor, need_grad != 0, h->tl.losses5 + 3, s));
+                    extra->attr_factor, tr, need_grad != 0, h->tl.losses5 + 3, s));
     if (h->head[2].on)
       KCHK(head_run(h, 2, hdec, extra->n_rel, extra->rel_obj_rows, extra->rel_subj_rows, nullptr, extra->rel_labels,
-                    extra->rel_factor, need_grad != 0, h->tl.losses5 + 4, s));
+                    extra->rel_factor, tr, need_grad != 0, h->tl.losses5 + 4, s));
     if (need_grad && any) HIPCHK(kmb_add_f32_into_bf16_launch(h->tl.dhdec, h->tl.dhead, (size_t)Md * d, s));
     HIPCHK(kmb_mean_rows_launch(h->tl.losses5 + 1, 4, 1.f, 1.f, h->tl.losses5, s));
     if (extra->losses_out)

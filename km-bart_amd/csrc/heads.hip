@@ -61,6 +61,39 @@ __global__ __launch_bounds__(256) void gather_rows_bf16_kernel(const bf16_t* __r
   }
 }
 
+// The gather plus a dropout mask (classif_dropout: both F.dropout calls of a BartClassificationHead go through here):
+//   dst[i][c]        = m(i, c) * src[ia(i)][c],         c < cols, ia(i) = idx_a[i], or i itself when idx_a is null (identity rows)
+//   dst[i][cols + c] = m(i, cols + c) * src[idx_b[i]][c]   when idx_b is not null: the relation head's object | subject row in one launch
+// m(row, col) = drop_keep(seed, row, col) ? scale : 0 at the DESTINATION coordinate, so the two halves draw from one [rows, 2 cols] mask and
+// kmb_op_dropout_mask(seed, thr16 / 65536, rows, written columns) rebuilds it.  Per 16-byte chunk four hashes (one per column pair); kept values are
+// multiplied in fp32 and rounded once to bf16, dropped ones are +0.  With identity rows (both index arrays null) dst may be src: a thread reads
+// its chunk before it writes it and no other thread touches that chunk; the launcher refuses dst == src with an index array.
+__global__ __launch_bounds__(256) void gather_rows_drop_bf16_kernel(const bf16_t* src, int src_ld,
+                                                                    const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_b,
+                                                                    bf16_t* dst, int dst_ld, int rows, int cols, KmbDrop dr) {
+  const int chunks = cols >> 3;
+  const int per_row = idx_b != nullptr ? 2 * chunks : chunks;
+  const size_t total = (size_t)rows * per_row;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int r = (int)(i / per_row), cc = (int)(i % per_row);
+    const bool second = cc >= chunks;
+    const int c = (second ? cc - chunks : cc) * 8;
+    const int sr = second ? idx_b[r] : (idx_a != nullptr ? idx_a[r] : r);
+    const int dcol = second ? cols + c : c;
+    float v[8];
+    unpack8(*reinterpret_cast<const u32x4*>(src + (size_t)sr * src_ld + c), v);
+    const uint32_t rowterm = (uint32_t)r * 0x9E3779B1u;
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+      bool k0, k1;
+      drop_keep_pair(dr.seed, rowterm, drop_colterm((uint32_t)(dcol + e)), dr.thr16, k0, k1);
+      v[e] = k0 ? v[e] * dr.scale : 0.f;
+      v[e + 1] = k1 ? v[e + 1] * dr.scale : 0.f;
+    }
+    *reinterpret_cast<u32x4*>(dst + (size_t)r * dst_ld + dcol) = pack8(v);
+  }
+}
+
 // acc[idx[i]*cols + c] += src[i*src_ld + c]   (fp32 atomics; one wave per source row, 256-B contiguous per instruction)
 __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const bf16_t* __restrict__ src, int src_ld,
                                                                const int32_t* __restrict__ idx, float* __restrict__ acc,
@@ -115,6 +148,28 @@ hipError_t kmb_gather_rows_bf16_launch(const bf16_t* src, int src_ld, const int3
   if (rows <= 0) return hipSuccess;
   if ((cols & 7) || (src_ld & 7) || (dst_ld & 7)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gather_rows_bf16_kernel, dim3(grid_for((size_t)rows * (cols >> 3))), dim3(256), 0, stream, src, src_ld, idx, dst, dst_ld, rows, cols);
+  return hipGetLastError();
+}
+hipError_t kmb_gather_rows_drop_bf16_launch(const bf16_t* src, int src_ld, const int32_t* idx_a, const int32_t* idx_b, bf16_t* dst,
+                                            int dst_ld, int rows, int cols, KmbDrop drop, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
+  const int halves = idx_b != nullptr ? 2 : 1;
+  if (cols <= 0 || (cols & 7) || (src_ld & 7) || (dst_ld & 7) || src_ld < cols || dst_ld < halves * cols || drop.thr16 > 65535u)
+    return hipErrorInvalidValue;
+  if (idx_a == nullptr && idx_b != nullptr) return hipErrorInvalidValue;   // identity rows beside a gathered half: nothing asks for it
+  if (dst == src && idx_a != nullptr) return hipErrorInvalidValue;         // in place only with identity rows: a gather would race
+  if (drop.thr16 == 0u) {   // no mask: the bits move untouched -- the plain gather (once per half), or a strided copy for identity rows
+    if (idx_a == nullptr) {
+      if (dst == src) return hipSuccess;
+      return hipMemcpy2DAsync(dst, (size_t)dst_ld * sizeof(bf16_t), src, (size_t)src_ld * sizeof(bf16_t), (size_t)cols * sizeof(bf16_t),
+                              (size_t)rows, hipMemcpyDeviceToDevice, stream);
+    }
+    hipError_t e = kmb_gather_rows_bf16_launch(src, src_ld, idx_a, dst, dst_ld, rows, cols, stream);
+    if (e == hipSuccess && idx_b != nullptr) e = kmb_gather_rows_bf16_launch(src, src_ld, idx_b, dst + cols, dst_ld, rows, cols, stream);
+    return e;
+  }
+  hipLaunchKernelGGL(gather_rows_drop_bf16_kernel, dim3(grid_for((size_t)rows * halves * (cols >> 3))), dim3(256), 0, stream, src, src_ld,
+                     idx_a, idx_b, dst, dst_ld, rows, cols, drop);
   return hipGetLastError();
 }
 hipError_t kmb_scatter_add_rows_launch(const bf16_t* src, int src_ld, const int32_t* idx, float* acc, int rows, int cols,

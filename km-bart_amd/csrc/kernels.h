@@ -208,6 +208,11 @@ hipError_t kmb_kl_div_launch(const float* logits, int ld, int C, const float* ta
                              float grad_scale, float* loss_rows, bf16_t* dlogits, int ldd, hipStream_t stream);
 hipError_t kmb_gather_rows_bf16_launch(const bf16_t* src, int src_ld, const int32_t* idx, bf16_t* dst, int dst_ld,
                                        int rows, int cols, hipStream_t stream);
+// the gather with a dropout mask at the destination coordinate; idx_a null: identity rows (idx_b must then be null too; only then may dst be
+// src); idx_b not null: a second row gathered into columns [cols, 2 cols) of the same destination row; drop.thr16 == 0 moves the bits untouched
+// (the plain gather, or a strided copy for identity rows)
+hipError_t kmb_gather_rows_drop_bf16_launch(const bf16_t* src, int src_ld, const int32_t* idx_a, const int32_t* idx_b, bf16_t* dst,
+                                            int dst_ld, int rows, int cols, KmbDrop drop, hipStream_t stream);
 hipError_t kmb_scatter_add_rows_launch(const bf16_t* src, int src_ld, const int32_t* idx, float* acc, int rows, int cols,
                                        hipStream_t stream);
 hipError_t kmb_add_f32_into_bf16_launch(bf16_t* y, const float* a, size_t n, hipStream_t stream);

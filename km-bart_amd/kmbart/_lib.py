@@ -110,6 +110,8 @@ PROTOTYPES = {
     "kmb_attention_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
     "kmb_set_activation_dropout": (C.c_int, [c_p, f32]),
     "kmb_activation_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
+    "kmb_set_classif_dropout": (C.c_int, [c_p, f32]),
+    "kmb_classif_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
     "kmb_abi_sizeof_attn": (C.c_int, []),
     "kmb_bucket_count": (C.c_int, [c_p]),
     "kmb_bucket_range": (C.c_int, [c_p, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
@@ -223,6 +225,7 @@ PROTOTYPES = {
     "kmb_op_ce_dgrad_finish": (C.c_int, [c_p, C.c_int, i64, c_p, c_p, C.c_int, C.c_int, c_p]),
     "kmb_op_kl_div": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, c_p, c_p, C.c_int, c_p]),
     "kmb_op_gather_rows_bf16": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p]),
+    "kmb_op_gather_rows_drop_bf16": (C.c_int, [c_p, C.c_int, c_p, c_p, c_p, C.c_int, C.c_int, C.c_int, C.POINTER(KmbDrop), c_p]),
     "kmb_op_scatter_add_rows": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, c_p]),
     "kmb_op_add_f32_into_bf16": (C.c_int, [c_p, c_p, i64, c_p]),
     "kmb_op_mean_rows": (C.c_int, [c_p, C.c_int, f32, f32, c_p, c_p]),

@@ -85,8 +85,6 @@ class Engine:
         c.activation_dropout = 0.0   # likewise (set_activation_dropout)
         c.layer_norm_eps = 1e-5
         if with_heads:  # MultiModalBartForPreTraining (reference src/model/model.py:133-158)
-            if float(getattr(config, "classif_dropout", 0.0)) != 0.0:
-                raise NotImplementedError("classif_dropout != 0 is not implemented (pretrain_base.json uses 0.0)")
             c.num_labels = int(config.num_labels)
             c.num_attributes = int(config.num_attributes)
             c.num_relations = int(config.num_relations)
@@ -96,6 +94,7 @@ class Engine:
         self.h = h
         self.set_attention_dropout(float(getattr(config, "attention_dropout", 0.0)))
         self.set_activation_dropout(float(getattr(config, "activation_dropout", 0.0)))
+        self.set_classif_dropout(float(getattr(config, "classif_dropout", 0.0)))   # (without heads there is nothing to drop: no effect)
         with torch.cuda.device(self.device):
             n = self.lib.kmb_arena_elems(h)
             nb = self.lib.kmb_bf16_arena_elems(h)
@@ -182,6 +181,20 @@ class Engine:
         dropout.  kmb_op_dropout_mask(seed, thr16 / 65536, rows, F) rebuilds the mask (rows = B * S encoder, B * T decoder)."""
         thr, seed = C.c_uint32(0), C.c_uint32(0)
         check(self.lib.kmb_activation_dropout_site(self.h, int(kind), int(layer), C.byref(thr), C.byref(seed)))
+        return int(thr.value), int(seed.value)
+
+    def set_classif_dropout(self, p):
+        """Dropout probability of the classification heads (config.classif_dropout: a head's input and its tanh output), from the
+        next training-mode pre-training forward on; eval forwards, score() and generation never drop."""
+        check(self.lib.kmb_set_classif_dropout(self.h, C.c_float(float(p))))
+        self.classif_dropout = float(p)
+
+    def classif_dropout_site(self, head, which):
+        """(thr16, seed) the last training forward used at a head site (head 0 masked-region, 1 attribute, 2 relation; which 0 the
+        head's input, 1 its hidden activations); (0, 0) when it ran without dropout, the head had no rows or does not exist.
+        kmb_op_dropout_mask(seed, thr16 / 65536, n, d_in or d_model) rebuilds the mask over the head's n gathered rows."""
+        thr, seed = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.kmb_classif_dropout_site(self.h, int(head), int(which), C.byref(thr), C.byref(seed)))
         return int(thr.value), int(seed.value)
 
     # ---- workspace --------------------------------------------------------------------------
