@@ -164,6 +164,11 @@ typedef struct KmbDecodeBlock {
 
 typedef struct KmbDrop { uint32_t thr16; uint32_t seed; float scale; } KmbDrop;
 typedef struct KmbAdamW { double lr, beta1, beta2, eps, weight_decay; int32_t step; int32_t correct_bias; float grad_scale; } KmbAdamW;
+/* The device record of a clipped / guarded optimizer step (kmb_clip_finish writes it, kmb_adamw_step_dev reads it):
+ * norm = the global L2 norm of the gradients before clipping, gradient scaling included; coef = min(1, max_norm / (norm + 1e-6));
+ * step_size = lr * sqrt(1 - beta2^steps) / (1 - beta1^steps); applied = 1 if this step updates; steps / skipped = applied and
+ * skipped steps so far.  The bias-correction step count of such a step is `steps`, NOT KmbAdamW.step. */
+typedef struct KmbStepState { float norm, coef, step_size; int32_t applied, steps, skipped; } KmbStepState;
 
 const char* kmb_last_error(void);
 int kmb_version(void);
@@ -291,6 +296,27 @@ int kmb_backward(kmb_handle* h, float loss_scale, void* stream);
 int kmb_backward_dev(kmb_handle* h, const float* loss_scale_dev, void* stream);
 /* transformers.AdamW.step (vcg_train.py:100, src/training.py:139,143) over [offset, offset+count) */
 int kmb_adamw_step(kmb_handle* h, const KmbAdamW* hp, int64_t offset, int64_t count, void* stream);
+/* ---- clipped / guarded step: global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, L2) and the skip of a step whose
+ * gradients are not finite (what GradScaler.step does), decided ON THE DEVICE before any parameter moves.
+ *   kmb_grad_sumsq (one call per contiguous piece, each into its own block of partial slots)  ->  kmb_clip_finish (once)  ->
+ *   kmb_adamw_step_dev (per piece)
+ * The step-state buffer is the caller's: a KmbStepState record followed (at byte 64) by double partial sums, kmb_step_state_bytes in all.
+ * It must NOT live in the workspace (the bias-correction step count has to survive whatever rewrites that); kmb_bind_step_state
+ * zeroes it (synchronously).  Nothing here synchronises the host except the bind. */
+int64_t kmb_step_state_bytes(const kmb_handle* h);
+int kmb_bind_step_state(kmb_handle* h, void* buf, int64_t bytes);
+/* partial sums of (G[i] * grad_scale)^2 over [offset, offset + count) (offset a multiple of 4) into slots [slot0, slot0 +
+ * kmb_op_grad_sumsq_slots(count)); the sums are doubles, one per workgroup, no atomics: the same pieces give the same bits */
+int kmb_grad_sumsq(kmb_handle* h, int64_t offset, int64_t count, float grad_scale, int32_t slot0, void* stream);
+/* sums slots [0, nslots) and writes the record; max_norm <= 0: no clipping; hp: lr, betas and correct_bias are read (hp->step is not) */
+int kmb_clip_finish(kmb_handle* h, const KmbAdamW* hp, float max_norm, int32_t skip_nonfinite, int32_t nslots, void* stream);
+/* kmb_adamw_step under the record: nothing moves when applied == 0; otherwise gradients are scaled by hp->grad_scale * coef and the
+ * record's step_size is used.  Same range rules and the same image-weight re-pad as kmb_adamw_step. */
+int kmb_adamw_step_dev(kmb_handle* h, const KmbAdamW* hp, int64_t offset, int64_t count, void* stream);
+/* asynchronous copy of the record to host_record (page-locked memory); the caller synchronises the stream before reading */
+int kmb_step_state_read(kmb_handle* h, KmbStepState* host_record, void* stream);
+/* sets the record's applied-step count (loading a checkpoint), in stream order */
+int kmb_step_state_set_steps(kmb_handle* h, int32_t steps, void* stream);
 /* status word written by device-side input validation (bit 0: #<img_feat> ids != #region rows) */
 int kmb_read_status(kmb_handle* h, int32_t* status_host, void* stream);
 /* The same without the synchronisation: the status word is copied to `status_host` (page-locked memory) in stream order; the
@@ -667,6 +693,13 @@ int kmb_op_add_f32_into_bf16(kmb_bf16* y, const float* a, int64_t n, void* strea
 int kmb_op_mean_rows(const float* rows, int n, float factor, float denom, float* out, void* stream);
 int kmb_op_adamw(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16, int64_t n, const KmbAdamW* hp,
                  void* stream);
+/* the clipped / guarded step's three kernels on raw pointers (see kmb_grad_sumsq): partials are doubles, g is 16-byte aligned */
+int kmb_op_grad_sumsq(const float* g, int64_t n, float grad_scale, double* partials, int32_t slot0, void* stream);
+int kmb_op_grad_sumsq_slots(int64_t n);   /* min(ceil(n / 1024), 1024): a function of n alone */
+int kmb_op_clip_finish(const double* partials, int32_t nslots, float max_norm, int32_t skip_nonfinite, const KmbAdamW* hp,
+                       KmbStepState* state, void* stream);
+int kmb_op_adamw_dev(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16, int64_t n, const KmbAdamW* hp,
+                     const KmbStepState* state, void* stream);
 int kmb_op_cast_bf16(const float* x, kmb_bf16* y, int64_t n, void* stream);
 /* keep[i] = 1 if the dropout generator keeps element (row, col) for this site seed / probability */
 int kmb_op_dropout_mask(uint32_t seed, float p, int rows, int cols, uint8_t* keep, void* stream);

@@ -279,6 +279,22 @@ int kmb_op_adamw(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16,
                  void* stream) {
   return hipfail(kmb_adamw_launch(p, g, m, v, p_bf16, (size_t)n, *hp, (hipStream_t)stream), "adamw");
 }
+int kmb_op_grad_sumsq_slots(int64_t n) { return n > 0 ? kmb_grad_sumsq_slots((size_t)n) : 0; }
+int kmb_op_grad_sumsq(const float* g, int64_t n, float grad_scale, double* partials, int32_t slot0, void* stream) {
+  if (!g || !partials || n <= 0 || slot0 < 0) return kmb_set_error("kmb_op_grad_sumsq: bad arguments");
+  if ((uintptr_t)g & 15) return kmb_set_error("kmb_op_grad_sumsq: g must be 16-byte aligned");
+  return hipfail(kmb_grad_sumsq_launch(g, (size_t)n, grad_scale, partials + slot0, (hipStream_t)stream), "grad_sumsq");
+}
+int kmb_op_clip_finish(const double* partials, int32_t nslots, float max_norm, int32_t skip_nonfinite, const KmbAdamW* hp,
+                       KmbStepState* state, void* stream) {
+  if (!partials || nslots <= 0 || !hp || !state) return kmb_set_error("kmb_op_clip_finish: bad arguments");
+  return hipfail(kmb_clip_finish_launch(partials, nslots, max_norm, skip_nonfinite, *hp, state, (hipStream_t)stream), "clip_finish");
+}
+int kmb_op_adamw_dev(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16, int64_t n, const KmbAdamW* hp,
+                     const KmbStepState* state, void* stream) {
+  if (!hp || !state) return kmb_set_error("kmb_op_adamw_dev: hp and state are required");
+  return hipfail(kmb_adamw_dev_launch(p, g, m, v, p_bf16, (size_t)n, *hp, state, (hipStream_t)stream), "adamw_dev");
+}
 int kmb_op_cast_bf16(const float* x, kmb_bf16* y, int64_t n, void* stream) {
   return hipfail(kmb_cast_f32_bf16_launch(x, y, (size_t)n, (hipStream_t)stream), "cast");
 }

@@ -55,9 +55,11 @@ int comm_ready(const kmb_handle* h, const char* who) {
 
 // the optimizer update of arena range [off, off + cnt) on stream s (kmb_adamw_step and the fused step of the exchange); the padded
 // image-weight mirror lives outside the flat mirror
-int adamw_range(kmb_handle* h, const KmbAdamW& hp, size_t off, size_t cnt, hipStream_t s) {
+// state: the device record of a clipped / guarded step (kmb_adamw_step_dev), null for the host-state step
+int adamw_range(kmb_handle* h, const KmbAdamW& hp, size_t off, size_t cnt, hipStream_t s, const KmbStepState* state = nullptr) {
   if (!h->M1 || !h->M2) return fail("fused optimizer step: the moment arenas are not bound");
-  HIPCHK(kmb_adamw_launch(h->P + off, h->G + off, h->M1 + off, h->M2 + off, h->PB + off, cnt, hp, s));
+  if (state) HIPCHK(kmb_adamw_dev_launch(h->P + off, h->G + off, h->M1 + off, h->M2 + off, h->PB + off, cnt, hp, state, s));
+  else HIPCHK(kmb_adamw_launch(h->P + off, h->G + off, h->M1 + off, h->M2 + off, h->PB + off, cnt, hp, s));
   h->mirror_version++;
   const size_t iw0 = h->img_w, iw1 = h->img_w + (size_t)h->d * h->Fin;
   if (off < iw1 && off + cnt > iw0)
@@ -65,6 +67,22 @@ int adamw_range(kmb_handle* h, const KmbAdamW& hp, size_t off, size_t cnt, hipSt
   return 0;
 }
 
+// ---- clipped / guarded step (include/kmbart.h).  Partial slots: a piece of n elements takes kmb_grad_sumsq_slots(n); the buffer holds enough for
+// any cut of the arena into parameter runs x buckets (a run of parameters needs at most the sum of its parameters' slots plus one per parameter for
+// the alignment gap in front of it; a bucket boundary adds at most one piece).
+constexpr size_t STEP_PARTIALS_AT = 64;   // byte offset of the partial sums behind the record
+int step_slots_cap(const kmb_handle* h) {
+  size_t n = h->buckets.size();
+  for (const auto& p : h->params) n += (size_t)kmb_grad_sumsq_slots((size_t)p.rows * p.cols) + 1;
+  return (int)n;
+}
+int step_ready(const kmb_handle* h, const char* who) {
+  if (!h->step_state) return fail("%s: no step-state buffer (call kmb_bind_step_state first)", who);
+  if (!h->P || !h->G || !h->M1 || !h->M2) return fail("%s: arenas are not bound", who);
+  const char *a = (const char*)h->step_state, *b = (const char*)(h->step_partials + h->step_slots);
+  if (h->ws && a < h->ws + h->ws_bytes && b > h->ws) return fail("%s: the step-state buffer lies inside the workspace", who);
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -74,6 +92,60 @@ int kmb_adamw_step(kmb_handle* h, const KmbAdamW* hp, int64_t offset, int64_t co
   if (offset < 0 || count < 0 || (size_t)(offset + count) > h->arena) return fail("kmb_adamw_step: range out of the arena");
   if (offset & 7) return fail("kmb_adamw_step: offset must be a multiple of 8 elements");
   return adamw_range(h, *hp, (size_t)offset, (size_t)count, (hipStream_t)stream);
+}
+
+// ---- clipped / guarded step
+int64_t kmb_step_state_bytes(const kmb_handle* h) { return (int64_t)(STEP_PARTIALS_AT + sizeof(double) * (size_t)step_slots_cap(h)); }
+
+int kmb_bind_step_state(kmb_handle* h, void* buf, int64_t bytes) {
+  static_assert(sizeof(KmbStepState) == 24 && sizeof(KmbStepState) <= STEP_PARTIALS_AT, "KmbStepState is six 4-byte fields");
+  if (!buf || bytes < kmb_step_state_bytes(h)) return fail("kmb_bind_step_state: the buffer is smaller than kmb_step_state_bytes");
+  if ((uintptr_t)buf & 15) return fail("kmb_bind_step_state: the buffer must be 16-byte aligned");
+  if (h->ws && (char*)buf < h->ws + h->ws_bytes && (char*)buf + bytes > h->ws) return fail("kmb_bind_step_state: the buffer lies inside the workspace");
+  HIPCHK(hipMemset(buf, 0, (size_t)kmb_step_state_bytes(h)));
+  h->step_state = (KmbStepState*)buf;
+  h->step_partials = (double*)((char*)buf + STEP_PARTIALS_AT);
+  h->step_slots = step_slots_cap(h);
+  return 0;
+}
+
+int kmb_grad_sumsq(kmb_handle* h, int64_t offset, int64_t count, float grad_scale, int32_t slot0, void* stream) {
+  KCHK(step_ready(h, "kmb_grad_sumsq"));
+  if (offset < 0 || count < 0 || (size_t)(offset + count) > h->arena) return fail("kmb_grad_sumsq: range out of the arena");
+  if (offset & 3) return fail("kmb_grad_sumsq: offset must be a multiple of 4 elements");
+  if (slot0 < 0 || slot0 + (count > 0 ? kmb_grad_sumsq_slots((size_t)count) : 0) > h->step_slots) return fail("kmb_grad_sumsq: slots out of the step-state buffer");
+  HIPCHK(kmb_grad_sumsq_launch(h->G + offset, (size_t)count, grad_scale, h->step_partials + slot0, (hipStream_t)stream));
+  return 0;
+}
+
+int kmb_clip_finish(kmb_handle* h, const KmbAdamW* hp, float max_norm, int32_t skip_nonfinite, int32_t nslots, void* stream) {
+  KCHK(step_ready(h, "kmb_clip_finish"));
+  if (!hp) return fail("kmb_clip_finish: hp is required");
+  if (nslots <= 0 || nslots > h->step_slots) return fail("kmb_clip_finish: nslots out of the step-state buffer");
+  HIPCHK(kmb_clip_finish_launch(h->step_partials, nslots, max_norm, skip_nonfinite, *hp, h->step_state, (hipStream_t)stream));
+  return 0;
+}
+
+int kmb_adamw_step_dev(kmb_handle* h, const KmbAdamW* hp, int64_t offset, int64_t count, void* stream) {
+  KCHK(step_ready(h, "kmb_adamw_step_dev"));
+  if (!hp) return fail("kmb_adamw_step_dev: hp is required");
+  if (offset < 0 || count < 0 || (size_t)(offset + count) > h->arena) return fail("kmb_adamw_step_dev: range out of the arena");
+  if (offset & 7) return fail("kmb_adamw_step_dev: offset must be a multiple of 8 elements");
+  return adamw_range(h, *hp, (size_t)offset, (size_t)count, (hipStream_t)stream, h->step_state);
+}
+
+int kmb_step_state_read(kmb_handle* h, KmbStepState* host_record, void* stream) {
+  if (!h->step_state) return fail("kmb_step_state_read: no step-state buffer (call kmb_bind_step_state first)");
+  if (!host_record) return fail("kmb_step_state_read: host_record is required");
+  HIPCHK(hipMemcpyAsync(host_record, h->step_state, sizeof(KmbStepState), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  return 0;
+}
+
+int kmb_step_state_set_steps(kmb_handle* h, int32_t steps, void* stream) {
+  if (!h->step_state) return fail("kmb_step_state_set_steps: no step-state buffer (call kmb_bind_step_state first)");
+  if (steps < 0) return fail("kmb_step_state_set_steps: steps must not be negative");
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&h->step_state->steps, steps, 1, (hipStream_t)stream));
+  return 0;
 }
 
 int kmb_comm_unique_id(void* id_host) {

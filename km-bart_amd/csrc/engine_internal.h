@@ -180,6 +180,8 @@ struct kmb_handle {
   bf16_t* PB = nullptr;
   bf16_t* imgw_pad = nullptr;       // inside the bf16 arena tail: [d, Fpad]
   char* ws = nullptr; size_t ws_bytes = 0;
+  // the clipped / guarded optimizer step's device record and partial sums (kmb_bind_step_state): the caller's buffer, outside the workspace
+  KmbStepState* step_state = nullptr; double* step_partials = nullptr; int step_slots = 0;
   uint64_t seed = 0x5eedULL; uint64_t step = 0;
   bool fp32 = false;    // kmb_set_precision(1): fp32 validation forward
   bool have_hdec = false;   // xd[Ld] of the last forward is still in the workspace (kmb_last_logits)

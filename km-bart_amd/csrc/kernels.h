@@ -170,6 +170,15 @@ hipError_t kmb_logsoftmax_topk_launch(const float* logits, int ldv, int V, int r
 // transformers-3.0.2 AdamW on a flat fp32 arena; also refreshes the bf16 mirror of the parameters
 hipError_t kmb_adamw_launch(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n,
                             KmbAdamW h, hipStream_t stream);
+// the same under a device record (KmbStepState): skipped when applied == 0, else grad_scale * coef and the record's step size
+hipError_t kmb_adamw_dev_launch(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n, KmbAdamW h,
+                                const KmbStepState* state, hipStream_t stream);
+// global gradient norm: per-workgroup double sums of (g * grad_scale)^2 into partials[0, kmb_grad_sumsq_slots(n)), then ONE
+// workgroup that sums nslots of them and writes the step's record
+int kmb_grad_sumsq_slots(size_t n);
+hipError_t kmb_grad_sumsq_launch(const float* g, size_t n, float grad_scale, double* partials, hipStream_t stream);
+hipError_t kmb_clip_finish_launch(const double* partials, int nslots, float max_norm, int skip_nonfinite, KmbAdamW h,
+                                  KmbStepState* state, hipStream_t stream);
 hipError_t kmb_cast_f32_bf16_launch(const float* x, bf16_t* y, size_t n, hipStream_t stream);
 hipError_t kmb_fill_f32_launch(float* x, float v, size_t n, hipStream_t stream);
 // y[r*ldy + c] = bf16(x[r*ldx + c]) for c < cols, zero for cols <= c < ldy

@@ -7,11 +7,19 @@
 namespace {
 
 // 28 B/param: read p,g,m,v (16) + write p,m,v (12) + 2 B bf16 mirror
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    bf16_t* __restrict__ pb, size_t n4, size_t n, float lr,
-                                                    float b1, float b2, float omb1, float omb2, float eps, float wd,
-                                                    float step_size, float gscale) {
+// DEV: the step's decision comes from the device record clip_finish_kernel wrote (KmbStepState): nothing is touched when the step
+// is skipped, otherwise the gradient scale carries the clip coefficient and the step size is the record's.  The host-state
+// instance (adamw_kernel) is compiled without any of it.
+template <bool DEV>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, bf16_t* __restrict__ pb, size_t n4, size_t n, float lr,
+                                           float b1, float b2, float omb1, float omb2, float eps, float wd,
+                                           float step_size, float gscale, const KmbStepState* __restrict__ st) {
+  if (DEV) {
+    if (st->applied == 0) return;
+    gscale = gscale * st->coef;
+    step_size = st->step_size;
+  }
   const size_t stride = (size_t)gridDim.x * 256;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
@@ -47,6 +55,109 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
       p[i] = pp; m[i] = mm; v[i] = vv;
       if (pb != nullptr) pb[i] = f2bf(pp);
     }
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v,
+                                                    bf16_t* __restrict__ pb, size_t n4, size_t n, float lr,
+                                                    float b1, float b2, float omb1, float omb2, float eps, float wd,
+                                                    float step_size, float gscale) {
+  adamw_body<false>(p, g, m, v, pb, n4, n, lr, b1, b2, omb1, omb2, eps, wd, step_size, gscale, nullptr);
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v,
+                                                        bf16_t* __restrict__ pb, size_t n4, size_t n, float lr,
+                                                        float b1, float b2, float omb1, float omb2, float eps, float wd,
+                                                        float gscale, const KmbStepState* __restrict__ st) {
+  adamw_body<true>(p, g, m, v, pb, n4, n, lr, b1, b2, omb1, omb2, eps, wd, 0.f, gscale, st);
+}
+
+// ---- global gradient norm (clipping and the non-finite skip of the fused optimizer) ----
+// 4 B/param: sum of (g * gscale)^2 over a contiguous range, every value widened to double BEFORE the product (a finite fp32
+// gradient above 1.8e19 squares to a finite double).  One double per workgroup, stored into that workgroup's own slot: no
+// atomics, and the grid is a function of n alone (kmb_grad_sumsq_slots), so the result depends on the gradients only.
+// Four 16-byte loads per thread and turn are requested before the first is used.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, size_t n4, size_t n, float gscale,
+                                                         double* __restrict__ partials) {
+  const double sc = (double)gscale;
+  const size_t stride = (size_t)gridDim.x * 256;
+  double acc = 0.0;
+  for (size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * 4) {
+    f32x4 gg[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t i = i0 + u * stride;
+      gg[u] = i < n4 ? reinterpret_cast<const f32x4*>(g)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double x = (double)gg[u][e] * sc;
+        acc += x * x;
+      }
+  }
+  // tail (n not a multiple of 4)
+  if (blockIdx.x == 0) {
+    const size_t i = n4 * 4 + threadIdx.x;
+    if (i < n) {
+      const double x = (double)g[i] * sc;
+      acc += x * x;
+    }
+  }
+  __shared__ double wsum[4];
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// One workgroup: total = the used slots summed in a fixed order (thread t takes slots t, t + 256, ... in ascending order, then the
+// same wave / LDS tree as above: a function of nslots alone), the step's record from it.  The bias-correction step count lives in
+// the record: a skipped step does not advance it and the host never has to ask.
+__global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restrict__ partials, int nslots, float max_norm,
+                                                          int skip_nonfinite, double lr, double b1, double b2,
+                                                          int correct_bias, KmbStepState* __restrict__ st) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nslots; i += 256) acc += partials[i];
+  __shared__ double wsum[4];
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double total = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  const double norm = sqrt(total);
+  const bool finite = isfinite(total);
+  double coef = 1.0;
+  if (max_norm > 0.f) {
+    const double c = (double)max_norm / (norm + 1e-6);
+    coef = c < 1.0 ? c : (c != c ? c : 1.0);   // min(1, c); a NaN norm stays a NaN coefficient (torch.clamp)
+  }
+  st->norm = (float)norm;
+  st->coef = (float)coef;
+  if (finite || !skip_nonfinite) {
+    const int steps = st->steps + 1;
+    double step_size = lr;
+    if (correct_bias) {
+      const double bc1 = 1.0 - pow(b1, (double)steps);
+      const double bc2 = 1.0 - pow(b2, (double)steps);
+      step_size = step_size * sqrt(bc2) / bc1;
+    }
+    st->step_size = (float)step_size;
+    st->steps = steps;
+    st->applied = 1;
+  } else {
+    st->step_size = 0.f;
+    st->applied = 0;
+    st->skipped = st->skipped + 1;
   }
 }
 
@@ -215,6 +326,41 @@ hipError_t kmb_adamw_launch(float* p, const float* g, float* m, float* v, bf16_t
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, stream, p, g, m, v, p_bf16, n4, n,
                      (float)h.lr, (float)h.beta1, (float)h.beta2, (float)(1.0 - h.beta1), (float)(1.0 - h.beta2),
                      (float)h.eps, (float)h.weight_decay, (float)step_size, h.grad_scale);
+  return hipGetLastError();
+}
+
+// the device-state step: h.step is not read (the record's count is the authority), h.grad_scale is multiplied by the record's coefficient
+hipError_t kmb_adamw_dev_launch(float* p, const float* g, float* m, float* v, bf16_t* p_bf16, size_t n, KmbAdamW h,
+                                const KmbStepState* state, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (state == nullptr) return hipErrorInvalidValue;
+  const size_t n4 = n >> 2;
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n4, 8192)), dim3(256), 0, stream, p, g, m, v, p_bf16, n4, n,
+                     (float)h.lr, (float)h.beta1, (float)h.beta2, (float)(1.0 - h.beta1), (float)(1.0 - h.beta2),
+                     (float)h.eps, (float)h.weight_decay, h.grad_scale, state);
+  return hipGetLastError();
+}
+
+// workgroups (= partial slots) of a sum over n elements: 1024 elements per workgroup and turn, at most 1024 workgroups
+int kmb_grad_sumsq_slots(size_t n) {
+  if (n == 0) return 0;
+  const size_t b = (n + 1023) / 1024;
+  return (int)(b > 1024 ? 1024 : b);
+}
+
+// partials[0, kmb_grad_sumsq_slots(n)) = per-workgroup sums of (g[i] * grad_scale)^2; g must be 16-byte aligned
+hipError_t kmb_grad_sumsq_launch(const float* g, size_t n, float grad_scale, double* partials, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (((uintptr_t)g & 15) || ((uintptr_t)partials & 7)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(kmb_grad_sumsq_slots(n)), dim3(256), 0, stream, g, n >> 2, n, grad_scale, partials);
+  return hipGetLastError();
+}
+
+hipError_t kmb_clip_finish_launch(const double* partials, int nslots, float max_norm, int skip_nonfinite, KmbAdamW h,
+                                  KmbStepState* state, hipStream_t stream) {
+  if (nslots < 0 || state == nullptr || (nslots > 0 && partials == nullptr)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, stream, partials, nslots, max_norm, skip_nonfinite, h.lr,
+                     h.beta1, h.beta2, (int)h.correct_bias, state);
   return hipGetLastError();
 }
 

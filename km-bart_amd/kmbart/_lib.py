@@ -82,6 +82,11 @@ class KmbAdamW(C.Structure):
                 ("step", i32), ("correct_bias", i32), ("grad_scale", f32)]
 
 
+class KmbStepState(C.Structure):
+    """The device record of a clipped / guarded optimizer step (include/kmbart.h)."""
+    _fields_ = [("norm", f32), ("coef", f32), ("step_size", f32), ("applied", i32), ("steps", i32), ("skipped", i32)]
+
+
 class KmbAllreduceOpts(C.Structure):
     _fields_ = [("algo", i32), ("after_compute", i32), ("max_piece_elems", i64), ("adamw", C.POINTER(KmbAdamW))]
 
@@ -132,6 +137,13 @@ PROTOTYPES = {
     "kmb_backward": (C.c_int, [c_p, f32, c_p]),
     "kmb_backward_dev": (C.c_int, [c_p, c_p, c_p]),
     "kmb_adamw_step": (C.c_int, [c_p, C.POINTER(KmbAdamW), i64, i64, c_p]),
+    "kmb_step_state_bytes": (i64, [c_p]),
+    "kmb_bind_step_state": (C.c_int, [c_p, c_p, i64]),
+    "kmb_grad_sumsq": (C.c_int, [c_p, i64, i64, f32, i32, c_p]),
+    "kmb_clip_finish": (C.c_int, [c_p, C.POINTER(KmbAdamW), f32, i32, i32, c_p]),
+    "kmb_adamw_step_dev": (C.c_int, [c_p, C.POINTER(KmbAdamW), i64, i64, c_p]),
+    "kmb_step_state_read": (C.c_int, [c_p, c_p, c_p]),
+    "kmb_step_state_set_steps": (C.c_int, [c_p, i32, c_p]),
     "kmb_read_status": (C.c_int, [c_p, C.POINTER(i32), c_p]),
     "kmb_read_status_async": (C.c_int, [c_p, c_p, c_p]),
     "kmb_gen_begin": (C.c_int, [c_p, C.POINTER(KmbBatch), C.c_int, C.c_int, c_p]),
@@ -230,6 +242,10 @@ PROTOTYPES = {
     "kmb_op_add_f32_into_bf16": (C.c_int, [c_p, c_p, i64, c_p]),
     "kmb_op_mean_rows": (C.c_int, [c_p, C.c_int, f32, f32, c_p, c_p]),
     "kmb_op_adamw": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, C.POINTER(KmbAdamW), c_p]),
+    "kmb_op_grad_sumsq": (C.c_int, [c_p, i64, f32, c_p, i32, c_p]),
+    "kmb_op_grad_sumsq_slots": (C.c_int, [i64]),
+    "kmb_op_clip_finish": (C.c_int, [c_p, i32, f32, i32, C.POINTER(KmbAdamW), c_p, c_p]),
+    "kmb_op_adamw_dev": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, C.POINTER(KmbAdamW), c_p, c_p]),
     "kmb_op_cast_bf16": (C.c_int, [c_p, c_p, i64, c_p]),
     "kmb_op_dropout_mask": (C.c_int, [u32, f32, C.c_int, C.c_int, c_p, c_p]),
 }

@@ -65,6 +65,22 @@ def refuse_ignored_head_labels(head, labels):
                          "label for it); drop those rows from the head's row list instead" % (head, head))
 
 
+class StepRecord:
+    """A device copy of a KmbStepState (Engine.step_record)."""
+
+    def __init__(self, dev):
+        self.dev = dev
+
+    @staticmethod
+    def decode(host_bytes):
+        r = _lib.KmbStepState.from_buffer_copy(host_bytes.numpy().tobytes())
+        return {"norm": float(r.norm), "coef": float(r.coef), "step_size": float(r.step_size), "applied": int(r.applied),
+                "steps": int(r.steps), "skipped": int(r.skipped)}
+
+    def read(self):
+        return self.decode(self.dev.cpu())
+
+
 class Engine:
     """One model replica on one GPU."""
 
@@ -515,6 +531,108 @@ class Engine:
                 check(self.lib.kmb_adamw_step(self.h, C.byref(hp), lo, cnt, C.c_void_p(side.cuda_stream)))
             main.wait_stream(side)
         return True
+
+    # ---- clipped / guarded optimizer step (kmbart.optim.AdamW(max_grad_norm=..., skip_nonfinite=...)) ------------------
+    def bind_step_state(self):
+        """The step's device record (KmbStepState) and the partial sums of the gradient norm: a buffer of its own, NOT part of
+        the workspace (KMB_POISON rewrites that before every forward; the bias-correction step count lives here).  Bound once;
+        the device step count starts at the host's."""
+        if getattr(self, "_step_buf", None) is None:
+            with torch.cuda.device(self.device):
+                buf = torch.zeros(int(self.lib.kmb_step_state_bytes(self.h)), dtype=torch.uint8, device=self.device)
+                torch.cuda.synchronize(self.device)
+                check(self.lib.kmb_bind_step_state(self.h, ptr(buf), buf.numel()))
+                check(self.lib.kmb_step_state_set_steps(self.h, int(self.step_count), _stream()))
+            self._step_buf = buf
+            self._steps_written = True   # on the caller's stream: see guarded_step
+            self._step_host = torch.zeros(C.sizeof(_lib.KmbStepState), dtype=torch.uint8).pin_memory()
+        return self._step_buf
+
+    def step_pieces(self, ranges):
+        """[(bucket, offset, count, slot0)] in ascending offset order: the (offset, count) ranges cut at the gradient buckets'
+        boundaries, each with its own block of partial slots -- the same pieces, hence the same bits, whichever stream
+        sums them.  The second value is the number of slots in use."""
+        if getattr(self, "_bucket_list", None) is None:
+            self._bucket_list = self.buckets()
+            self._opt_stream = torch.cuda.Stream(device=self.device)
+        pieces = []
+        for off, cnt in ranges:
+            for i, (boff, bcnt) in enumerate(self._bucket_list):
+                lo, hi = max(off, boff), min(off + cnt, boff + bcnt)
+                if lo < hi:
+                    pieces.append((i, lo, hi - lo))
+        if sum(c for _, _, c in pieces) != sum(c for _, c in ranges):
+            raise _lib.KmbError("the optimizer's parameter ranges are not covered by the engine's gradient buckets")
+        pieces.sort(key=lambda x: x[1])
+        out, slot = [], 0
+        for i, lo, cnt in pieces:
+            out.append((i, lo, cnt, slot))
+            slot += int(self.lib.kmb_op_grad_sumsq_slots(cnt))
+        return out, slot
+
+    def guarded_step(self, groups, max_norm, skip_nonfinite, grad_scale=1.0, overlap=False):
+        """Sum of squares of every piece -> ONE finish launch (norm, clip coefficient, finite?, step size: the KmbStepState
+        record) -> the device-state AdamW of every piece.  groups: [(hyperparameter dict, [(offset, count)])].  overlap: each
+        piece's sum goes on the optimizer's side stream behind its bucket's completion event of the backward pass still
+        running on the GPU; the finish launch and the updates follow on that stream (the norm needs every gradient, so they
+        cannot start earlier) and the caller's stream waits for it.  Nothing here synchronises the host."""
+        self.bind_step_state()
+        # the pieces, their slots and each piece's parameter group are constant for a given set of ranges: built once
+        key = tuple((off, cnt, gi) for gi, (_, ranges) in enumerate(groups) for off, cnt in ranges)
+        plan = getattr(self, "_step_plan", None)
+        if plan is None or plan[0] != key:
+            pieces, nslots = self.step_pieces([(off, cnt) for off, cnt, _ in key])
+            owner = [next(gi for off, cnt, gi in key if off <= lo < off + cnt) for _, lo, _, _ in pieces]
+            plan = self._step_plan = (key, pieces, nslots, owner, sorted(pieces, key=lambda x: x[0]))
+        _, pieces, nslots, owner, by_bucket = plan
+        if overlap and not getattr(self, "adamw_overlap_ok", True):
+            overlap = False
+        hps = [KmbAdamW(lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], weight_decay=g["weight_decay"],
+                        step=0, correct_bias=1 if g["correct_bias"] else 0, grad_scale=grad_scale) for g, _ in groups]
+        self.fwd_serial += 1   # the weights move
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream()
+            side = self._opt_stream if overlap else main
+            s = C.c_void_p(side.cuda_stream)
+            if overlap and self._steps_written:
+                # the record's step count was written on the caller's stream (first bind, set_device_steps), possibly behind the
+                # backward pass whose bucket events are all the side stream waits for: order the finish launch behind that write
+                side.wait_stream(main)
+            self._steps_written = False
+            # launch order = bucket completion order (what backward finishes first is summed first); the slots do not depend on it
+            for i, lo, cnt, slot0 in by_bucket:
+                if overlap:
+                    self.stream_wait_bucket(i, side)
+                check(self.lib.kmb_grad_sumsq(self.h, lo, cnt, C.c_float(grad_scale), slot0, s))
+            check(self.lib.kmb_clip_finish(self.h, C.byref(hps[0]), C.c_float(max_norm if max_norm is not None else 0.0),
+                                           1 if skip_nonfinite else 0, nslots, s))
+            for (i, lo, cnt, _), gi in zip(pieces, owner):
+                check(self.lib.kmb_adamw_step_dev(self.h, C.byref(hps[gi]), lo, cnt, s))
+            if overlap:
+                main.wait_stream(side)
+
+    @property
+    def grad_norm(self):
+        """0-d fp32 device view of the record's `norm` (the last guarded step's pre-clip global gradient norm): no sync."""
+        return self.bind_step_state()[:4].view(torch.float32).view(())
+
+    def step_state(self):
+        """The record on the host (synchronises)."""
+        self.bind_step_state()
+        with torch.cuda.device(self.device):
+            check(self.lib.kmb_step_state_read(self.h, C.c_void_p(self._step_host.data_ptr()), _stream()))
+            torch.cuda.current_stream().synchronize()
+        return StepRecord.decode(self._step_host)
+
+    def step_record(self):
+        """A device copy of the record in stream order (no synchronisation); StepRecord.read() brings it to the host later."""
+        return StepRecord(self.bind_step_state()[:C.sizeof(_lib.KmbStepState)].clone())
+
+    def set_device_steps(self, steps):
+        self.bind_step_state()
+        with torch.cuda.device(self.device):
+            check(self.lib.kmb_step_state_set_steps(self.h, int(steps), _stream()))
+        self._steps_written = True
 
     # ---- data-parallel buckets --------------------------------------------------------------
     def buckets(self):

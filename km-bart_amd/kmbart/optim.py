@@ -65,16 +65,26 @@ def reference_parameter_order(names):
 
 
 class AdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
+                 max_grad_norm=None, skip_nonfinite=False):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError("Invalid beta parameters: {} - should be in [0.0, 1.0[".format(betas))
         if not 0.0 <= eps:
             raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("Invalid max_grad_norm: {} - should be > 0.0 (None: no clipping)".format(max_grad_norm))
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       correct_bias=correct_bias))
         self.grad_scale = 1.0  # data-parallel wrapper may fold 1/world here
+        # Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, L2, over ALL parameter groups) and the skip of a step
+        # whose gradients are not finite (what GradScaler.step does), both decided on the device inside step(): one pass
+        # over the gradient arena for the norm, one tiny launch for the decision, then the update under it (Engine.guarded_step).
+        # Nothing synchronises and nothing touches the gradients, so the overlap below stays allowed.  With either set the
+        # bias-correction step count lives on the device (a skipped step does not advance it); with both off nothing changes.
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         import os
         # Overlapped stepping (Engine.adamw_step_overlapped) issues each bucket's update on a second stream behind that
         # bucket's completion event of the backward pass still running on the GPU.  It is only correct when NOTHING
@@ -117,6 +127,10 @@ class AdamW(torch.optim.Optimizer):
         overlap allowed, no gradient scaling)."""
         if not (self.overlap and self.grad_scale == 1.0 and len(self.param_groups) == 1):
             return False
+        if self.guarded:
+            # the global norm needs every reduced gradient before any parameter moves: the wrapper all-reduces as it does
+            # without an attached optimizer and step() clips the averaged gradient (what DDP + clip_grad_norm_ computes)
+            return False
         params = self.param_groups[0]["params"]
         # every parameter of this engine and nothing else: the pieces then tile the whole arena (alignment gaps between
         # parameters hold zeros in all four arenas: their update is exactly zero)
@@ -150,6 +164,46 @@ class AdamW(torch.optim.Optimizer):
                 engines[id(e)] = e
         return list(engines.values())
 
+    # ---- clipping and the non-finite skip ----------------------------------------------------------------------------
+    @property
+    def guarded(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _one_engine(self):
+        engines = self._engines()
+        if len(engines) != 1:
+            raise RuntimeError("this optimizer steps %d engines: ask each engine (Engine.grad_norm / Engine.step_state())"
+                               % len(engines))
+        return engines[0]
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor: the global gradient norm the last step() saw, before clipping and with grad_scale applied (a
+        view of the step's device record: reading it enqueues on the current stream, nothing synchronises here)."""
+        return self._one_engine().grad_norm
+
+    def step_state(self):
+        """The last step's device record on the host (synchronises): norm, coef, applied, steps, skipped."""
+        r = self._one_engine().step_state()
+        return {k: r[k] for k in ("norm", "coef", "applied", "steps", "skipped")}
+
+    def step_record(self):
+        """A device copy of the last step's record, enqueued on the current stream (no synchronisation): `.read()` later gives
+        what step_state() would have given now."""
+        return self._one_engine().step_record()
+
+    def _guarded_step(self, all_ranges):
+        first = self.param_groups[0]
+        for g in self.param_groups[1:]:
+            if any(g[k] != first[k] for k in ("lr", "betas", "correct_bias")):
+                raise ValueError("max_grad_norm / skip_nonfinite: the step size is computed once on the device, so lr, betas and "
+                                 "correct_bias must be the same in every parameter group (eps and weight_decay may differ)")
+        overlap = self.overlap and self.grad_scale == 1.0
+        for e in self._engines():
+            groups = [(g, [(off, cnt) for eng, off, cnt in ranges if eng is e])
+                      for g, ranges in zip(self.param_groups, all_ranges)]
+            e.guarded_step(groups, self.max_grad_norm, self.skip_nonfinite, self.grad_scale, overlap=overlap)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
@@ -165,6 +219,9 @@ class AdamW(torch.optim.Optimizer):
             # collective is matched.
             if getattr(e, "moments_sharded", False):
                 e.comm_gather_moments()
+        if self.guarded:
+            self._guarded_step(all_ranges)
+            return loss
         # ONE bias-correction step per optimizer.step(), whatever the number of parameter groups
         for e in self._engines():
             e.step_count += 1
@@ -190,7 +247,8 @@ class AdamW(torch.optim.Optimizer):
                                    "(it is a collective) before optimizer.state_dict()")
         return {
             "kmbart_adamw": True,
-            "step": [e.step_count for e in eng],
+            # (clipping / skip on: the device's count of APPLIED steps is the authority; reading it synchronises)
+            "step": [e.step_state()["steps"] if self.guarded else e.step_count for e in eng],
             "exp_avg": [e.exp_avg.detach().cpu() for e in eng],
             "exp_avg_sq": [e.exp_avg_sq.detach().cpu() for e in eng],
             # the arena layout the two moment arenas were dumped in: name -> (offset, element count).  The arena order is an
@@ -199,6 +257,11 @@ class AdamW(torch.optim.Optimizer):
             "layout": [{n: (int(off), int(rows) * int(cols)) for n, (off, rows, cols) in e.index.items()} for e in eng],
             "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
         }
+
+    def _set_steps(self, e, steps):
+        e.step_count = steps
+        if self.guarded:
+            e.set_device_steps(steps)   # in stream order, no synchronisation
 
     def load_state_dict(self, state, assume_layout=False):
         """Accepts this class's own format and the torch / transformers.AdamW format the reference saves in
@@ -212,7 +275,7 @@ class AdamW(torch.optim.Optimizer):
                 engines = self._engines()
                 if assume_layout and all(state["exp_avg"][i].numel() == e.exp_avg.numel() for i, e in enumerate(engines)):
                     for i, e in enumerate(engines):
-                        e.step_count = int(state["step"][i])
+                        self._set_steps(e, int(state["step"][i]))
                         e.exp_avg.copy_(state["exp_avg"][i])
                         e.exp_avg_sq.copy_(state["exp_avg_sq"][i])
                     for g, s in zip(self.param_groups, state["param_groups"]):
@@ -228,7 +291,7 @@ class AdamW(torch.optim.Optimizer):
                 if set(saved) != set(here):
                     raise ValueError("optimizer state was saved for a different parameter set: %s"
                                      % sorted(set(saved) ^ set(here))[:4])
-                e.step_count = int(state["step"][i])
+                self._set_steps(e, int(state["step"][i]))
                 if all(tuple(saved[n]) == here[n] for n in here) and state["exp_avg"][i].numel() == e.exp_avg.numel():
                     e.exp_avg.copy_(state["exp_avg"][i])
                     e.exp_avg_sq.copy_(state["exp_avg_sq"][i])
@@ -282,4 +345,4 @@ class AdamW(torch.optim.Optimizer):
                 raise ValueError("per-parameter step counts differ (%d..%d): one fused step count is kept per engine"
                                  % (min(steps), max(steps)))
             for e in self._engines():
-                e.step_count = steps[0]
+                self._set_steps(e, steps[0])

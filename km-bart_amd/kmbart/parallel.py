@@ -21,7 +21,10 @@ communication stream.  The tied matrix (154 MB, complete last) travels in <= 64 
 update, so the un-overlapped tail is one piece, not 564 MB of all-reduce plus a 1.1 ms optimizer launch.
 `grad_dtype="bf16"` halves the bytes on the wire (282 MB): a piece is cast into a bf16 staging buffer, reduced, and
 cast back (fp32 accumulation inside the optimizer is unchanged); off by default -- xGMI has the bandwidth at the
-benchmark batch, SURVEY.md section 5 prices when it does not.
+benchmark batch, SURVEY.md section 5 prices when it does not.  An optimizer that clips the global gradient norm or skips
+non-finite steps itself (`AdamW(max_grad_norm=..., skip_nonfinite=...)`) declines the tail (`begin_fused_step` returns False):
+the norm needs every reduced gradient before any parameter moves, so the exchange runs as without an attached optimizer and
+`opt.step()` clips the averaged gradient -- what DDP + `clip_grad_norm_` computes.
 
 Native exchange (nccl backend; the default for a one-rank group, OPT-IN with KMB_DP_NATIVE=1 / native=True for more than one
 rank until a multi-GPU run of tests/dp_rccl_worker.py has passed on hardware: none of its world > 1 collectives has ever

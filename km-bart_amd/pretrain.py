@@ -110,7 +110,7 @@ def main(rank, args):
     model.to(device)
     if distributed:
         model = DistributedDataParallel(model, device_ids=[rank], find_unused_parameters=True)
-    optimizer = AdamW(model.parameters(), lr=args.lr)
+    optimizer = AdamW(model.parameters(), lr=args.lr, max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
     epoch = 0
     if args.continue_training:
         epoch = load_training_data(args.checkpoint, optimizer=optimizer, map_location="cpu")["epoch"] + 1
@@ -165,6 +165,10 @@ def parse_args(argv=None):
     p.add_argument("--gpu_num", default=1, type=int)
     p.add_argument("--cpu", action="store_true")
     p.add_argument("--amp", action="store_true")
+    p.add_argument("--max_grad_norm", default=None, type=float,
+                   help="clip the global L2 gradient norm inside the fused optimizer step (default: no clipping)")
+    p.add_argument("--skip_nonfinite", action="store_true",
+                   help="skip an optimizer step whose gradients hold a NaN or Inf (decided on the device, no synchronisation)")
     p.add_argument("--master_port", type=str, default="12355")
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--num_workers", type=int, default=0)

@@ -23,6 +23,21 @@ def _allow_overlap(optimizer, ok):
         optimizer.allow_overlap(ok)
 
 
+def _step_record(optimizer):
+    """An optimizer that clips / guards its own step (kmbart.optim.AdamW(max_grad_norm=..., skip_nonfinite=...)): a device copy of
+    the step's record, taken in stream order right behind `step()` -- no synchronisation; None for any other optimizer."""
+    return optimizer.step_record() if getattr(optimizer, "guarded", False) else None
+
+
+def _norm_line(record, logger, epoch, args, j, n_steps):
+    """ONE additional line of the per-interval log: the gradient norm of step j and the steps skipped so far (read where the
+    loss is read, one step behind the enqueue)."""
+    if record is not None:
+        st = record.read()
+        logger.info("Epoch [{}/{}], Step [{}/{}], Grad norm: {:.4f}, Skipped steps: {}".format(
+            epoch + 1, args.epochs, j + 1, n_steps, st["norm"], st["skipped"]))
+
+
 def _attach(model, optimizer, ok):
     """Data-parallel wrapper: chain each gradient piece's optimizer update behind its all-reduce (kmbart.parallel)."""
     if ok and hasattr(model, "attach_optimizer"):
@@ -65,13 +80,14 @@ def _fine_tune(epoch, model, train_loader, optimizer, device, args, logger, call
     def report(item):
         if item is None:
             return
-        j, dev_loss, _ = item
+        j, dev_loss, _, record = item
         loss_value = dev_loss.item()
         state["sum"] += loss_value
         if logger is not None and j % log_interval == 0:
             eta = (n_steps - (j + 1)) / (j + 1) * (datetime.now() - t0)
             logger.info("Epoch [{}/{}], Step [{}/{}], Loss: {:.4f}, ETA: {}".format(
                 epoch + 1, args.epochs, j + 1, n_steps, loss_value, str(eta)))
+            _norm_line(record, logger, epoch, args, j, n_steps)
         if tb_writer is not None and j % tb_interval == 0:
             tb_writer.add_scalars("loss/step", {"loss": loss_value}, epoch * n_steps + j + 1)
 
@@ -99,7 +115,7 @@ def _fine_tune(epoch, model, train_loader, optimizer, device, args, logger, call
             loss.backward()
             optimizer.step()
         report(pending)                       # step i-1, while step i runs on the GPU
-        pending = (i, loss.detach(), None)
+        pending = (i, loss.detach(), None, _step_record(optimizer))
         if callback is not None:
             report(pending)
             pending = None
@@ -137,13 +153,14 @@ def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callb
     def report(item):
         if item is None:
             return
-        j, dev_loss, parts = item
+        j, dev_loss, parts, record = item
         loss_value = dev_loss.item()
         state["sum"] += loss_value
         if logger is not None and j % log_interval == 0:
             eta = (n_steps - (j + 1)) / (j + 1) * (datetime.now() - t0)
             logger.info("Epoch [{}/{}], Step [{}/{}], Loss: {:.4f}, ETA: {}".format(
                 epoch + 1, args.epochs, j + 1, n_steps, loss_value, str(eta)))
+            _norm_line(record, logger, epoch, args, j, n_steps)
         if tb_writer is not None and j % tb_interval == 0:
             step = epoch * n_steps + j + 1
             tb_writer.add_scalars("loss/step", {"total loss": loss_value}, step)
@@ -181,7 +198,7 @@ def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callb
             loss.backward()
             optimizer.step()
         report(pending)
-        pending = (i, loss.detach(), {k: v.detach() for k, v in losses.items() if k != "loss"})
+        pending = (i, loss.detach(), {k: v.detach() for k, v in losses.items() if k != "loss"}, _step_record(optimizer))
         if callback is not None:
             report(pending)
             pending = None
