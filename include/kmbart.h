@@ -317,6 +317,23 @@ int kmb_adamw_step_dev(kmb_handle* h, const KmbAdamW* hp, int64_t offset, int64_
 int kmb_step_state_read(kmb_handle* h, KmbStepState* host_record, void* stream);
 /* sets the record's applied-step count (loading a checkpoint), in stream order */
 int kmb_step_state_set_steps(kmb_handle* h, int32_t steps, void* stream);
+/* ---- gradient accumulation over micro-batches.  Every gradient writer of a forward + backward overwrites; with accumulation on they
+ * write this micro-batch's gradient into a second fp32 arena of the same layout, the STAGE, and kmb_backward folds each bucket of it into
+ * the gradient arena right before it records that bucket's completion event: G = stage for the first backward after kmb_zero_grad, G +=
+ * stage for later ones.  A bucket's event (kmb_stream_wait_bucket) then means "the ACCUMULATED gradient of this bucket is complete", and
+ * every reader (kmb_adamw_step*, kmb_grad_sumsq, kmb_allreduce_grads, the caller's views of the arena) sees the running total.
+ * The stage is the caller's buffer of at least kmb_arena_elems floats, 256-byte aligned, zero-filled (the alignment gaps between
+ * parameters are never written and are folded like everything else), outside the workspace: that is rewritten and re-laid out per
+ * micro-batch.  A bound stage must outlive accumulation (switch it off before freeing the buffer). */
+int kmb_bind_grad_stage(kmb_handle* h, float* stage, int64_t floats);
+/* on != 0: gradient writers target the stage and kmb_backward folds; 0 (default): the writers target the gradient arena, as without this
+ * call.  Fails between a need_grad forward and its backward (that forward's gradients already went to one of the two), and when switched
+ * on without a bound stage.  Switching on starts as if kmb_zero_grad had been called. */
+int kmb_set_grad_accumulation(kmb_handle* h, int on);
+/* the next kmb_backward's folds overwrite the gradient arena instead of adding to it (they never read it).  A host flag, no launch; read
+ * when backward runs (forward -> kmb_zero_grad -> backward is the reference's order, src/training.py:136) and cleared by it.  No effect
+ * while accumulation is off. */
+int kmb_zero_grad(kmb_handle* h);
 /* status word written by device-side input validation (bit 0: #<img_feat> ids != #region rows) */
 int kmb_read_status(kmb_handle* h, int32_t* status_host, void* stream);
 /* The same without the synchronisation: the status word is copied to `status_host` (page-locked memory) in stream order; the
@@ -700,6 +717,9 @@ int kmb_op_clip_finish(const double* partials, int32_t nslots, float max_norm, i
                        KmbStepState* state, void* stream);
 int kmb_op_adamw_dev(float* p, const float* g, float* m, float* v, kmb_bf16* p_bf16, int64_t n, const KmbAdamW* hp,
                      const KmbStepState* state, void* stream);
+/* gradient accumulation's fold: dst[0, n) = (add ? dst : 0) + src, one rounded add per element; add == 0 never reads dst.  Any 4-byte
+ * aligned, non-overlapping ranges */
+int kmb_op_grad_fold(float* dst, const float* src, int64_t n, int add, void* stream);
 int kmb_op_cast_bf16(const float* x, kmb_bf16* y, int64_t n, void* stream);
 /* keep[i] = 1 if the dropout generator keeps element (row, col) for this site seed / probability */
 int kmb_op_dropout_mask(uint32_t seed, float p, int rows, int cols, uint8_t* keep, void* stream);

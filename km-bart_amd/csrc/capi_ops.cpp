@@ -295,6 +295,12 @@ int kmb_op_adamw_dev(float* p, const float* g, float* m, float* v, kmb_bf16* p_b
   if (!hp || !state) return kmb_set_error("kmb_op_adamw_dev: hp and state are required");
   return hipfail(kmb_adamw_dev_launch(p, g, m, v, p_bf16, (size_t)n, *hp, state, (hipStream_t)stream), "adamw_dev");
 }
+int kmb_op_grad_fold(float* dst, const float* src, int64_t n, int add, void* stream) {
+  if (!dst || !src || n <= 0) return kmb_set_error("kmb_op_grad_fold: bad arguments");
+  if (((uintptr_t)dst | (uintptr_t)src) & 3) return kmb_set_error("kmb_op_grad_fold: dst and src must be 4-byte aligned");
+  if (dst < src + n && src < dst + n) return kmb_set_error("kmb_op_grad_fold: dst and src overlap");
+  return hipfail(kmb_grad_fold_launch(dst, src, (size_t)n, add, (hipStream_t)stream), "grad_fold");
+}
 int kmb_op_cast_bf16(const float* x, kmb_bf16* y, int64_t n, void* stream) {
   return hipfail(kmb_cast_f32_bf16_launch(x, y, (size_t)n, (hipStream_t)stream), "cast");
 }

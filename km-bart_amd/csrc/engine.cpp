@@ -586,6 +586,34 @@ int kmb_bind_workspace(kmb_handle* h, void* ws, int64_t bytes) {
   return 0;
 }
 
+// ---- gradient accumulation (include/kmbart.h; the folds are kmb_backward's, engine_train.cpp)
+int kmb_bind_grad_stage(kmb_handle* h, float* stage, int64_t floats) {
+  if (!h) return fail("kmb_bind_grad_stage: null handle");
+  if (h->accum) return fail("kmb_bind_grad_stage: switch accumulation off before binding another stage");
+  if (!stage) { h->GS = nullptr; h->stage_floats = 0; return 0; }
+  if (floats < 0 || (size_t)floats < h->arena) return fail("kmb_bind_grad_stage: the stage holds %lld floats, the arena %zu", (long long)floats, h->arena);
+  if ((uintptr_t)stage & 255) return fail("kmb_bind_grad_stage: the stage must be 256-byte aligned");
+  if (h->ws && (char*)stage < h->ws + h->ws_bytes && (char*)(stage + floats) > h->ws) return fail("kmb_bind_grad_stage: the stage lies inside the workspace");
+  if (h->G && stage < h->G + h->arena && stage + floats > h->G) return fail("kmb_bind_grad_stage: the stage overlaps the gradient arena");
+  h->GS = stage; h->stage_floats = (size_t)floats;
+  return 0;
+}
+
+int kmb_set_grad_accumulation(kmb_handle* h, int on) {
+  if (!h) return fail("kmb_set_grad_accumulation: null handle");
+  if (h->have_fwd) return fail("kmb_set_grad_accumulation: a need_grad forward is waiting for its backward (its gradients are already written)");
+  if (on && !h->GS) return fail("kmb_set_grad_accumulation: no stage is bound (kmb_bind_grad_stage)");
+  if (on && !h->accum) h->grad_fresh = true;
+  h->accum = on != 0;
+  return 0;
+}
+
+int kmb_zero_grad(kmb_handle* h) {
+  if (!h) return fail("kmb_zero_grad: null handle");
+  h->grad_fresh = true;
+  return 0;
+}
+
 int kmb_set_seed(kmb_handle* h, uint64_t seed) { h->seed = seed; h->step = 0; return 0; }
 
 int kmb_set_attention_dropout(kmb_handle* h, float p) {

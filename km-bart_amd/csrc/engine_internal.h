@@ -291,7 +291,13 @@ struct kmb_handle {
   }
   bf16_t* wb(size_t off) const { return kmbi::g_f32 ? reinterpret_cast<bf16_t*>(P + off) : PB + off; }   // GEMM B operand: bf16 mirror (fp32 master in validation mode)
   float* pf(size_t off) const { return P + off; }
-  float* gf(size_t off) const { return G + off; }
+  // Gradient accumulation (kmb_set_grad_accumulation): every gradient WRITER goes through gf() and lands in the stage, a second arena of
+  // the caller's with this micro-batch's gradient only; kmb_backward folds each bucket of it into G in front of the bucket's completion
+  // event (fold_bucket, engine_train.cpp).  Every READER (the optimizer, the norm, the exchange, the caller's views) uses G.
+  float* GS = nullptr; size_t stage_floats = 0;
+  bool accum = false;
+  bool grad_fresh = true;   // kmb_zero_grad: the next backward's folds overwrite G; cleared by that backward
+  float* gf(size_t off) const { return (accum ? GS : G) + off; }
 };
 
 namespace kmbi __attribute__((visibility("hidden"))) {

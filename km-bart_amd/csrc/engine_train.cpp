@@ -1,5 +1,5 @@
-// The training step: workspace layout, forward (encoder, decoder, LM head, pre-training heads), backward, kmb_score and the readers
-// of the last forward's activations.
+// The training step: workspace layout, forward (encoder, decoder, LM head, pre-training heads), backward (with gradient
+// accumulation's per-bucket folds), kmb_score and the readers of the last forward's activations.
 #include "engine_internal.h"
 
 namespace kmbi __attribute__((visibility("hidden"))) {
@@ -839,12 +839,27 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
   // the bucket of layer c is complete when BOTH streams are past this point: record its event on the side stream
   // behind a marker of the main stream, so the main stream never waits here
   // (c < 0: a bucket that is no layer's -- the decoder embedding's)
+  // Gradient accumulation: this backward's writers fill the stage (kmb_handle::gf); a bucket's fold into G goes out on the stream that
+  // records the bucket's event, right in front of it and behind both streams' writers, exactly as the event is.  The event then
+  // means "the ACCUMULATED gradient of this bucket is complete".  The first backward after kmb_zero_grad overwrites G without reading it.
+  // The next micro-step's writers are ordered behind these folds: every backward ends with the caller's stream behind the side stream,
+  // and the side stream's work always starts behind a marker of the caller's stream (wgrad_side, wgrad_flush, reducer_stream).
+  const bool accum = h->accum, fold_add = accum && !h->grad_fresh;
+  if (accum) h->grad_fresh = false;
+  auto fold_bucket = [&](int bucket, hipStream_t fs) -> int {
+    if (!accum) return 0;
+    const Bucket& bk = h->buckets[bucket];
+    HIPCHK(kmb_grad_fold_launch(h->G + bk.off, h->GS + bk.off, bk.count, fold_add ? 1 : 0, fs));
+    return 0;
+  };
   auto layer_end = [&](int c, int bucket) -> int {
     KCHK(wgrad_flush(h, s));   // the layer's parked weight gradients go out as one launch (grouped path)
-    if (!side) { HIPCHK(hipEventRecord(h->events[bucket], s)); return 0; }
+    if (!side) { KCHK(fold_bucket(bucket, s)); HIPCHK(hipEventRecord(h->events[bucket], s)); return 0; }
     KCHK(order_behind(h, s, h->side));
+    if (accum && c >= 0) HIPCHK(hipEventRecord(h->layer_done[c], h->side));   // (the fold reads none of the layer's gradient buffers)
+    KCHK(fold_bucket(bucket, h->side));
     HIPCHK(hipEventRecord(h->events[bucket], h->side));
-    if (c >= 0) HIPCHK(hipEventRecord(h->layer_done[c], h->side));
+    if (!accum && c >= 0) HIPCHK(hipEventRecord(h->layer_done[c], h->side));
     return 0;
   };
   const bool scaled = loss_scale != 1.f || loss_scale_dev != nullptr;
@@ -945,11 +960,14 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
     // contributions: the head's weight gradient and the decoder embedding's scatter-add above).
     for (int l = Le - 1; l >= 0; --l, ++ev) {
       HIPCHK(hipMemsetAsync(h->gf(h->buckets[ev].off), 0, h->buckets[ev].count * sizeof(float), s));
+      KCHK(fold_bucket(ev, s));
       HIPCHK(hipEventRecord(h->events[ev], s));
     }
     HIPCHK(hipMemsetAsync(h->gf(h->buckets[ev].off), 0, h->buckets[ev].count * sizeof(float), s));
     if (side) KCHK(order_behind(h, h->side, s));
+    KCHK(fold_bucket(ev, s));
     HIPCHK(hipEventRecord(h->events[ev++], s));
+    KCHK(fold_bucket(ev, s));
     HIPCHK(hipEventRecord(h->events[ev++], s));
     return 0;
   }
@@ -983,7 +1001,9 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
   }
   KCHK(wgrad_flush(h, s));
   if (side) KCHK(order_behind(h, h->side, s));  // everything the optimizer reads must be ordered behind the side stream's last weight gradient
+  KCHK(fold_bucket(ev, s));
   HIPCHK(hipEventRecord(h->events[ev++], s));
+  KCHK(fold_bucket(ev, s));
   HIPCHK(hipEventRecord(h->events[ev++], s));  // tied matrix: complete once the encoder-side scatter-add is in
   return 0;
 }

@@ -179,6 +179,8 @@ int kmb_grad_sumsq_slots(size_t n);
 hipError_t kmb_grad_sumsq_launch(const float* g, size_t n, float grad_scale, double* partials, hipStream_t stream);
 hipError_t kmb_clip_finish_launch(const double* partials, int nslots, float max_norm, int skip_nonfinite, KmbAdamW h,
                                   KmbStepState* state, hipStream_t stream);
+// gradient accumulation: dst[0, n) = (add ? dst : 0) + src (the overwrite form never reads dst); 4-byte aligned pointers
+hipError_t kmb_grad_fold_launch(float* dst, const float* src, size_t n, int add, hipStream_t stream);
 hipError_t kmb_cast_f32_bf16_launch(const float* x, bf16_t* y, size_t n, hipStream_t stream);
 hipError_t kmb_fill_f32_launch(float* x, float v, size_t n, hipStream_t stream);
 // y[r*ldy + c] = bf16(x[r*ldx + c]) for c < cols, zero for cols <= c < ldy

@@ -1,5 +1,6 @@
 // Fused multi-tensor AdamW (transformers 3.0.2 form, reference vcg_train.py:100) over the flat
-// parameter arena, plus small HBM-bound movers (casts, fills, KV-cache append, row gather).
+// parameter arena, the gradient norm of the clipped / guarded step, gradient accumulation's fold (stage -> gradient arena), plus
+// small HBM-bound movers (casts, fills, KV-cache append, row gather).
 #include "common.h"
 #include "kernels.h"
 #include "diag.h"
@@ -158,6 +159,46 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restri
     st->step_size = 0.f;
     st->applied = 0;
     st->skipped = st->skipped + 1;
+  }
+}
+
+// ---- gradient accumulation: fold one micro-batch's gradient (the stage) into the running total ----
+// dst[i] = (ADD ? dst[i] : 0) + src[i]: 12 B/param (ADD) or 8 (overwrite), one correctly rounded add per element.  The overwrite
+// form never READS dst (the arena may hold NaN from a skipped step).  dst and src are only 4-byte aligned and need not share their
+// phase: the vector body starts at dst's first 16-byte boundary (`head` elements in), so the stores are 16-byte ones, and src is read
+// with 16-byte loads when it has the same phase, else element by element (the engine's buckets always have).  Four loads per operand
+// and turn are requested before the first add, as in grad_sumsq_kernel; the grid is sized to the chip.
+template <bool ADD, bool SRC_VEC>
+__global__ __launch_bounds__(256) void grad_fold_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t head,
+                                                        size_t n4, size_t n) {
+  float* d4 = dst + head;
+  const float* s4 = src + head;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * 4) {
+    f32x4 ss[4], dd[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t i = i0 + u * stride;
+      if (i < n4) {
+        if (SRC_VEC) ss[u] = reinterpret_cast<const f32x4*>(s4)[i];
+        else ss[u] = f32x4{s4[4 * i], s4[4 * i + 1], s4[4 * i + 2], s4[4 * i + 3]};
+        if (ADD) dd[u] = reinterpret_cast<const f32x4*>(d4)[i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t i = i0 + u * stride;
+      if (i < n4) reinterpret_cast<f32x4*>(d4)[i] = ADD ? dd[u] + ss[u] : ss[u];
+    }
+  }
+  // the elements in front of the first and behind the last whole 16 bytes of dst (at most 3 each)
+  if (blockIdx.x == 0) {
+    const size_t tail0 = head + n4 * 4;
+    const size_t edge = head + (n - tail0);
+    if (threadIdx.x < edge) {
+      const size_t i = threadIdx.x < head ? threadIdx.x : tail0 + (threadIdx.x - head);
+      dst[i] = ADD ? dst[i] + src[i] : src[i];
+    }
   }
 }
 
@@ -361,6 +402,22 @@ hipError_t kmb_clip_finish_launch(const double* partials, int nslots, float max_
   if (nslots < 0 || state == nullptr || (nslots > 0 && partials == nullptr)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, stream, partials, nslots, max_norm, skip_nonfinite, h.lr,
                      h.beta1, h.beta2, (int)h.correct_bias, state);
+  return hipGetLastError();
+}
+
+// dst[0, n) = (add ? dst : 0) + src; both only 4-byte aligned.  Grid: four 16-byte pieces per thread and turn, at most 256 CUs x 8 workgroups
+hipError_t kmb_grad_fold_launch(float* dst, const float* src, size_t n, int add, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if (((uintptr_t)dst & 3) || ((uintptr_t)src & 3)) return hipErrorInvalidValue;
+  size_t head = ((16 - ((uintptr_t)dst & 15)) & 15) >> 2;   // elements in front of dst's first 16-byte boundary
+  if (head > n) head = n;
+  const size_t n4 = (n - head) >> 2;
+  const bool src_vec = (((uintptr_t)(src + head)) & 15) == 0;
+  const dim3 grid(grid_for((n4 + 3) / 4, 2048)), block(256);
+#define KMB_FOLD(A, V) hipLaunchKernelGGL((grad_fold_kernel<A, V>), grid, block, 0, stream, dst, src, head, n4, n)
+  if (add) { if (src_vec) KMB_FOLD(true, true); else KMB_FOLD(true, false); }
+  else { if (src_vec) KMB_FOLD(false, true); else KMB_FOLD(false, false); }
+#undef KMB_FOLD
   return hipGetLastError();
 }
 

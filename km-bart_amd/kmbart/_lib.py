@@ -144,6 +144,9 @@ PROTOTYPES = {
     "kmb_adamw_step_dev": (C.c_int, [c_p, C.POINTER(KmbAdamW), i64, i64, c_p]),
     "kmb_step_state_read": (C.c_int, [c_p, c_p, c_p]),
     "kmb_step_state_set_steps": (C.c_int, [c_p, i32, c_p]),
+    "kmb_bind_grad_stage": (C.c_int, [c_p, c_p, i64]),
+    "kmb_set_grad_accumulation": (C.c_int, [c_p, C.c_int]),
+    "kmb_zero_grad": (C.c_int, [c_p]),
     "kmb_read_status": (C.c_int, [c_p, C.POINTER(i32), c_p]),
     "kmb_read_status_async": (C.c_int, [c_p, c_p, c_p]),
     "kmb_gen_begin": (C.c_int, [c_p, C.POINTER(KmbBatch), C.c_int, C.c_int, c_p]),
@@ -244,6 +247,7 @@ PROTOTYPES = {
     "kmb_op_adamw": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, C.POINTER(KmbAdamW), c_p]),
     "kmb_op_grad_sumsq": (C.c_int, [c_p, i64, f32, c_p, i32, c_p]),
     "kmb_op_grad_sumsq_slots": (C.c_int, [i64]),
+    "kmb_op_grad_fold": (C.c_int, [c_p, c_p, i64, C.c_int, c_p]),
     "kmb_op_clip_finish": (C.c_int, [c_p, i32, f32, i32, C.POINTER(KmbAdamW), c_p, c_p]),
     "kmb_op_adamw_dev": (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, C.POINTER(KmbAdamW), c_p, c_p]),
     "kmb_op_cast_bf16": (C.c_int, [c_p, c_p, i64, c_p]),

@@ -486,6 +486,31 @@ class Engine:
             else:
                 check(self.lib.kmb_backward(self.h, C.c_float(loss_scale), _stream()))
 
+    # ---- gradient accumulation over micro-batches (kmb_set_grad_accumulation, include/kmbart.h) ---------------------------
+    def grad_accumulation(self, on=True):
+        """on: a backward leaves its micro-batch's gradient in the stage (a second arena, allocated here on first use: 4 B per
+        parameter) and folds it into `grads` bucket by bucket, overwriting on the first backward after zero_grad() and adding
+        afterwards; `grads` -- what the optimizer, the norm, the data-parallel exchange and `p.grad` read -- holds the running
+        total.  off: every backward overwrites `grads` directly (the default).  Not between a need_grad forward and its backward."""
+        with torch.cuda.device(self.device):
+            if on and getattr(self, "_grad_stage", None) is None:
+                self._grad_stage = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+                check(self.lib.kmb_bind_grad_stage(self.h, ptr(self._grad_stage), self._grad_stage.numel()))
+            check(self.lib.kmb_set_grad_accumulation(self.h, 1 if on else 0))
+        self.accumulating = bool(on)
+
+    accumulating = False
+
+    def zero_grad(self):
+        """The next backward starts a new sum (a host flag: nothing is launched, `grads` keeps its values until then).  No
+        effect while accumulation is off."""
+        check(self.lib.kmb_zero_grad(self.h))
+
+    @property
+    def grad_stage(self):
+        """The stage as a tensor (the LAST backward's own gradient while accumulation is on), None before grad_accumulation(True)."""
+        return getattr(self, "_grad_stage", None)
+
     def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, grad_scale=1.0,
                    offset=0, count=None, bump=True):
         if bump:

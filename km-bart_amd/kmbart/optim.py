@@ -236,7 +236,17 @@ class AdamW(torch.optim.Optimizer):
         return loss
 
     def zero_grad(self, set_to_none=False):
-        pass  # gradients are views into the arena and are overwritten by the next backward
+        # gradients are views into the arena and are overwritten by the next backward; while an engine accumulates
+        # (Engine.grad_accumulation) this makes its next backward start a new sum
+        n = sum(len(g["params"]) for g in self.param_groups)
+        cached = self.__dict__.get("_zero_engines")
+        if cached is None or cached[0] != n:   # (built once: this runs every step of every loop)
+            found = {id(e): e for g in self.param_groups for e in (getattr(p, "_kmb_engine", None) for p in g["params"])
+                     if e is not None}
+            cached = self._zero_engines = (n, list(found.values()))
+        for e in cached[1]:
+            if e.accumulating:
+                e.zero_grad()
 
     def state_dict(self):
         eng = self._engines()

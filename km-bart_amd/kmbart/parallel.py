@@ -26,6 +26,11 @@ non-finite steps itself (`AdamW(max_grad_norm=..., skip_nonfinite=...)`) decline
 the norm needs every reduced gradient before any parameter moves, so the exchange runs as without an attached optimizer and
 `opt.step()` clips the averaged gradient -- what DDP + `clip_grad_norm_` computes.
 
+Gradient accumulation (`module.accumulate_gradients()`): a bucket's event then marks the ACCUMULATED gradient of the
+bucket, so everything above works on the running total.  Run every micro-batch but a group's last inside `no_sync()`: nothing is
+exchanged and no optimizer piece runs there; the last backward reduces the sum -- one exchange per optimizer step.  (A backward
+outside `no_sync()` averages the arena in place: accumulating on top of an already averaged partial sum is not what anyone wants.)
+
 Native exchange (nccl backend; the default for a one-rank group, OPT-IN with KMB_DP_NATIVE=1 / native=True for more than one
 rank until a multi-GPU run of tests/dp_rccl_worker.py has passed on hardware: none of its world > 1 collectives has ever
 executed; their offsets are pinned on the CPU by tests/test_comm_plan_cpu.py).  The library owns an RCCL communicator and a communication stream
@@ -41,6 +46,13 @@ import os
 
 import torch
 import torch.distributed as dist
+
+
+_TWICE = ("loss.backward() ran twice without optimizer.step() while an optimizer is attached to the data-parallel wrapper "
+          "(attach_optimizer fuses the AdamW step into backward, so a second backward would meet parameters that already moved). "
+          "For gradient accumulation call model.accumulate_gradients() and run every micro-batch but the group's last inside "
+          "no_sync(): nothing is reduced and nothing steps there, and the last backward reduces and steps the accumulated "
+          "gradient.  For any other custom loop call detach_optimizer().")
 
 
 class BucketedAllReducer:
@@ -132,7 +144,23 @@ class _Null:
         return False
 
 
+class _NoSync:
+    def __init__(self, ddp):
+        self.ddp = ddp
+
+    def __enter__(self):
+        self.was = self.ddp._no_sync
+        self.ddp._no_sync = True
+        return self.ddp
+
+    def __exit__(self, *a):
+        self.ddp._no_sync = self.was
+        return False
+
+
 class DistributedDataParallel(torch.nn.Module):
+    _no_sync = False   # inside no_sync(): _post_backward does nothing
+
     def __init__(self, module, device_ids=None, find_unused_parameters=False, process_group=None,
                  max_bucket_mb=64, reduce_single_rank=False, grad_dtype=None, native=None, algo=None):
         super().__init__()
@@ -264,6 +292,13 @@ class DistributedDataParallel(torch.nn.Module):
             self._opt._fused_pending = False
         self._opt = None
 
+    def no_sync(self):
+        """Context manager (torch DistributedDataParallel.no_sync): a `loss.backward()` inside it exchanges nothing and runs none
+        of an attached optimizer's pieces -- the gradients stay this rank's.  With `module.accumulate_gradients()` the first
+        backward OUTSIDE it then reduces (and, with an optimizer attached, steps) the sum over the micro-batches: one exchange per
+        optimizer step.  Without accumulation a backward overwrites, so the earlier micro-batches would simply be lost."""
+        return _NoSync(self)
+
     def _step_piece(self, off, cnt):
         if self._opt is not None and self._fusing:
             self._opt.fused_piece_step(self.engine, off, cnt)
@@ -278,13 +313,13 @@ class DistributedDataParallel(torch.nn.Module):
     def _reduce_native(self):
         """loss.backward()'s tail on the native path: ONE library call enqueues the step's whole exchange (and the fused
         optimizer pieces) on the communication stream, a second makes the compute stream wait for it."""
+        if self._no_sync:
+            return
         eng = self.engine
         first = self._first_reduce     # the first backward times the GEMM variants of every shape: keep RCCL out of it
         self._first_reduce = False
         if self._opt is not None and getattr(self._opt, "_fused_pending", False):
-            raise RuntimeError("loss.backward() ran twice without optimizer.step() while an optimizer is attached to the "
-                               "data-parallel wrapper (attach_optimizer fuses the AdamW step into backward); call "
-                               "detach_optimizer() for gradient accumulation or custom loops")
+            raise RuntimeError(_TWICE)
         self._fusing = self._opt is not None and self._opt.begin_fused_step(eng)
         hp = self._opt.fused_hyperparams(eng) if self._fusing else None
         pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -299,15 +334,15 @@ class DistributedDataParallel(torch.nn.Module):
         self._fusing = False
 
     def _reduce(self):
+        if self._no_sync:
+            return
         if self._first_reduce:
             # the first backward times the GEMM variants of every shape (autotune): keep the all-reduces out of it
             self._first_reduce = False
             if self.reducer.comm_stream is not None:
                 self.reducer.comm_stream.wait_stream(torch.cuda.current_stream())
         if self._opt is not None and getattr(self._opt, "_fused_pending", False):
-            raise RuntimeError("loss.backward() ran twice without optimizer.step() while an optimizer is attached to the "
-                               "data-parallel wrapper (attach_optimizer fuses the AdamW step into backward); call "
-                               "detach_optimizer() for gradient accumulation or custom loops")
+            raise RuntimeError(_TWICE)
         self._fusing = self._opt is not None and self._opt.begin_fused_step(self.engine)
         # exposed tail: the compute stream has nothing left to run between these two events except waiting for the
         # communication stream (the all-reduces that did not fit under backward + the optimizer pieces chained behind them)

@@ -169,6 +169,8 @@ def parse_args(argv=None):
                    help="clip the global L2 gradient norm inside the fused optimizer step (default: no clipping)")
     p.add_argument("--skip_nonfinite", action="store_true",
                    help="skip an optimizer step whose gradients hold a NaN or Inf (decided on the device, no synchronisation)")
+    p.add_argument("--accumulation_steps", default=1, type=int,
+                   help="optimizer step every N batches on the sum of their gradients, each batch's loss divided by N (default 1)")
     p.add_argument("--master_port", type=str, default="12355")
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--num_workers", type=int, default=0)
@@ -180,6 +182,8 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.cpu:
         raise ValueError("--cpu: this build has no CPU path (the hot path runs on MI355X only)")
+    if args.accumulation_steps < 1:
+        raise ValueError("--accumulation_steps must be >= 1, got %d" % args.accumulation_steps)
     if args.checkpoint is None and args.model_config is None:
         raise ValueError("--model_config and --checkpoint cannot be empty at the same time")
     if args.synthetic <= 0 and not args.dataset:

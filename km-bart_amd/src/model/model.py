@@ -503,7 +503,18 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         return self.to(torch.device("cuda", torch.cuda.current_device() if device is None else device))
 
     def zero_grad(self, set_to_none=False):
-        pass  # every gradient is overwritten by the next backward (reference zeroes after forward, training.py:136)
+        """Without accumulation every gradient is overwritten by the next backward and this changes nothing (the reference zeroes
+        after forward, training.py:136).  With accumulate_gradients() it makes the next backward start a new sum."""
+        if self._engine is not None:
+            self._engine.zero_grad()
+
+    def accumulate_gradients(self, on=True):
+        """on: every `loss.backward()` ADDS its gradients to `p.grad` (the engine's gradient arena) until `zero_grad()` /
+        `optimizer.zero_grad()`, as torch's does; off (the default): every backward overwrites them.  The engine keeps a second
+        gradient-sized buffer while this is on (Engine.grad_accumulation).  Under kmbart.parallel.DistributedDataParallel run all
+        micro-batches but the group's last inside its no_sync()."""
+        self._need_engine().grad_accumulation(on)
+        return self
 
     @property
     def device(self):

@@ -6,7 +6,16 @@ One deliberate difference in timing, none in content: the reference reads `loss.
 (training.py:134), which stalls the host until the GPU has drained and leaves the GPU idle while the host enqueues
 the next ~600 launches.  Here step i's loss is read AFTER step i+1 has been enqueued (the last one after the loop), so
 log lines / TensorBoard points / the returned epoch mean carry the same values, one step later.  A `callback` gets
-called in step order as in the reference; it forces the pending loss to be read first."""
+called in step order as in the reference; it forces the pending loss to be read first.
+
+Gradient accumulation (`args.accumulation_steps = N > 1`, not in the reference): the batches of the loader are micro-batches, taken in
+groups of N (the last group of an epoch may be shorter).  `optimizer.zero_grad()` runs on a group's first micro-batch, every
+micro-batch runs `(loss / N).backward()` -- the mean over the group of the micro-batches' mean losses; a short last group is still
+divided by N -- and `optimizer.step()` runs on the group's last one.  Under the data-parallel wrapper the other micro-batches run
+inside its `no_sync()`: one gradient exchange per optimizer step.  Log lines, the callback and the returned epoch mean stay per
+micro-batch and carry the unscaled loss; the gradient-norm line appears on optimizer steps only."""
+import contextlib
+import sys
 from datetime import datetime
 
 import torch
@@ -44,12 +53,50 @@ def _attach(model, optimizer, ok):
         model.attach_optimizer(optimizer)
 
 
-def _release(model, optimizer):
-    """The fusions above hold only inside these loops: afterwards `loss.backward()` is a plain backward again (gradient
-    accumulation, clip_grad_norm_, a diagnostic backward) and `optimizer.step()` a plain step."""
+def _accumulation_steps(args):
+    n = getattr(args, "accumulation_steps", 1)
+    n = 1 if n is None else int(n)
+    if n < 1:
+        raise ValueError("accumulation_steps must be >= 1, got %d" % n)
+    return n
+
+
+def _micro_step(i, n_steps, n_accum):
+    """(first, last) of micro-batch i of a loader of n_steps batches taken in groups of n_accum: zero_grad runs on a group's first
+    micro-batch, the optimizer steps on its last -- which is also the loader's last batch when the final group is short."""
+    return i % n_accum == 0, (i % n_accum == n_accum - 1 or i == n_steps - 1)
+
+
+def _accumulate(model, on):
+    """Switches the engine's gradient accumulation (model.accumulate_gradients, through a data-parallel wrapper's .module)."""
+    target = model if hasattr(model, "accumulate_gradients") else getattr(model, "module", None)
+    if not hasattr(target, "accumulate_gradients"):
+        raise RuntimeError("accumulation_steps > 1 needs a model with accumulate_gradients(): a backward of this engine overwrites "
+                           "the gradients, nothing outside it can add them up")
+    target.accumulate_gradients(on)
+
+
+def _sync_scope(model, sync):
+    """The data-parallel wrapper's no_sync() around a micro-batch that is not its group's last; nothing otherwise."""
+    if not sync and hasattr(model, "no_sync"):
+        return model.no_sync()
+    return contextlib.nullcontext()
+
+
+def _release(model, optimizer, accumulating=False):
+    """The fusions above hold only inside these loops: afterwards `optimizer.step()` is a plain step and `loss.backward()` a plain
+    backward that OVERWRITES the gradients again (clip_grad_norm_, a diagnostic backward; accumulation the loop switched on is
+    switched off here -- a loop of the caller's own asks for it with model.accumulate_gradients())."""
+    failing = sys.exc_info()[0] is not None   # (called from the loops' `finally`: an error of the loop's is on its way out)
     _allow_overlap(optimizer, False)
     if hasattr(model, "detach_optimizer"):
         model.detach_optimizer()
+    if accumulating:
+        try:
+            _accumulate(model, False)
+        except Exception:
+            if not failing:   # (else the loop's error is the one to report: it may have left a forward without its backward)
+                raise
 
 
 def _features(feats, device):
@@ -59,15 +106,18 @@ def _features(feats, device):
 
 def fine_tune(epoch, model, train_loader, optimizer, device, args, logger=None, callback=None, log_interval=1,
               tb_writer=None, tb_interval=1, scaler=None):
+    n_accum = _accumulation_steps(args)
     try:
+        if n_accum > 1:
+            _accumulate(model, True)
         return _fine_tune(epoch, model, train_loader, optimizer, device, args, logger, callback, log_interval, tb_writer,
-                          tb_interval, scaler)
+                          tb_interval, scaler, n_accum)
     finally:
-        _release(model, optimizer)
+        _release(model, optimizer, n_accum > 1)
 
 
 def _fine_tune(epoch, model, train_loader, optimizer, device, args, logger, callback, log_interval, tb_writer, tb_interval,
-               scaler):
+               scaler, n_accum=1):
     n_steps = len(train_loader)
     model.train()
     t0 = datetime.now()
@@ -106,16 +156,23 @@ def _fine_tune(epoch, model, train_loader, optimizer, device, args, logger, call
                 answer_attention_mask=_on(batch, "answer_attention_mask", device),
             )
             loss = outputs[0]
-        optimizer.zero_grad()
-        if use_amp and scaler is not None:
-            scaler.scale(loss).backward()
-            scaler.step(optimizer)
-            scaler.update()
-        else:
-            loss.backward()
-            optimizer.step()
+        first, last = _micro_step(i, n_steps, n_accum)
+        if first:
+            optimizer.zero_grad()
+        micro_loss = loss if n_accum == 1 else loss / n_accum
+        with _sync_scope(model, last):
+            if use_amp and scaler is not None:
+                scaler.scale(micro_loss).backward()
+            else:
+                micro_loss.backward()
+        if last:
+            if use_amp and scaler is not None:
+                scaler.step(optimizer)
+                scaler.update()
+            else:
+                optimizer.step()
         report(pending)                       # step i-1, while step i runs on the GPU
-        pending = (i, loss.detach(), None, _step_record(optimizer))
+        pending = (i, loss.detach(), None, _step_record(optimizer) if last else None)
         if callback is not None:
             report(pending)
             pending = None
@@ -132,15 +189,18 @@ def pretrain(epoch, model, train_loader, optimizer, device, args, logger=None, c
              tb_writer=None, tb_interval=1, scaler=None):
     """Multi-task pre-training loop with the reference's contract (reference src/training.py:9-93): the model
     returns a dict of losses as outputs[0]; `loss` drives backward, the others are logged."""
+    n_accum = _accumulation_steps(args)
     try:
+        if n_accum > 1:
+            _accumulate(model, True)
         return _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callback, log_interval, tb_writer,
-                         tb_interval, scaler)
+                         tb_interval, scaler, n_accum)
     finally:
-        _release(model, optimizer)
+        _release(model, optimizer, n_accum > 1)
 
 
 def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callback, log_interval, tb_writer, tb_interval,
-              scaler):
+              scaler, n_accum=1):
     n_steps = len(train_loader)
     model.train()
     t0 = datetime.now()
@@ -189,16 +249,24 @@ def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callb
         )
         losses = outputs[0]
         loss = losses["loss"]
-        optimizer.zero_grad()
-        if use_amp and scaler is not None:
-            scaler.scale(loss).backward()
-            scaler.step(optimizer)
-            scaler.update()
-        else:
-            loss.backward()
-            optimizer.step()
+        first, last = _micro_step(i, n_steps, n_accum)
+        if first:
+            optimizer.zero_grad()
+        micro_loss = loss if n_accum == 1 else loss / n_accum
+        with _sync_scope(model, last):
+            if use_amp and scaler is not None:
+                scaler.scale(micro_loss).backward()
+            else:
+                micro_loss.backward()
+        if last:
+            if use_amp and scaler is not None:
+                scaler.step(optimizer)
+                scaler.update()
+            else:
+                optimizer.step()
         report(pending)
-        pending = (i, loss.detach(), {k: v.detach() for k, v in losses.items() if k != "loss"}, _step_record(optimizer))
+        pending = (i, loss.detach(), {k: v.detach() for k, v in losses.items() if k != "loss"},
+                   _step_record(optimizer) if last else None)
         if callback is not None:
             report(pending)
             pending = None
