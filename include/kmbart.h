@@ -502,6 +502,30 @@ int kmb_greedy_step(const float* logits, int ld, int V, int R, int ban_token, in
 int kmb_gen_greedy_step(kmb_handle* h, const float* logits, int ld, int ban_token, int64_t* unfinished, int64_t pad_token,
                         int64_t eos_token, int64_t* next_tokens, int64_t* ids, int t, int ld_ids, int32_t* flag, float* logprob_sum,
                         float* logprob_out, int embed_step, void* stream);
+/* generate()'s score processors on one decode step's logits, in place, in front of kmb_greedy_step / kmb_sample_step (transformers
+ * 3.0.2 postprocess_next_token_scores as _generate_no_beam_search applies it, in its order; the arguments the reference validates in
+ * src/model/mixins.py:150-235).  ONE launch, one workgroup per row, no pass over [R, V]; stateless like kmb_greedy_step.  Per row
+ * r < R of logits [R, ld] (fp32, V real columns), with the row's tokens so far ids[r * ld_ids + 0 .. t) (int64; t = the column the
+ * step behind this call writes; a token outside [0, V) is dropped from the row as if it had not been generated):
+ *   repetition_penalty p != 1: every DISTINCT token of the row once, v = logits[r, token] becomes v < 0 ? v * p : v * (1 / p), the
+ *     reciprocal rounded to fp32 once (what torch's device kernel computes for tensor / python_scalar);
+ *   no_repeat_ngram_size n > 0 with t + 1 >= n: every j <= t - n whose n - 1 tokens equal the row's last n - 1 sets
+ *     logits[r, row[j + n - 1]] = -inf (n == 1: every token of the row);
+ *   bad words: sequence s = bad_tokens[bad_offsets[s] .. bad_offsets[s + 1]) (int32, device; n_bad + 1 ascending offsets), head =
+ *     all but its last token: the last token is set to -inf when the head is empty, or len(head) <= R (the length test of 3.0.2's
+ *     calc_banned_bad_words_ids against the number of ROWS, kept) and len(head) <= t and the row ends with the head.  A last token
+ *     outside [0, V) bans nothing.
+ * Every row is processed, finished ones too.  Columns >= V and every word not named above keep their bits.  No atomics: a word
+ * has one penalty writer, the bans are idempotent stores behind a barrier.  Needs ld >= V, R >= 1, 1 <= t <= 1024, ld_ids >= t, a
+ * finite penalty >= 1, n >= 0, 0 <= n_bad <= 4096 (both tables with n_bad > 0); bad arguments fail with a message and launch nothing. */
+int kmb_logits_process(float* logits, int ld, int V, int R, const int64_t* ids, int ld_ids, int t, float repetition_penalty,
+                       int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets, int n_bad, void* stream);
+/* The decode loop's form of kmb_logits_process on the logits the last kmb_gen_step wrote (V and R are the handle's; needs kmb_gen_begin
+ * with num_beams == 1): the same edit.  When `logits` are the ones that step's statistics were taken for, the statistics are dropped
+ * (kmb_gen_stats_blocks() == 0 afterwards): they describe the unedited logits.  The embedding a later kmb_gen_greedy_step /
+ * kmb_gen_sample_step folds in is not affected. */
+int kmb_gen_logits_process(kmb_handle* h, float* logits, int ld, const int64_t* ids, int ld_ids, int t, float repetition_penalty,
+                           int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets, int n_bad, void* stream);
 /* One decode step of beam sampling (generate(do_sample=True, num_beams > 1): transformers 3.0.2 _generate_beam_search, sampling
  * branch, reached from the reference's --num_beams with --do_sample, src/generation.py:22-32), two launches, stateless
  * like kmb_beam_step.  Per row r = b * num_beams + j of logits [B * num_beams, ld] (fp32, V real columns, NaN read as -inf):

@@ -8,6 +8,7 @@
 #include "sample.h"
 #include "beam_sample.h"
 #include "greedy.h"
+#include "logits_process.h"
 
 extern "C" const char* kmb_last_error(void);
 int kmb_set_error(const char* msg);  // engine.cpp
@@ -385,6 +386,16 @@ int kmb_greedy_step(const float* logits, int ld, int V, int R, int ban_token, in
                  "greedy_step");
 }
 
+int kmb_logits_process(float* logits, int ld, int V, int R, const int64_t* ids, int ld_ids, int t, float repetition_penalty,
+                       int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets, int n_bad, void* stream) {
+  if (kmb_logits_process_validate("kmb_logits_process", logits, ld, V, R, ids, ld_ids, t, repetition_penalty, no_repeat_ngram_size,
+                                  bad_tokens, bad_offsets, n_bad) != 0)
+    return -1;
+  return hipfail(kmb_logits_process_launch(logits, ld, V, R, ids, ld_ids, t, repetition_penalty, no_repeat_ngram_size, bad_tokens,
+                                           bad_offsets, n_bad, (hipStream_t)stream),
+                 "logits_process");
+}
+
 int64_t kmb_beam_sample_scratch(int rows) { return (int64_t)kmb_beam_sample_scratch_floats(rows); }
 int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beams, const float* add, float temperature, int top_k,
                          float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
@@ -464,5 +475,24 @@ int kmb_greedy_validate(const char* who, const float* logits, int ld, int V, int
   if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
   if (unfinished && (pad_token < 0 || pad_token >= V)) return bad("pad_token must be a token id < V");
   if (ids && (t < 0 || t >= ld_ids)) return bad("need 0 <= t < ld_ids");
+  return 0;
+}
+
+// The argument checks of kmb_logits_process and kmb_gen_logits_process (`who` names the caller in the message).
+int kmb_logits_process_validate(const char* who, const float* logits, int ld, int V, int R, const int64_t* ids, int ld_ids, int t,
+                                float repetition_penalty, int no_repeat_ngram_size, const int32_t* bad_tokens,
+                                const int32_t* bad_offsets, int n_bad) {
+  char buf[256];
+  auto bad = [&](const char* what) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return kmb_set_error(buf);
+  };
+  if (!logits || !ids) return bad("logits and ids are required");
+  if (V < 1 || R < 1 || ld < V) return bad("need V >= 1, R >= 1, ld >= V");
+  if (t < 1 || t > KMB_PROCESS_MAX_T || ld_ids < t) return bad("need 1 <= t <= 1024 and ld_ids >= t");
+  if (!(repetition_penalty >= 1.f) || std::isinf(repetition_penalty)) return bad("repetition_penalty must be finite and >= 1");
+  if (no_repeat_ngram_size < 0) return bad("no_repeat_ngram_size must be >= 0");
+  if (n_bad < 0 || n_bad > KMB_PROCESS_MAX_BAD) return bad("need 0 <= n_bad <= 4096");
+  if (n_bad > 0 && (!bad_tokens || !bad_offsets)) return bad("bad_tokens and bad_offsets (n_bad + 1 of them) are required with n_bad > 0");
   return 0;
 }

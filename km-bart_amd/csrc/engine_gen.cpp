@@ -3,6 +3,7 @@
 #include "engine_internal.h"
 #include "beam_sample.h"
 #include "greedy.h"
+#include "logits_process.h"
 #include "sample.h"
 
 using namespace kmbi;
@@ -429,6 +430,23 @@ int kmb_gen_sample_step(kmb_handle* h, const float* logits, int ld, float temper
                                        pad_token, eos_token, next_tokens, ids, t, ld_ids, flag, info_out, logprob_sum, logprob_out,
                                        ld_logprob, (hipStream_t)stream, ep.arg()));
   gen_embed_done(h, ep);
+  return 0;
+}
+
+// The score processors of the decode loop (kmb_logits_process on the logits of the last kmb_gen_step, in place).  The statistics the
+// step's vocabulary projection left describe the logits as it wrote them: edited logits have none.
+int kmb_gen_logits_process(kmb_handle* h, float* logits, int ld, const int64_t* ids, int ld_ids, int t, float repetition_penalty,
+                           int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets, int n_bad, void* stream) {
+  if (!h) return fail("kmb_gen_logits_process: call kmb_gen_begin first");
+  auto& G = h->gen;
+  if (!G.active) return fail("kmb_gen_logits_process: call kmb_gen_begin first");
+  if (G.nb != 1) return fail("kmb_gen_logits_process: needs num_beams == 1, kmb_gen_begin had %d", G.nb);
+  if (kmb_logits_process_validate("kmb_gen_logits_process", logits, ld, h->V, G.R, ids, ld_ids, t, repetition_penalty,
+                                  no_repeat_ngram_size, bad_tokens, bad_offsets, n_bad) != 0)
+    return -1;
+  if (G.head_stats_for == logits) { G.head_stats_blocks = 0; G.head_stats_for = nullptr; }
+  HIPCHK(kmb_logits_process_launch(logits, ld, h->V, G.R, ids, ld_ids, t, repetition_penalty, no_repeat_ngram_size, bad_tokens,
+                                   bad_offsets, n_bad, (hipStream_t)stream));
   return 0;
 }
 

@@ -177,6 +177,8 @@ PROTOTYPES = {
     "kmb_greedy_step": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, i64, i64, c_p, c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p]),
     "kmb_gen_greedy_step": (C.c_int, [c_p, c_p, C.c_int, C.c_int, c_p, i64, i64, c_p, c_p, C.c_int, C.c_int, c_p, c_p, c_p, C.c_int,
                                       c_p]),
+    "kmb_logits_process": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
+    "kmb_gen_logits_process": (C.c_int, [c_p, c_p, C.c_int, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
     "kmb_beam_sample_step": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, f32, C.c_int, f32, C.c_int, c_p, C.c_int,
                                        C.c_int, c_p, C.c_int, c_p, c_p, c_p, c_p, C.c_int64, c_p]),
     "kmb_beam_sample_scratch": (C.c_int64, [C.c_int]),

@@ -975,6 +975,36 @@ class Engine:
                 check(self.lib.kmb_greedy_step(ptr(logits), logits.stride(0), V, R, *args, _stream()))
         return next_tokens
 
+    def process_logits(self, logits, ids, t, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words=None):
+        """generate()'s score processors on one decode step's logits, in place, in front of greedy_step / sample_step
+        (kmb_logits_process): repetition penalty, no-repeat n-grams and bad words from the rows' tokens ids[:, :t] (int64 [R, ld],
+        the id buffer the step tails keep; t = the column about to be written).  bad_words: (tokens int32, offsets int32
+        [n_bad + 1]) device tensors, the packed table, or None.  `logits` may be gen_step's padded view: the call then takes its
+        decode-loop form (kmb_gen_logits_process).  Only raw pointers are passed -- torch sees no in-place op, the logits'
+        _version stays the one gen_step left, and the step tail behind this call keeps its kmb_gen_* form with the folded
+        embedding."""
+        R, V = logits.shape[0], int(self.config.vocab_size)
+        assert logits.device == self.device and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1, \
+            "process_logits: bad logits"
+        assert ids.device == self.device and ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 \
+            and ids.shape[0] == R, "process_logits: bad ids"
+        btok = boff = None
+        n_bad = 0
+        if bad_words is not None:
+            btok, boff = bad_words
+            for x in (btok, boff):
+                assert x.device == self.device and x.dtype == torch.int32 and x.is_contiguous(), "process_logits: bad table"
+            n_bad = boff.numel() - 1
+            assert n_bad >= 0 and (n_bad == 0 or btok.numel() > 0)
+        with torch.cuda.device(self.device):
+            args = (ptr(ids), ids.stride(0), int(t), float(repetition_penalty), int(no_repeat_ngram_size),
+                    ptr(btok) if n_bad > 0 else None, ptr(boff) if n_bad > 0 else None, n_bad, _stream())
+            if logits is self.__dict__.get("_gen_logits"):
+                check(self.lib.kmb_gen_logits_process(self.h, ptr(logits), logits.stride(0), *args))
+            else:
+                check(self.lib.kmb_logits_process(ptr(logits), logits.stride(0), V, R, *args))
+        return logits
+
     def _topk_scratch_for(self, R):
         nscr = int(self.lib.kmb_logsoftmax_topk_scratch(R))
         scr = self.__dict__.get("_topk_scratch")

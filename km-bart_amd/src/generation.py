@@ -17,6 +17,11 @@ def generate_text(model, gen_loader, tokenizer, args, device, logger=None, log_i
     num_gen = args.num_gen
     with_scores = bool(getattr(args, "with_scores", False)) and args.num_beams == 1
     extra = {"return_logprobs": True} if with_scores else {}
+    # the score processors only when asked for: an `args` without them calls generate() as before
+    if getattr(args, "repetition_penalty", 1.0) != 1.0:
+        extra["repetition_penalty"] = args.repetition_penalty
+    if getattr(args, "no_repeat_ngram_size", 0) != 0:
+        extra["no_repeat_ngram_size"] = args.no_repeat_ngram_size
     for i, batch in enumerate(gen_loader):
         out = model.generate(
             input_ids=batch["input_ids"].to(device),

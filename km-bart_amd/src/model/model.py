@@ -227,6 +227,43 @@ def _one_beam_on_device(do_sample, processors_on, fp32, device_greedy):
     return not do_sample and not processors_on and not fp32 and bool(device_greedy)
 
 
+_PROCESS_MAX_T = 1024      # tokens of a row kmb_logits_process holds (csrc/logits_process.h)
+_PROCESS_MAX_BAD = 4096    # bad-word sequences of its table
+
+
+def _processors_on_device(num_beams, do_sample, processors_on, fp32, device_processors, device_greedy, device_sampling, max_length,
+                          table):
+    """Whether generate() applies its score processors (repetition_penalty / no_repeat_ngram_size / bad_words_ids) on the device
+    (Engine.process_logits in front of the greedy / sampling step) instead of taking the torch loop: opt-in (device_processors
+    is model._device_processors, falsy or absent: no), one beam only, not in the fp32 validation mode, the matching one-beam
+    device loop switched on (model._device_greedy / model._device_sampling), max_length <= 1024 (a row's tokens are held on
+    chip) and the bad words packed (`table`: what _pack_bad_words returned, None when it could not).  generate() then hands
+    `processors_on and not this` to _decode_route / _one_beam_on_device, which stay what they were."""
+    if not (processors_on and bool(device_processors)) or num_beams != 1 or fp32:
+        return False
+    if not bool(device_sampling if do_sample else device_greedy):
+        return False
+    return max_length <= _PROCESS_MAX_T and table is not None
+
+
+def _pack_bad_words(bad_words_ids, V):
+    """bad_words_ids as kmb_logits_process reads them: (tokens, offsets), the sequences flattened and len + 1 ascending offsets
+    (([], [0]) for None).  An empty inner list raises the reference's assertion (calc_banned_bad_words_ids).  None -- the torch
+    loop handles the call -- when a token lies outside [0, V), for more than 4096 sequences or one longer than 1024 tokens."""
+    tokens, offsets = [], [0]
+    if bad_words_ids is None:
+        return tokens, offsets
+    if len(bad_words_ids) > _PROCESS_MAX_BAD:
+        return None
+    for seq in bad_words_ids:
+        assert len(seq) > 0, "Banned words token sequences {} cannot have an empty list".format(bad_words_ids)
+        if len(seq) > _PROCESS_MAX_T or any(not 0 <= int(x) < V for x in seq):
+            return None
+        tokens.extend(int(x) for x in seq)
+        offsets.append(len(tokens))
+    return tokens, offsets
+
+
 def _forced_tokens(cur_len, max_length, bos_token_id, eos_token_id):
     """adjust_logits_during_generation (mixins.py:400-405) of a greedy beam search: the tokens forced at decode step cur_len, in
     the reference's order -- BOS on the first step, EOS on the last.  Both only when max_length == 2: the pipelined loop then
@@ -854,7 +891,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             "`bad_words_ids` is either `None` or a list of lists of tokens that should not be generated"
         # the score post-processing of transformers 3.0.2 (postprocess_next_token_scores: mixins.py:150-235 validates these
         # arguments, the loops apply them) needs every row's tokens on the host at every step: such searches take the
-        # step-by-step host loop (like beam sampling), not the pipelined one
+        # step-by-step host loop (like beam sampling), not the pipelined one -- unless model._device_processors moves them into
+        # the one-beam device loops (_processors_on_device below)
         processors_on = repetition_penalty != 1.0 or no_repeat_ngram_size > 0 or bad_words_ids is not None
         if not do_sample:
             if num_beams == 1:
@@ -881,6 +919,18 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         # blocks; every step is an eval forward on the exact-fp32 kernels over the rows' tokens so far (the encoder runs once,
         # its fp32 states are handed back in), and the host loops below do the reference's bookkeeping on those logits
         fp32 = bool(getattr(eng, "fp32_mode", False))
+        # opt-in (model._device_processors): the one-beam device loops apply the processors themselves (kmb_logits_process between
+        # the decode step and its tail), and the routing below sees a search without them
+        device_processors = getattr(self, "_device_processors", False)
+        table = _pack_bad_words(bad_words_ids, V) if (processors_on and device_processors) else None
+        on_device = _processors_on_device(num_beams, do_sample, processors_on, fp32, device_processors,
+                                          getattr(self, "_device_greedy", True), getattr(self, "_device_sampling", True),
+                                          max_length, table)
+        host_processors = processors_on and not on_device
+        processors = None
+        if on_device:   # the table goes up once, before the loop
+            bad = tuple(torch.tensor(x, dtype=torch.int32, device=dev) for x in table) if len(table[1]) > 1 else None
+            processors = (float(repetition_penalty), int(no_repeat_ngram_size), bad)
         step_logits = None
         if fp32:
             step_logits = self._fp32_step_fn(eng, input_ids, image_features, attention_mask, num_beams)
@@ -889,11 +939,11 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             # the device-side input validation is read back without waiting (the decode steps are enqueued while the encoder
             # still runs); a flagged batch raises at the first point where the host waits for the device anyway
             eng.check_inputs_begin()
-        route = _decode_route(num_beams, do_sample, processors_on, fp32, getattr(self, "_device_sampling", True),
+        route = _decode_route(num_beams, do_sample, host_processors, fp32, getattr(self, "_device_sampling", True),
                               getattr(self, "_sampler", None) is not None, V)
         if route == "device_sampling":
             return self._sample_on_device(eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id,
-                                          eos_token_id, decoder_start_token_id, return_logprobs)
+                                          eos_token_id, decoder_start_token_id, return_logprobs, processors)
         s = SimpleNamespace(B=B, V=V, R=B * num_beams, num_beams=num_beams, max_length=max_length, min_length=min_length,
                             do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, processors_on=processors_on,
                             repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -902,9 +952,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                             length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences)
         if route == "one_beam":
             want_scores = return_scores and not do_sample
-            if _one_beam_on_device(do_sample, processors_on, fp32, getattr(self, "_device_greedy", True)):
+            if _one_beam_on_device(do_sample, host_processors, fp32, getattr(self, "_device_greedy", True)):
                 return self._greedy_on_device(eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id,
-                                              want_scores, return_logprobs)
+                                              want_scores, return_logprobs, processors)
             return self._one_beam_loop(eng, s, step_logits, want_scores, return_logprobs)
         book = _BeamBook(s)
         if route == "pipelined_beams":
@@ -963,11 +1013,13 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         return (out, scores) if want_scores else out
 
     def _greedy_on_device(self, eng, B, max_length, min_length, pad_token_id, eos_token_id, decoder_start_token_id, want_scores,
-                          want_logprobs=False):
-        """generate(num_beams=1, do_sample=False) without score post-processing: every decode step is gen_step ->
-        kmb_gen_greedy_step (EOS ban, argmax, the token's log-probability, the finished-row bookkeeping and the next step's
-        embedding in one launch).  It reads the fp32 logits the torch path reads and breaks ties to the lowest index as
-        torch.argmax does: the same tokens.  model._device_greedy = False selects the torch path."""
+                          want_logprobs=False, processors=None):
+        """generate(num_beams=1, do_sample=False): every decode step is gen_step -> kmb_gen_greedy_step (EOS ban, argmax, the
+        token's log-probability, the finished-row bookkeeping and the next step's embedding in one launch).  It reads the fp32
+        logits the torch path reads and breaks ties to the lowest index as torch.argmax does: the same tokens.
+        model._device_greedy = False selects the torch path.  processors (model._device_processors; (repetition_penalty,
+        no_repeat_ngram_size, packed bad words)): kmb_gen_logits_process edits the step's logits from the id buffer in between,
+        one more launch per step; None: the score post-processing is off, nothing more is enqueued."""
         dev = eng.device
         eos = -1 if eos_token_id is None else int(eos_token_id)
         ids = torch.full((B, max_length), pad_token_id if pad_token_id is not None else 0, dtype=torch.long, device=dev)
@@ -983,6 +1035,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         while cur_len < max_length:
             # the tokens of step cur_len - 1 were embedded by the greedy step that chose them whenever it could (gen_step tells)
             logits = eng.gen_step(toks[(cur_len - 1) % 2], cur_len - 1)
+            if processors is not None:
+                eng.process_logits(logits, ids, cur_len, *processors)
             ban = eos if (eos >= 0 and cur_len < min_length) else -1
             eng.greedy_step(logits, ban_token=ban, unfinished=unfinished, pad_token=pad_token_id if unfinished is not None else 0,
                             eos_token=eos, next_tokens=toks[cur_len % 2], ids=ids, t=cur_len, flag=dflags[cur_len:cur_len + 1],
@@ -1111,9 +1165,9 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             cur_len += 1
 
     def _sample_on_device(self, eng, B, V, max_length, min_length, temperature, top_k, top_p, pad_token_id, eos_token_id,
-                          decoder_start_token_id, want_logprobs=False):
-        """generate(do_sample=True, num_beams=1) without score post-processing: every decode step is gen_step -> Exp(1)
-        noise -> kmb_gen_sample_step (EOS ban, temperature, top-k, top-p, draw, the finished-row bookkeeping, the next step's
+                          decoder_start_token_id, want_logprobs=False, processors=None):
+        """generate(do_sample=True, num_beams=1): every decode step is gen_step -> [kmb_gen_logits_process, with `processors` as
+        in _greedy_on_device ->] Exp(1) noise -> kmb_gen_sample_step (EOS ban, temperature, top-k, top-p, draw, the finished-row bookkeeping, the next step's
         embedding and, with want_logprobs, the token's log-probability under the filtered distribution, in one launch).
         The noise is drawn as torch.multinomial(probs, 1) draws it ([B, V] exponential_ on the default generator), so a
         seeded run consumes the random stream the torch path consumes and picks the same tokens except where fp32 rounding
@@ -1133,6 +1187,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         while cur_len < max_length:
             # the tokens of step cur_len - 1 were embedded by the sampling step that drew them whenever it could (gen_step tells)
             logits = eng.gen_step(toks[(cur_len - 1) % 2], cur_len - 1)
+            if processors is not None:
+                eng.process_logits(logits, ids, cur_len, *processors)
             ban = eos if (eos >= 0 and cur_len < min_length) else -1
             noise.exponential_(1)
             eng.sample_step(logits, noise, temperature, top_k, top_p, ban_token=ban, unfinished=unfinished,

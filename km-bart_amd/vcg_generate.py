@@ -32,6 +32,8 @@ def main(args):
     logger = Logger(args.log_dir)
     model = MultiModalBartForConditionalGeneration.from_pretrained(args.checkpoint)
     model.to(device)
+    if args.device_processors:
+        model._device_processors = True
     tokenizer = IdTokenizer()
     loader = []
     if args.synthetic > 0:
@@ -73,6 +75,11 @@ def parse_args(argv=None):
     p.add_argument("--top_k", default=0, type=int)
     p.add_argument("--with_scores", action="store_true",
                    help="with --num_beams 1: add \"scores\" to every record, the generations' sums of token log-probabilities")
+    p.add_argument("--repetition_penalty", default=1.0, type=float, help="generate()'s repetition_penalty (>= 1; 1: off)")
+    p.add_argument("--no_repeat_ngram_size", default=0, type=int, help="generate()'s no_repeat_ngram_size (0: off)")
+    p.add_argument("--device_processors", action="store_true",
+                   help="with --num_beams 1: apply the two options above on the device inside the pipelined decode loop "
+                        "(model._device_processors) instead of taking the torch loop")
     p.add_argument("--gpu_num", default=1, type=int)
     p.add_argument("--cpu", action="store_true")
     p.add_argument("--amp", action="store_true")
