@@ -522,8 +522,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const KmbGemm p) {
 //   phase B: MFMAs of k-half 1  ||  ds_reads of stage t+1's k-half 0  ||  DMA of stage t+2 into the freed buffer
 // with sched_group_barrier interleaving DS / VMEM issue between the MFMAs.  DMA sources are a uniform (SGPR) tile
 // base that advances per K step plus a per-lane 32-bit offset computed once.
-template <bool KC>
+// ROWS: rows (columns) of the tile, 128 or 256 -- 16 or 32 pieces of 1 KiB, four per wave of a 4- or 8-wave workgroup; a
+// token-major image's K row is ROWS / 8 lanes wide
+template <bool KC, int ROWS = 128>
 __device__ __forceinline__ void dma_offsets(uint32_t (&off)[4], int ld, int r0, int R, int wave, int lane) {
+  static_assert(ROWS == 128 || ROWS == 256, "128- or 256-row tiles");
+  constexpr int LSH = ROWS == 128 ? 4 : 5, LPR = 1 << LSH;   // lanes per K row of the token-major image: 16 or 32
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int piece = wave * 4 + i;
@@ -534,8 +538,8 @@ __device__ __forceinline__ void dma_offsets(uint32_t (&off)[4], int ld, int r0, 
       grow = grow < R ? grow : R - 1;
       off[i] = (uint32_t)(((grow - r0) * ld + c * 8) * 2);
     } else {
-      const int krow = piece * 4 + (lane >> 4);
-      const int ps = lane & 15;
+      const int krow = piece * (64 / LPR) + (lane >> LSH);
+      const int ps = lane & (LPR - 1);
       const int c32 = (ps >> 1) ^ swz_nkc(krow);
       int m = r0 + c32 * 16 + (ps & 1) * 8;
       const int mlast = ((R - 1) >> 3) << 3;
@@ -545,17 +549,11 @@ __device__ __forceinline__ void dma_offsets(uint32_t (&off)[4], int ld, int r0, 
   }
 }
 
-// the same with the non-temporal cache policy (aux bit 1 = nt on gfx950): the line is allocated in L2 as the first to leave.  For
-// the STREAMED operand of a persistent launch (the activation panel: read by the column tiles of one round, never again) so
-// that it does not push the REUSED one (the weight panels, re-read every round) out of a 4 MB L2.  Experiment: -DKMB_A_NT.
-__device__ __forceinline__ void dma_piece_nt(const char* gbase, uint32_t off, char* lds_dst) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + off),
-                                   (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
-}
-
-// One 128x128 output tile (block `block` of `nblocks` of problem p): the body of gemm_kernel_v7 and of the grouped launch below
-template <bool A_KC, bool B_KC>
-__device__ __forceinline__ void v7_tile(const KmbGemm& p, char* smem, int block, int nblocks) {
+// One 128x128 output tile (block `block` of `nblocks` of problem p) through STAGES LDS stages: the body of gemm_kernel_v7 and of
+// the grouped launch below (two stages) and of gemm_kernel_v7d (four).  Same fragment reads, same MFMA order for either depth.
+template <bool A_KC, bool B_KC, int STAGES>
+__device__ __forceinline__ void tile128(const KmbGemm& p, char* smem, int block, int nblocks) {
+  static_assert(STAGES == 2 || STAGES == 4, "two or four LDS stages");
   KMB_STAMP(0);
   KMB_STAMP_ID();
   const int tid = threadIdx.x;
@@ -596,14 +594,7 @@ __device__ __forceinline__ void v7_tile(const KmbGemm& p, char* smem, int block,
   char* const dstA = smem + wave * 4096;            // this wave's 4 pieces of the A image (stage 0)
   char* const dstB = smem + A_TILE + wave * 4096;
 
-  // K step `ks` (relative to t_begin) of this tile -> LDS stage buffer; the tile base is forced into SGPRs so the
-  // loads take the saddr + 32-bit-voffset form (no per-piece 64-bit VALU address arithmetic)
-  auto uniform_ptr = [](const char* ptr) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-  };
+  // K step `ks` (relative to t_begin) of this tile -> LDS stage buffer; the tile base is uniform (SGPRs)
   auto dma_stage = [&](int ks, int stage_buf) {
     char* da = dstA + stage_buf * STAGE_BYTES;
     char* db = dstB + stage_buf * STAGE_BYTES;
@@ -615,178 +606,24 @@ __device__ __forceinline__ void v7_tile(const KmbGemm& p, char* smem, int block,
     for (int i = 0; i < 4; ++i) dma_piece(gb, offB[i], db + i * 1024);
   };
 
-  bf16x8 fa0[4], fb0[4], fa1[4], fb1[4];
-  dma_stage(0, 0);
-  if (nt > 1) {
-    dma_stage(1, 1);
-    __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8): stage 0 has landed
-  } else {
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-  }
-  __syncthreads();
-  KMB_STAMP(1);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) fa0[i] = read_frag<A_KC, true>(smem, wm * 4 + i, 0, r, g);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) fb0[j] = read_frag<B_KC, true>(smem + A_TILE, wn * 4 + j, 0, r, g);
-
-  constexpr int NDS = (A_KC ? 4 : 8) + (B_KC ? 4 : 8);  // ds_read instructions per fragment set
-  auto kstep = [&](int t, auto do_dma, auto do_next) {
-    const char* cur = smem + (t & 1) * STAGE_BYTES;
-    const char* nxt = smem + ((t + 1) & 1) * STAGE_BYTES;
-    // ---- phase A ----
-    if constexpr (!(A_KC && B_KC)) KMB_TR_SYNC();   // the (asm-read) fragments requested in phase B of the previous step have arrived
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa1[i] = read_frag<A_KC, true>(cur, wm * 4 + i, 1, r, g);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fb1[j] = read_frag<B_KC, true>(cur + A_TILE, wn * 4 + j, 1, r, g);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa0[i], fb0[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA first: they wait on phase B's reads, not on these
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      __builtin_amdgcn_sched_group_barrier(0x100, NDS / 4, 0);  // DS read
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);        // MFMA
-    }
-    __builtin_amdgcn_sched_group_barrier(0x100, NDS / 4, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0): the builtin (not inline asm) so the compiler's own
-                                         // wait tracking knows the fragments have arrived
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- phase B ----  (the DMA overwrites LDS the fragment reads may alias: reads first, DMA pieces behind them)
-    if (decltype(do_next)::value) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa0[i] = read_frag<A_KC, true>(nxt, wm * 4 + i, 0, r, g);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb0[j] = read_frag<B_KC, true>(nxt + A_TILE, wn * 4 + j, 0, r, g);
-    }
-    if (decltype(do_dma)::value) dma_stage(t + 2, t & 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa1[i], fb1[j], acc[i][j], 0, 0, 0);
-    if (decltype(do_next)::value && decltype(do_dma)::value) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x100, NDS / 4, 1);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 1);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x010, 2, 1);  // VMEM (LDS-DMA)
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 1);
-      }
-    } else if (decltype(do_next)::value) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x100, NDS / 4, 1);
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 1);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  using Yes = std::true_type;
-  using No = std::false_type;
-  int t = 0;
-  for (; t + 2 < nt; ++t) kstep(t, Yes{}, Yes{});
-  if (t + 1 < nt) { kstep(t, No{}, Yes{}); ++t; }
-  kstep(t, No{}, No{});
-  __syncthreads();
-  KMB_STAMP(2);
-  gemm_epilogue<256>(p, smem, acc, tid, wm, wn, r, g, row0, col0, slice);
-  KMB_STAMP(4);
-}
-
-template <bool A_KC, bool B_KC>
-__global__ __launch_bounds__(256, 2) void gemm_kernel_v7(const KmbGemm p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  v7_tile<A_KC, B_KC>(p, smem, (int)blockIdx.x, (int)gridDim.x);
-}
-
-// v7d ("deep", launch variant 5; round 5): the same tile with FOUR LDS stages instead of two, for launches that put at most one
-// workgroup on a CU (<= 256 workgroups: M <= 4096 rows of N = 768, the reference's default batch of 64).  There v7's K step
-// is not bound by the MFMAs (0.21 us for its 32 per wave) but by the latency of the ONE stage it has in flight -- about 1 us
-// per 64-deep step with nobody else on the CU to hide it (4096 x 768 x 3072: 52-57 us inside a b = 64 step = 48 steps).  Four
-// stages keep three in flight behind a counted wait (s_waitcnt vmcnt(16): the in-order return path guarantees the oldest
-// stage has landed); 128 KB of LDS, so one workgroup per CU by construction.  Same fragment reads, same MFMA order: bit-identical.
-template <bool A_KC, bool B_KC>
-__device__ __forceinline__ void v7d_tile(const KmbGemm& p, char* smem, int block, int nblocks) {
-  KMB_STAMP(0);
-  KMB_STAMP_ID();
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r = lane & 15, g = lane >> 4;
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int nsl = p.split_k > 1 ? p.split_k : 1;
-  const int bid = (p.tile_order & 1) ? xcd_remap(block, nblocks) : block;
-  const int ntl = tiles_n * ((p.M + BM - 1) / BM);
-  const bool slice_major = (p.tile_order & 4) != 0 && nsl > 1;   // see split_order_note
-  const int tile = slice_major ? bid % ntl : bid / nsl, slice = slice_major ? bid / ntl : bid % nsl;
-  const int tm = tile / tiles_n, tn = tile % tiles_n;
-  const int row0 = tm * BM, col0 = tn * BN;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nt_all = p.K / BK;
-  const int t_begin = (int)((long)nt_all * slice / nsl), t_end = (int)((long)nt_all * (slice + 1) / nsl);
-  const int nt = t_end - t_begin;
-
-  uint32_t offA[4], offB[4];
-  dma_offsets<A_KC>(offA, p.lda, row0, p.M, wave, lane);
-  dma_offsets<B_KC>(offB, p.ldb, col0, p.N, wave, lane);
-  const size_t stepA = A_KC ? (size_t)BK * 2 : (size_t)BK * p.lda * 2;
-  const size_t stepB = B_KC ? (size_t)BK * 2 : (size_t)BK * p.ldb * 2;
-  const char* gA = reinterpret_cast<const char*>(p.A) +
-                   (A_KC ? ((size_t)row0 * p.lda + (size_t)t_begin * BK) * 2 : (size_t)row0 * 2) +
-                   (A_KC ? 0 : (size_t)t_begin * stepA);
-  const char* gB = reinterpret_cast<const char*>(p.B) +
-                   (B_KC ? ((size_t)col0 * p.ldb + (size_t)t_begin * BK) * 2 : (size_t)col0 * 2) +
-                   (B_KC ? 0 : (size_t)t_begin * stepB);
-  constexpr int A_TILE = BM * BK * 2;
-  char* const dstA = smem + wave * 4096;            // this wave's 4 pieces of the A image (stage 0)
-  char* const dstB = smem + A_TILE + wave * 4096;
-
-  // K step `ks` (relative to t_begin) of this tile -> LDS stage buffer; the tile base is forced into SGPRs so the
-  // loads take the saddr + 32-bit-voffset form (no per-piece 64-bit VALU address arithmetic)
-  auto uniform_ptr = [](const char* ptr) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-  };
-  auto dma_stage = [&](int ks, int stage_buf) {
-    char* da = dstA + stage_buf * STAGE_BYTES;
-    char* db = dstB + stage_buf * STAGE_BYTES;
-    const char* ga = uniform_ptr(gA + (size_t)ks * stepA);
-    const char* gb = uniform_ptr(gB + (size_t)ks * stepB);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma_piece(ga, offA[i], da + i * 1024);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma_piece(gb, offB[i], db + i * 1024);
-  };
+  // s_waitcnt immediates: a wave has eight pieces per stage in flight, and the in-order return path guarantees that the oldest stage
+  // (stage 0 in the prologue, stage t + 1 in K step t) has landed once at most the pieces of the younger ones are outstanding
+  constexpr int VM24 = 0x4F78, VM16 = 0x4F70, VM8 = 0x0F78, VM0 = 0x0F70;   // vmcnt(24 | 16 | 8 | 0) alone (prologue)
+  constexpr int VM16_LGKM0 = 0x4070, VM8_LGKM0 = 0x0078, VM0_LGKM0 = 0x0070;   // ... with lgkmcnt(0) (K step)
 
   bf16x8 fa0[4], fb0[4], fa1[4], fb1[4];
   dma_stage(0, 0);
   if (nt > 1) dma_stage(1, 1);
-  if (nt > 2) dma_stage(2, 2);
-  if (nt > 3) dma_stage(3, 3);
-  // stage 0 has landed once at most the pieces of the younger stages (eight per wave and stage) are outstanding
-  if (nt > 3) __builtin_amdgcn_s_waitcnt(0x4F78);        // vmcnt(24)
-  else if (nt > 2) __builtin_amdgcn_s_waitcnt(0x4F70);   // vmcnt(16)
-  else if (nt > 1) __builtin_amdgcn_s_waitcnt(0x0F78);   // vmcnt(8)
-  else __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0)
-  __builtin_amdgcn_s_barrier();   // (not __syncthreads(): its fence is a vmcnt(0) -- the three younger stages stay in flight here)
+  if constexpr (STAGES == 4) {
+    if (nt > 2) dma_stage(2, 2);
+    if (nt > 3) dma_stage(3, 3);
+  }
+  if (STAGES == 4 && nt > 3) __builtin_amdgcn_s_waitcnt(VM24);
+  else if (STAGES == 4 && nt > 2) __builtin_amdgcn_s_waitcnt(VM16);
+  else if (nt > 1) __builtin_amdgcn_s_waitcnt(VM8);
+  else __builtin_amdgcn_s_waitcnt(VM0);
+  if constexpr (STAGES == 2) __syncthreads();
+  else __builtin_amdgcn_s_barrier();   // (not __syncthreads(): its fence is a vmcnt(0) -- the three younger stages stay in flight here)
   KMB_STAMP(1);
 #pragma unroll
   for (int i = 0; i < 4; ++i) fa0[i] = read_frag<A_KC, KMB_TR_ALL>(smem, wm * 4 + i, 0, r, g);
@@ -794,12 +631,12 @@ __device__ __forceinline__ void v7d_tile(const KmbGemm& p, char* smem, int block
   for (int j = 0; j < 4; ++j) fb0[j] = read_frag<B_KC, KMB_TR_ALL>(smem + A_TILE, wn * 4 + j, 0, r, g);
 
   constexpr int NDS = (A_KC ? 4 : 8) + (B_KC ? 4 : 8);  // ds_read instructions per fragment set
-  // in_flight: stages younger than t + 1 that may still be outstanding at this step's wait (2, 1 or 0)
+  // in_flight: stages younger than t + 1 that may still be outstanding at this step's wait (STAGES - 2 at most)
   auto kstep = [&](int t, auto do_dma, auto do_next, auto in_flight) {
-    const char* cur = smem + (t & 3) * STAGE_BYTES;
-    const char* nxt = smem + ((t + 1) & 3) * STAGE_BYTES;
+    const char* cur = smem + (t & (STAGES - 1)) * STAGE_BYTES;
+    const char* nxt = smem + ((t + 1) & (STAGES - 1)) * STAGE_BYTES;
     // ---- phase A ----
-    if constexpr (KMB_TR_ALL && !(A_KC && B_KC)) KMB_TR_SYNC();
+    if constexpr (KMB_TR_ALL && !(A_KC && B_KC)) KMB_TR_SYNC();   // the (asm-read) fragments requested in phase B of the previous step have arrived
 #pragma unroll
     for (int i = 0; i < 4; ++i) fa1[i] = read_frag<A_KC, KMB_TR_ALL>(cur, wm * 4 + i, 1, r, g);
 #pragma unroll
@@ -820,9 +657,9 @@ __device__ __forceinline__ void v7d_tile(const KmbGemm& p, char* smem, int block
     __builtin_amdgcn_sched_barrier(0);
     // lgkmcnt(0) + vmcnt(8 x in_flight): stage t + 1 has landed; the builtin (not inline asm) so the compiler's own wait
     // tracking knows the fragments have arrived
-    if (decltype(in_flight)::value == 2) __builtin_amdgcn_s_waitcnt(0x4070);
-    else if (decltype(in_flight)::value == 1) __builtin_amdgcn_s_waitcnt(0x0078);
-    else __builtin_amdgcn_s_waitcnt(0x0070);
+    if (decltype(in_flight)::value == 2) __builtin_amdgcn_s_waitcnt(VM16_LGKM0);
+    else if (decltype(in_flight)::value == 1) __builtin_amdgcn_s_waitcnt(VM8_LGKM0);
+    else __builtin_amdgcn_s_waitcnt(VM0_LGKM0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     // ---- phase B ----  (the DMA overwrites LDS the fragment reads may alias: reads first, DMA pieces behind them)
@@ -832,7 +669,7 @@ __device__ __forceinline__ void v7d_tile(const KmbGemm& p, char* smem, int block
 #pragma unroll
       for (int j = 0; j < 4; ++j) fb0[j] = read_frag<B_KC, KMB_TR_ALL>(nxt + A_TILE, wn * 4 + j, 0, r, g);
     }
-    if (decltype(do_dma)::value) dma_stage(t + 4, t & 3);   // into the buffer this step has just read for the last time
+    if (decltype(do_dma)::value) dma_stage(t + STAGES, t & (STAGES - 1));   // into the buffer this step has just read for the last time
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -864,10 +701,15 @@ __device__ __forceinline__ void v7d_tile(const KmbGemm& p, char* smem, int block
   using I1 = std::integral_constant<int, 1>;
   using I0 = std::integral_constant<int, 0>;
   int t = 0;
-  for (; t + 4 < nt; ++t) kstep(t, Yes{}, Yes{}, I2{});                // stages t + 1 .. t + 3 outstanding, t + 4 requested
-  if (nt - t == 4) { kstep(t, No{}, Yes{}, I2{}); ++t; }
-  if (nt - t == 3) { kstep(t, No{}, Yes{}, I1{}); ++t; }
-  if (nt - t == 2) { kstep(t, No{}, Yes{}, I0{}); ++t; }
+  // steady state: stages t + 1 .. t + STAGES - 1 outstanding, t + STAGES requested; then one rung per stage still in flight
+  for (; t + STAGES < nt; ++t) kstep(t, Yes{}, Yes{}, std::integral_constant<int, STAGES - 2>{});
+  if constexpr (STAGES == 4) {
+    if (nt - t == 4) { kstep(t, No{}, Yes{}, I2{}); ++t; }
+    if (nt - t == 3) { kstep(t, No{}, Yes{}, I1{}); ++t; }
+  }
+  // (the same test, "two steps left", in the form each depth has always been compiled with: written the other way hipcc lays out
+  // the whole K loop of that kernel differently)
+  if (STAGES == 2 ? t + 1 < nt : nt - t == 2) { kstep(t, No{}, Yes{}, I0{}); ++t; }
   kstep(t, No{}, No{}, I0{});
   __syncthreads();
   KMB_STAMP(2);
@@ -875,13 +717,24 @@ __device__ __forceinline__ void v7d_tile(const KmbGemm& p, char* smem, int block
   KMB_STAMP(4);
 }
 
+template <bool A_KC, bool B_KC>
+__global__ __launch_bounds__(256, 2) void gemm_kernel_v7(const KmbGemm p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  tile128<A_KC, B_KC, 2>(p, smem, (int)blockIdx.x, (int)gridDim.x);
+}
 
+// v7d ("deep", launch variant 5; round 5): the same tile with FOUR LDS stages instead of two, for launches that put at most one
+// workgroup on a CU (<= 256 workgroups: M <= 4096 rows of N = 768, the reference's default batch of 64).  There v7's K step
+// is not bound by the MFMAs (0.21 us for its 32 per wave) but by the latency of the ONE stage it has in flight -- about 1 us
+// per 64-deep step with nobody else on the CU to hide it (4096 x 768 x 3072: 52-57 us inside a b = 64 step = 48 steps).  Four
+// stages keep three in flight behind a counted wait (s_waitcnt vmcnt(16): the in-order return path guarantees the oldest
+// stage has landed); 128 KB of LDS, so one workgroup per CU by construction.  Same fragment reads, same MFMA order: bit-identical.
 constexpr int LDS_DEEP = 4 * STAGE_BYTES;   // 128 KB (the epilogue's fp32 image + column sums fit in it)
 static_assert(LDS_DEEP >= LDS_BYTES, "the deep variant's epilogue uses the stage buffers");
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(256, 2) void gemm_kernel_v7d(const KmbGemm p) {   // (2: the register budget of gemm_kernel_v7 -- 128 KB of LDS keep it at one workgroup per CU; with the 512-register budget of (256, 1) hipcc rotated the accumulators through ~100 v_accvgpr moves per K step)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  v7d_tile<A_KC, B_KC>(p, smem, (int)blockIdx.x, (int)gridDim.x);
+  tile128<A_KC, B_KC, 4>(p, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Grouped weight gradients (round 5): ONE launch walks the 128x128 tiles of up to KMB_GEMM_GROUP_MAX independent problems of the
@@ -911,7 +764,7 @@ __global__ __launch_bounds__(256, 2) void gemm_group_wgrad_kernel(const KmbGemmG
     if (i < grp.n && b >= grp.first[i]) k = i;
   const int local = b - grp.first[k];
   if (local >= grp.blocks[k]) return;   // padding up to the next multiple of 8
-  v7_tile<false, false>(grp.p[k], smem, local, grp.blocks[k]);
+  tile128<false, false, 2>(grp.p[k], smem, local, grp.blocks[k]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -933,29 +786,6 @@ constexpr int LDS4 = ((2 * ST4 > 2 * EPI_BYTES) ? 2 * ST4 : 2 * EPI_BYTES) + CS5
 //   1: A(k0, rows 64-127) x B(k0)    || read A(k1, rows 0-63), B(k1)
 //   2: A(k1, rows 0-63) x B(k1)      || read A(k1, rows 64-127);  wait DMA(t+1), barrier
 //   3: A(k1, rows 64-127) x B(k1)    || read A/B(k0) of stage t+1, then DMA stage t+2 into the freed buffer
-template <bool KC>
-__device__ __forceinline__ void dma_offsets256(uint32_t (&off)[4], int ld, int r0, int R, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int piece = wave * 4 + i;  // 32 pieces of 1 KiB per 256-row tile
-    if (KC) {
-      const int row = piece * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ ((row >> 1) & 7);
-      int grow = r0 + row;
-      grow = grow < R ? grow : R - 1;
-      off[i] = (uint32_t)(((grow - r0) * ld + c * 8) * 2);
-    } else {
-      const int krow = piece * 2 + (lane >> 5);
-      const int ps = lane & 31;
-      const int c32 = (ps >> 1) ^ swz_nkc(krow);
-      int m = r0 + c32 * 16 + (ps & 1) * 8;
-      const int mlast = ((R - 1) >> 3) << 3;
-      m = m < R ? m : mlast;
-      off[i] = (uint32_t)((krow * ld + (m - r0)) * 2);
-    }
-  }
-}
-
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(512) void gemm_kernel_v8(const KmbGemm p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -986,20 +816,14 @@ __global__ __launch_bounds__(512) void gemm_kernel_v8(const KmbGemm p) {
   constexpr int A_BYTES = BM4 * BK * 2;
 
   uint32_t offA[4], offB[4];
-  dma_offsets256<A_KC>(offA, p.lda, row0, p.M, wave, lane);
-  dma_offsets256<B_KC>(offB, p.ldb, col0, p.N, wave, lane);
+  dma_offsets<A_KC, BM4>(offA, p.lda, row0, p.M, wave, lane);
+  dma_offsets<B_KC, BN4>(offB, p.ldb, col0, p.N, wave, lane);
   const size_t stepA = A_KC ? (size_t)BK * 2 : (size_t)BK * p.lda * 2;
   const size_t stepB = B_KC ? (size_t)BK * 2 : (size_t)BK * p.ldb * 2;
   const char* gA = reinterpret_cast<const char*>(p.A) + (A_KC ? (size_t)row0 * p.lda * 2 : (size_t)row0 * 2) + (size_t)t_begin * stepA;
   const char* gB = reinterpret_cast<const char*>(p.B) + (B_KC ? (size_t)col0 * p.ldb * 2 : (size_t)col0 * 2) + (size_t)t_begin * stepB;
   char* const dstA = smem + wave * 4096;
   char* const dstB = smem + A_BYTES + wave * 4096;
-  auto uniform_ptr = [](const char* ptr) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-  };
   // a stage is fetched in two halves one sub-phase apart: an LDS-DMA piece costs the issuing wave 60-180 cycles, and all
   // of a stage's pieces in sub-phase 3 made that sub-phase as long as two others (measured on v11: K loop -11 %)
   auto dma_a = [&](int ks, int stage_buf) {
@@ -1221,12 +1045,6 @@ __global__ __launch_bounds__(512) void gemm_kernel_allrows(const KmbGemm p, floa
     const int gcol = col < p.N ? col : p.N - 1;
     offB[i] = (uint32_t)(((gcol - col0) * p.ldb + pchunk * 8) * 2);
   }
-  auto uniform_ptr = [](const char* ptr) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-  };
   const char* const gA = reinterpret_cast<const char*>(p.A);
   const char* const gB = reinterpret_cast<const char*>(p.B) + (size_t)col0 * p.ldb * 2;
   auto dma_stage = [&](int s) {
@@ -1577,12 +1395,6 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
   constexpr int A_BYTES = BM4 * BK * 2;
   const size_t stepA = A_KC ? (size_t)BK * 2 : (size_t)BK * p.lda * 2;
   const size_t stepB = B_KC ? (size_t)BK * 2 : (size_t)BK * p.ldb * 2;
-  auto uniform_ptr = [](const char* ptr) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-  };
 
   // ---- DMA cursor: (tile, K step) of the next stage to fetch; runs two steps ahead of the MFMAs ----
   uint32_t offA[NPA], offB[NPB];
@@ -1656,35 +1468,22 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
   // cycles; sixteen of them in one 32-MFMA sub-phase made that sub-phase as long as the other three together)
   // (128-row wave blocks) where the 8 A and 8 B pieces of a stage go: A pieces [0, NA3) in sub-phase 3, the rest in the
   // next step's sub-phase 0; B pieces [0, NB3) in sub-phase 3, [NB3, NB3 + NB0) in sub-phase 0, the rest in sub-phase 1
-#ifndef KMB_V11_SPLIT
-#define KMB_V11_SPLIT 1
-#endif
-  constexpr int NA3 = KMB_V11_SPLIT == 3 ? NPA / 2 : NPA;
-  constexpr int NB3 = KMB_V11_SPLIT == 0 ? NPB : 0;
-  constexpr int NB0 = KMB_V11_SPLIT == 0 ? 0 : KMB_V11_SPLIT == 2 ? NPB / 2 : NPB;
-  constexpr int NB1 = NPB - NB3 - NB0;
+  // all of A in sub-phase 3, all of B in sub-phase 0: the best of the four splits measured (tools/gemm_stamps.py timelines; the
+  // other three, with the rest of v11's retired timing switches: tools/experiments/v11_timing_knobs.patch)
+  constexpr int NA3 = NPA, NB3 = 0, NB0 = NPB, NB1 = 0;
   constexpr int P3 = (NA3 + NB3) / 2, P0 = (NPA - NA3 + NB0) / 2, P1 = NB1 / 2;   // pairs of pieces per sub-phase
   auto dma_a = [&](int buf, int lo, int hi) {
     char* da = dstA + buf * STG;
-#ifndef KMB_V11_NODMA   // (timing experiment only: the K loop without its LDS-DMA -- results are garbage)
 #pragma unroll
-    for (int i = 0; i < NPA; ++i) {
-#ifdef KMB_A_NT
-      if (i >= lo && i < hi) { if constexpr (A_KC) dma_piece_nt(gA_d, offA[i], da + i * 1024); else dma_piece(gA_d, offA[i], da + i * 1024); }
-#else
+    for (int i = 0; i < NPA; ++i)
       if (i >= lo && i < hi) dma_piece(gA_d, offA[i], da + i * 1024);
-#endif
-    }
-#endif
     if (hi == NPA && lo < hi) gA_d = uniform_ptr(gA_d + stepA);
   };
   auto dma_b = [&](int buf, int lo, int hi) {
     char* db = dstB + buf * STG;
-#ifndef KMB_V11_NODMA
 #pragma unroll
     for (int i = 0; i < NPB; ++i)
       if (i >= lo && i < hi) dma_piece(gB_d, offB[i], db + i * 1024);
-#endif
     if (hi == NPB && lo < hi) {
       gB_d = uniform_ptr(gB_d + stepB);
       ++td;
@@ -1773,22 +1572,6 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       for (int j = 0; j < NJ; ++j) dst[j] = read_frag3<B_KC, BIMG, TRASM>(stage + A_BYTES, wn * NJ + j, kk, r, g);
     }
   };
-#ifdef KMB_V11_MFMA32_TIMING
-  // TIMING EXPERIMENT ONLY (diagnostic builds): the same fragments fed to 32x32x16 MFMAs -- half as many instructions,
-  // 32 cycles each, 8 of them holding the issue port.  Results are meaningless; the K loop's duration is the point.
-  f32x16 acc32[4][4];
-  static_assert(NJ == 8, "timing experiment: 128-column wave blocks only");
-  auto mma = [&](int half, const bf16x8 (&a)[4], const bf16x8 (&b)[8]) {
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          acc32[half * 2 + ii][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[jj * 2 + ks], a[ii * 2 + ks], acc32[half * 2 + ii][jj], 0, 0, 0);
-  };
-#define KMB_MF(n) ((n) / 2)
-#else
   auto mma = [&](int half, const bf16x8 (&a)[4], const bf16x8 (&b)[NJ]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -1796,8 +1579,6 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       for (int j = 0; j < NJ; ++j)
         acc[half * 4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[half * 4 + i][j], 0, 0, 0);  // C^T tile
   };
-#define KMB_MF(n) (n)
-#endif
 
   set_dma_tile(tile_d);
   if (PF_ON && pf_rt && wave == PFW) {   // steps 2 .. PFD + 1 of the first tile (issued before, so complete before, the stage pieces)
@@ -1835,14 +1616,6 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
     for (int i = 0; i < MH * 4; ++i)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef KMB_V11_MFMA32_TIMING
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc32[i][j][e] = 0.f;
-#endif
     [[maybe_unused]] const uint64_t kmb_t_loop = KMB_NOW();
     for (int t = 0; t < nt; ++t, ++it) {
       // publish the next tile to the other waves: written in step 1, behind step 1's barrier when the cursor reads it
@@ -1859,16 +1632,16 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       dma_a((it + 1) & 1, NA3, NPA);          // the rest of the stage whose first pieces went out in the previous
       dma_b((it + 1) & 1, NB3, NB3 + NB0);    // sub-phase 3
       mma(0, fa[0], fb[0]);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(4), 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         __builtin_amdgcn_sched_group_barrier(0x100, NDA / 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(4), 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
       }
 #pragma unroll
       for (int q = 0; q < P0; ++q) {
         __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);  // VMEM (LDS-DMA)
-        __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF((NM - 12) / (P0 > 0 ? P0 : 1)), 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, (NM - 12) / (P0 > 0 ? P0 : 1), 0);
       }
       __builtin_amdgcn_sched_barrier(0);
       // ---- sub-phase 1: A(k0, rows 64-127) x B(k0)  ||  read B(k1), A(k1, rows 0-63) ----
@@ -1878,26 +1651,26 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       dma_b((it + 1) & 1, NB3 + NB0, NPB);
       mma(1, fa[1], fb[0]);
       if constexpr (NM >= 24) {
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(6), 1);   // MFMAs first: their operands were read a sub-phase ago
+      __builtin_amdgcn_sched_group_barrier(0x008, 6, 1);   // MFMAs first: their operands were read a sub-phase ago
       __builtin_amdgcn_sched_group_barrier(0x100, NDB / 2, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(5), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, 5, 1);
       __builtin_amdgcn_sched_group_barrier(0x100, NDB / 2, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(5), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, 5, 1);
       __builtin_amdgcn_sched_group_barrier(0x100, NDA, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(4), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 1);
       } else {   // 16 / 12 MFMAs (64- / 48-column wave blocks of the eight-wave kernels)
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(NM / 4), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, NM / 4, 1);
       __builtin_amdgcn_sched_group_barrier(0x100, (NDB + 1) / 2, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(NM / 4), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, NM / 4, 1);
       __builtin_amdgcn_sched_group_barrier(0x100, NDB / 2, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(NM / 4), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, NM / 4, 1);
       __builtin_amdgcn_sched_group_barrier(0x100, NDA, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(NM / 4), 1);
+      __builtin_amdgcn_sched_group_barrier(0x008, NM / 4, 1);
       }
 #pragma unroll
       for (int q = 0; q < P1; ++q) {
         __builtin_amdgcn_sched_group_barrier(0x010, 2, 1);  // VMEM (LDS-DMA)
-        __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF((NM - 20) / (P1 > 0 ? P1 : 1)), 1);
+        __builtin_amdgcn_sched_group_barrier(0x008, (NM - 20) / (P1 > 0 ? P1 : 1), 1);
       }
       __builtin_amdgcn_sched_barrier(0);
       advance_cursor();
@@ -1923,9 +1696,9 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       if constexpr (TRASM) KMB_TR_SYNC();
       read_a(cur, 1, 1, fa[1]);
       mma(0, fa[0], fb[1]);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(8), 2);
+      __builtin_amdgcn_sched_group_barrier(0x008, 8, 2);
       __builtin_amdgcn_sched_group_barrier(0x100, NDA, 2);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(NM - 8), 2);
+      __builtin_amdgcn_sched_group_barrier(0x008, NM - 8, 2);
       __builtin_amdgcn_sched_barrier(0);
       {
         KMB_WAIT_BEGIN();
@@ -1947,13 +1720,13 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       dma_b(it & 1, 0, NB3);
       mma(1, fa[1], fb[1]);
       __builtin_amdgcn_sched_group_barrier(0x100, NDB, 3);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(4), 3);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 3);
       __builtin_amdgcn_sched_group_barrier(0x100, NDA, 3);
-      __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF(4), 3);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 3);
 #pragma unroll
       for (int q = 0; q < P3; ++q) {
         __builtin_amdgcn_sched_group_barrier(0x010, 2, 3);  // VMEM (LDS-DMA)
-        __builtin_amdgcn_sched_group_barrier(0x008, KMB_MF((NM - 8) / P3), 3);
+        __builtin_amdgcn_sched_group_barrier(0x008, (NM - 8) / P3, 3);
       }
       __builtin_amdgcn_sched_barrier(0);
       } else {
@@ -1996,14 +1769,6 @@ void gemm_kernel_v11(const KmbGemm p, uint32_t* sched, int dyn_first) {
       __builtin_amdgcn_sched_barrier(0);
       }
     }
-#ifdef KMB_V11_MFMA32_TIMING
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = acc32[i >> 1][j >> 1][((i & 1) * 2 + (j & 1)) * 4 + e];
-#endif
     // ---- epilogue of this tile (the next tile's first two stages are in flight / resident meanwhile) ----
     if constexpr (TRASM) KMB_TR_SYNC();   // the next tile's first fragments (asm reads of the last sub-phase) live across the epilogue: arrived before anything moves them
     [[maybe_unused]] const uint64_t kmb_t_epi = KMB_NOW();

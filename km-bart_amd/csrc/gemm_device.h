@@ -92,6 +92,15 @@ __device__ __forceinline__ s16x4 kmb_tr_read_asm_off(uint32_t addr) {
 #define KMB_TR_SYNC() do { } while (0)
 #endif
 
+// A wave-uniform pointer forced into SGPRs: LDS-DMA pieces issued from it take the saddr + 32-bit-voffset form (no per-piece
+// 64-bit VALU address arithmetic)
+__device__ __forceinline__ const char* uniform_ptr(const char* ptr) {
+  const uint64_t a = reinterpret_cast<uint64_t>(ptr);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
+}
+
 __device__ __forceinline__ void dma_piece(const char* gbase, uint32_t off, char* lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gbase + off),
                                    (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);

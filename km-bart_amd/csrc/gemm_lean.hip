@@ -27,13 +27,6 @@ constexpr int LN_LDS = 2 * LN_STG + 8 * LN_EPW;       // 160 KB
 
 enum { LN_BIAS = 0, LN_BIAS_RES = 1, LN_PLAIN = 2, LN_GELU = 3, LN_DGELU_CS = 4, LN_CE = 5, LN_SCORE = 6 };
 
-__device__ __forceinline__ const char* ln_uniform(const char* ptr) {
-  const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-}
-
 // LN_SCORE: the tied head's projection for SCORING a given sequence (kmb_score; reference scripts/filter_reason.py:24-52 takes the [B, T, V]
 // logits and runs log_softmax + a per-token pick over them).  The class stores NOTHING V-sized: per row and per 64-column wave block only the
 // block's maximum and its sum of exp(v - maximum), to p.row_sums[(row * p.row_sums_ld + col / 64) * 2 + {0, 1}]; score_rows_finish_kernel
@@ -177,20 +170,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto set_dma_tile = [&](int tile) {
     int tm, tn;
     decode_tile(tile, tm, tn);
-    gA_d = ln_uniform(reinterpret_cast<const char*>(p.A) + (size_t)tm * 256 * p.lda * 2);
-    gB_d = ln_uniform(reinterpret_cast<const char*>(p.B) + (B_KC ? (size_t)tn * 256 * p.ldb * 2 : (size_t)tn * 256 * 2));
+    gA_d = uniform_ptr(reinterpret_cast<const char*>(p.A) + (size_t)tm * 256 * p.lda * 2);
+    gB_d = uniform_ptr(reinterpret_cast<const char*>(p.B) + (B_KC ? (size_t)tn * 256 * p.ldb * 2 : (size_t)tn * 256 * 2));
     gA_tile = gA_d;
     pf_rows = (col_blocks ? tn % CB : tn) * pf_share;
     const int tx = (!dyn && tile + per < range1) ? tile + per : tile;   // (dynamic hand-out: the tile after this one is not known yet)
     decode_tile(tx, tm, tn);
-    gA_nx = ln_uniform(reinterpret_cast<const char*>(p.A) + (size_t)tm * 256 * p.lda * 2);
+    gA_nx = uniform_ptr(reinterpret_cast<const char*>(p.A) + (size_t)tm * 256 * p.lda * 2);
     pf_rows_nx = (col_blocks ? tn % CB : tn) * pf_share;
   };
   const unsigned touch_lds = kmb_lds_addr(smem + 2 * LN_STG + wave * LN_EPW + 2048);   // (word 0 of wave 0's image is next_slot)
   auto touch = [&](int ahead) {   // this wave's rows of the panel lines that the cursor will ask for `ahead` steps from now
     const int ps = td + ahead;
     const bool nx = ps >= nt;
-    const char* sbase = ln_uniform((nx ? gA_nx : gA_tile) + (size_t)(nx ? ps - nt : ps) * (BK * 2));
+    const char* sbase = uniform_ptr((nx ? gA_nx : gA_tile) + (size_t)(nx ? ps - nt : ps) * (BK * 2));
     int row = wave * pf_gs + (lane < pf_gs ? lane : pf_gs - 1);
     row = row < pf_share ? row : pf_share - 1;
     row += nx ? pf_rows_nx : pf_rows;
@@ -207,8 +200,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 4; ++i) dma_piece(gA_d, offA[i], da + i * 1024);
 #pragma unroll
     for (int i = 0; i < 4; ++i) dma_piece(gB_d, offB[i], db + i * 1024);
-    gA_d = ln_uniform(gA_d + BK * 2);
-    gB_d = ln_uniform(gB_d + stepB);
+    gA_d = uniform_ptr(gA_d + BK * 2);
+    gB_d = uniform_ptr(gB_d + stepB);
   };
   auto advance_cursor = [&]() {
     if (++td == nt) {

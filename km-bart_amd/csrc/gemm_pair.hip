@@ -41,13 +41,6 @@ enum { PR_BIAS = 0, PR_BIAS_RES = 1, PR_PLAIN = 2, PR_GELU = 3, PR_DGELU_CS = 4,
 // ds_read_b128 group ({0-3, 12-15, 20-27}, ... -- MI355X_MICROARCH.md, LDS) hit 16 distinct 16-byte bank groups
 __device__ __forceinline__ int pr_swz(int r) { return (0x78 >> (((r >> 2) & 3) * 2)) & 3; }
 
-__device__ __forceinline__ const char* pr_uniform(const char* ptr) {
-  const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
-}
-
 // PR_GDROP, a flag on the class number: the PR_GELU class with dropout in its epilogue (activation dropout), a kernel of its own,
 // gemm_kernel_pair<PR_GELU | PR_GDROP>: with both epilogues behind a run-time branch the GeLU kernel, which runs without scratch, needed 12
 // bytes of it.  Not an epilogue class: pr_class() answers PR_GELU with or without dropout, the launcher adds the flag.
@@ -119,13 +112,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) __a
   auto set_dma_tile = [&](int tile) {
     int tm, tn;
     decode_tile(tile, tm, tn);
-    gA_d = pr_uniform(reinterpret_cast<const char*>(p.A) + (size_t)tm * PR_BM * p.lda * 2);
-    gB_d = pr_uniform(reinterpret_cast<const char*>(p.B) + (size_t)tn * PR_BN * p.ldb * 2);
+    gA_d = uniform_ptr(reinterpret_cast<const char*>(p.A) + (size_t)tm * PR_BM * p.lda * 2);
+    gB_d = uniform_ptr(reinterpret_cast<const char*>(p.B) + (size_t)tn * PR_BN * p.ldb * 2);
     gA_tile = gA_d;
     pf_rows = (col_blocks ? tn % CB : tn) * pf_share;
     const int tx = tile + per < range1 ? tile + per : tile;
     decode_tile(tx, tm, tn);
-    gA_nx = pr_uniform(reinterpret_cast<const char*>(p.A) + (size_t)tm * PR_BM * p.lda * 2);
+    gA_nx = uniform_ptr(reinterpret_cast<const char*>(p.A) + (size_t)tm * PR_BM * p.lda * 2);
     pf_rows_nx = (col_blocks ? tn % CB : tn) * pf_share;
   };
   const unsigned touch_lds = kmb_lds_addr(smem + PR_LDS + wave * 256);
@@ -133,7 +126,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) __a
     const int ps = td - 1 + PR_PFD;                        // the step whose line is touched (with its odd neighbour's)
     const bool nx = ps >= nt;
     const int s2 = (nx ? ps - nt : ps) & ~1;
-    const char* sbase = pr_uniform((nx ? gA_nx : gA_tile) + s2 * (PR_BK * 2));
+    const char* sbase = uniform_ptr((nx ? gA_nx : gA_tile) + s2 * (PR_BK * 2));
     const int grp = (wave * 2 + (ps & 1)) * pf_gs;
     int row = grp + (lane < pf_gs ? lane : pf_gs - 1);
     row = row < pf_share ? row : pf_share - 1;
@@ -164,8 +157,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) __a
 #pragma unroll
     for (int i = 0; i < 2; ++i) dma_piece(gB_d, offB[i], db + i * 1024);
 #endif
-    gA_d = pr_uniform(gA_d + PR_BK * 2);
-    gB_d = pr_uniform(gB_d + PR_BK * 2);
+    gA_d = uniform_ptr(gA_d + PR_BK * 2);
+    gB_d = uniform_ptr(gB_d + PR_BK * 2);
     ++td;
   };
 

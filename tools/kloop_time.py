@@ -1,6 +1,6 @@
 """K-loop rate of a forced GEMM variant on the benchmark-batch forward shapes: back-to-back launches with the epilogue skipped
 (diagnostic build: KMB_GEMM_ABLATE), optionally from a timing-only library (KMB_LIB_PATH, e.g. `build.py --variant v11nodma KMB_DIAG
-KMB_V11_NODMA`: the loop without its LDS-DMA).  Forced variants bypass launch_config, so the tile order / prefetch bits are given here.
+KMB_V11_NODMA` with tools/experiments/v11_timing_knobs.patch applied, which holds that switch: the loop without its LDS-DMA).  Forced variants bypass launch_config, so the tile order / prefetch bits are given here.
 
     KMB_GEMM_VARIANT=11 python tools/kloop_time.py
 """
