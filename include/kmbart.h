@@ -526,6 +526,42 @@ int kmb_logits_process(float* logits, int ld, int V, int R, const int64_t* ids, 
  * kmb_gen_sample_step folds in is not affected. */
 int kmb_gen_logits_process(kmb_handle* h, float* logits, int ld, const int64_t* ids, int ld_ids, int t, float repetition_penalty,
                            int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets, int n_bad, void* stream);
+/* One step of greedy beam search with generate()'s score processors (transformers 3.0.2 _generate_beam_search: log_softmax, then
+ * postprocess_next_token_scores on the LOG-PROBABILITIES, then + beam score and the 2 * num_beams best per batch item): kmb_beam_step's
+ * arguments, outputs and selection, plus kmb_logits_process's processor arguments and the beams' token histories.  At most three
+ * launches (the rows' edit sets, kmb_beam_step's two), one when the token is forced; no pass over [R, V] beyond kmb_beam_step's one;
+ * stateless.  Per beam row r with tokens ids_in[r * ld_ids + 0 .. t) (int64):
+ *   s = log_softmax(logits[r, 0 .. V)), the log-sum-exp of the unedited row -- the edits never renormalise;
+ *   repetition_penalty p != 1: every distinct token x of the row once, s[x] = s[x] < 0 ? s[x] * p : s[x] * (1 / p);
+ *   -inf at ban_token, at the tokens no_repeat_ngram_size bans and at those the bad words ban (kmb_logits_process's rules, the bad
+ *     words' length test against R = B * num_beams rows); a ban wins over a penalty;
+ *   + add[r]; per batch item the k best of its num_beams * V scores by (value descending, beam * V + token ascending) into out, and
+ *   the next beams as kmb_beam_step chooses them.
+ * The selection is exact whatever the edits do to the order: the part launch selects among the unedited tokens only, the combine
+ * launch gathers the penalised tokens' logits and merges their scaled scores in.
+ * ids_out [B * num_beams, ld_ids] (another buffer than ids_in) receives the next beams' histories:
+ * ids_out[i][0 .. t) = ids_in[next_beam_idx[i]][0 .. t), ids_out[i][t] = next_tokens[i].
+ * force_token >= 0: kmb_beam_step's forced step (the forced token's log-probability is exactly 0, which the penalty leaves; the
+ * caller sees to it that no ban can hit a forced token): no edit, ids_out still advances.
+ * Needs kmb_beam_step's shape limits (k <= 16, num_beams <= 16, num_beams * k <= 256, ld % 4 == 0, ld <= 53248), V <= 65536,
+ * 1 <= t <= 1024, ld_ids > t, a finite penalty >= 1, n >= 0, 0 <= n_bad <= 4096 and scratch of
+ * kmb_beam_step_processed_scratch(B * num_beams, t, n_bad) floats; bad arguments fail with a message and launch nothing. */
+int64_t kmb_beam_step_processed_scratch(int rows, int t, int n_bad);
+int kmb_beam_step_processed(const float* logits, int ld, int V, int B, int num_beams, const float* add, int force_token, int ban_token,
+                            int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
+                            float* scratch, int64_t scratch_floats, const int64_t* ids_in, int64_t* ids_out, int ld_ids, int t,
+                            float repetition_penalty, int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets,
+                            int n_bad, void* stream);
+/* The decode loop's form of kmb_beam_step_processed on the logits the last kmb_gen_step wrote (V and B are the handle's), with
+ * kmb_gen_beam_step's reorder_step contract: reorder_step >= 0 also reorders the caches by next_beam_idx in the same launch and
+ * usually embeds next_tokens for step reorder_step + 1 (kmb_gen_embedded_step tells; kmb_gen_step(h, NULL, ...) uses them).  It never
+ * selects from the vocabulary projection's statistics (an edit can invalidate the block maxima their threshold comes from) and
+ * leaves them as they are: the logits are not edited. */
+int kmb_gen_beam_step_processed(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, int force_token, int ban_token,
+                                int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
+                                float* scratch, int64_t scratch_floats, const int64_t* ids_in, int64_t* ids_out, int ld_ids, int t,
+                                float repetition_penalty, int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets,
+                                int n_bad, int reorder_step, void* stream);
 /* One decode step of beam sampling (generate(do_sample=True, num_beams > 1): transformers 3.0.2 _generate_beam_search, sampling
  * branch, reached from the reference's --num_beams with --do_sample, src/generation.py:22-32), two launches, stateless
  * like kmb_beam_step.  Per row r = b * num_beams + j of logits [B * num_beams, ld] (fp32, V real columns, NaN read as -inf):

@@ -8,6 +8,7 @@
 #include "sample.h"
 #include "beam_sample.h"
 #include "greedy.h"
+#include "beam_process.h"
 #include "logits_process.h"
 
 extern "C" const char* kmb_last_error(void);
@@ -396,6 +397,23 @@ int kmb_logits_process(float* logits, int ld, int V, int R, const int64_t* ids, 
                  "logits_process");
 }
 
+int64_t kmb_beam_step_processed_scratch(int rows, int t, int n_bad) {
+  return (int64_t)kmb_beam_step_processed_scratch_floats(rows, t, n_bad);
+}
+int kmb_beam_step_processed(const float* logits, int ld, int V, int B, int num_beams, const float* add, int force_token, int ban_token,
+                            int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
+                            float* scratch, int64_t scratch_floats, const int64_t* ids_in, int64_t* ids_out, int ld_ids, int t,
+                            float repetition_penalty, int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets,
+                            int n_bad, void* stream) {
+  const KmbBeamProcess pr{ids_in, ids_out, ld_ids, t, repetition_penalty, no_repeat_ngram_size, bad_tokens, bad_offsets, n_bad};
+  if (kmb_beam_step_processed_validate("kmb_beam_step_processed", logits, ld, V, B, num_beams, force_token, ban_token, k, out, eos_token,
+                                       next_scores, next_tokens, next_beam_idx, scratch, scratch_floats, pr) != 0)
+    return -1;
+  return hipfail(kmb_beam_step_processed_launch(logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
+                                                next_tokens, next_beam_idx, scratch, (size_t)scratch_floats, pr, (hipStream_t)stream),
+                 "beam_step_processed");
+}
+
 int64_t kmb_beam_sample_scratch(int rows) { return (int64_t)kmb_beam_sample_scratch_floats(rows); }
 int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beams, const float* add, float temperature, int top_k,
                          float top_p, int ban_token, const float* noise, int ld_noise, int k, int32_t* out, int eos_token,
@@ -411,6 +429,37 @@ int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beam
 }
 
 }  // extern "C"
+
+// The argument checks of kmb_beam_step_processed and kmb_gen_beam_step_processed (`who` names the caller in the message): the
+// processors' as kmb_logits_process_validate, the beam step's shape limits, and what the kernels index with.
+int kmb_beam_step_processed_validate(const char* who, const float* logits, int ld, int V, int B, int num_beams, int force_token,
+                                     int ban_token, int k, const int32_t* out, int eos_token, const float* next_scores,
+                                     const int64_t* next_tokens, const int32_t* next_beam_idx, const float* scratch, int64_t scratch_floats,
+                                     const KmbBeamProcess& pr) {
+  char buf[256];
+  auto bad = [&](const char* what) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return kmb_set_error(buf);
+  };
+  if (!logits || !out || !next_scores || !next_tokens || !next_beam_idx || !scratch || !pr.ids_in || !pr.ids_out)
+    return bad("logits, out, next_scores, next_tokens, next_beam_idx, scratch, ids_in and ids_out are required");
+  if (pr.ids_in == pr.ids_out) return bad("ids_in and ids_out must be two buffers");
+  if (num_beams < 1 || num_beams > 16 || k < 1 || k > 16 || num_beams * k > 256)
+    return bad("need 1 <= k <= 16, 1 <= num_beams <= 16 and num_beams * k <= 256");
+  if (V < 1 || V > KMB_BEAM_EDIT_MAX_V || B < 0 || ld < V || (ld & 3) || ld > 4 * 4 * 13 * 256 || ((uintptr_t)logits & 15) ||
+      (int64_t)B * num_beams > 65535)
+    return bad("need 1 <= V <= 65536, B >= 0, B * num_beams <= 65535, V <= ld <= 53248, ld % 4 == 0 and 16-byte aligned logits");
+  if (B > 0 && kmb_logits_process_validate(who, logits, ld, V, B * num_beams, pr.ids_in, pr.ld_ids, pr.t, pr.repetition_penalty,
+                                           pr.no_repeat_ngram_size, pr.bad_tokens, pr.bad_offsets, pr.n_bad) != 0)
+    return -1;
+  if (pr.ld_ids <= pr.t) return bad("need ld_ids > t (column t is written)");
+  if (force_token < -1 || force_token >= V) return bad("force_token must be -1 or a token id < V");
+  if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
+  if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
+  if (scratch_floats < 0 || (size_t)scratch_floats < kmb_beam_step_processed_scratch_floats(B * num_beams, pr.t, pr.n_bad))
+    return bad("scratch needs kmb_beam_step_processed_scratch(B * num_beams, t, n_bad) floats");
+  return 0;
+}
 
 // The argument checks of kmb_beam_sample_step and kmb_gen_beam_sample_step (`who` names the caller in the message).
 int kmb_beam_sample_validate(const char* who, const float* logits, int ld, int V, int B, int num_beams, float temperature, int top_k,

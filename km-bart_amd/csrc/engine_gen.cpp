@@ -1,6 +1,7 @@
 // Generation: the decode workspace, kmb_gen_begin (encoder + cross-attention keys | values + weight packing), the decode step and the
 // step entry points that choose the next tokens.
 #include "engine_internal.h"
+#include "beam_process.h"
 #include "beam_sample.h"
 #include "greedy.h"
 #include "logits_process.h"
@@ -361,6 +362,34 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
                              ep.arg());
   if (e == hipErrorNotSupported) return fail("kmb_gen_beam_step: unsupported shape (k <= 16, num_beams <= 16, num_beams * k <= 256)");
   HIPCHK(e);
+  gen_embed_done(h, ep);
+  return fold ? gen_reordered(h, next_beam_idx, (hipStream_t)stream) : 0;
+}
+
+// The beam step of the decode loop with generate()'s score processors (kmb_beam_step_processed on the logits of the last kmb_gen_step),
+// with kmb_gen_beam_step's reorder / embedding contract.  The logits are not edited -- the head statistics stay what they are -- but an
+// edit can invalidate the block maxima the statistics path takes its threshold from: this step never selects from them.
+int kmb_gen_beam_step_processed(kmb_handle* h, const float* logits, int ld, int num_beams, const float* add, int force_token, int ban_token,
+                                int k, int32_t* out, int eos_token, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
+                                float* scratch, int64_t scratch_floats, const int64_t* ids_in, int64_t* ids_out, int ld_ids, int t,
+                                float repetition_penalty, int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets,
+                                int n_bad, int reorder_step, void* stream) {
+  if (!h) return fail("kmb_gen_beam_step_processed: call kmb_gen_begin first");
+  auto& G = h->gen;
+  if (!G.active) return fail("kmb_gen_beam_step_processed: call kmb_gen_begin first");
+  if (num_beams != G.nb) return fail("kmb_gen_beam_step_processed: num_beams %d, kmb_gen_begin had %d", num_beams, G.nb);
+  if (reorder_step >= G.Tmax) return fail("kmb_gen_beam_step_processed: reorder_step %d outside the cache (Tmax=%d)", reorder_step, G.Tmax);
+  // the stateless form's argument checks, before anything is launched or the generation state changes
+  const KmbBeamProcess pr{ids_in, ids_out, ld_ids, t, repetition_penalty, no_repeat_ngram_size, bad_tokens, bad_offsets, n_bad};
+  if (kmb_beam_step_processed_validate("kmb_gen_beam_step_processed", logits, ld, h->V, G.B, num_beams, force_token, ban_token, k, out,
+                                       eos_token, next_scores, next_tokens, next_beam_idx, scratch, scratch_floats, pr) != 0)
+    return -1;
+  const bool fold = reorder_step >= 0;
+  const KmbHistGather hg = gen_fold_hist(h, reorder_step);
+  const GenEmbedPlan ep = gen_embed_plan(h, fold ? reorder_step + 1 : -1, true);
+  HIPCHK(kmb_beam_step_processed_launch(logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
+                                        next_tokens, next_beam_idx, scratch, (size_t)scratch_floats, pr, (hipStream_t)stream,
+                                        fold ? &hg : nullptr, ep.arg()));
   gen_embed_done(h, ep);
   return fold ? gen_reordered(h, next_beam_idx, (hipStream_t)stream) : 0;
 }

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "logits_process.h"
+#include "process_row.h"
 
 namespace {
 
@@ -35,36 +36,12 @@ __global__ __launch_bounds__(kThreads) void logits_process_kernel(ProcessArgs a)
   __shared__ int kept;
   const int r = blockIdx.x, tid = threadIdx.x;
   float* row = a.logits + (size_t)r * a.ld;
-  const int64_t* idr = a.ids + (size_t)r * a.ld_ids;
-  int outside = 0;
-  for (int j = tid; j < a.t; j += kThreads) {
-    const int64_t v = idr[j];
-    const bool in = v >= 0 && v < (int64_t)a.V;
-    tok[j] = in ? (int)v : -1;
-    outside |= in ? 0 : 1;
-  }
-  int t = a.t;
-  if (__syncthreads_or(outside)) {
-    // tokens outside the vocabulary (never from generate()): one lane closes the gaps, in order
-    if (tid == 0) {
-      int w = 0;
-      for (int j = 0; j < a.t; ++j) {
-        const int x = tok[j];
-        if (x >= 0) tok[w++] = x;
-      }
-      kept = w;
-    }
-    __syncthreads();
-    t = kept;
-  }
+  const int t = process_row_load<kThreads>(a.ids + (size_t)r * a.ld_ids, a.t, a.V, tok, &kept, tid);
 
   if (a.penalise) {
     for (int j = tid; j < t; j += kThreads) {
-      const int x = tok[j];
-      bool first = true;
-      for (int i = 0; i < j; ++i)
-        if (tok[i] == x) { first = false; break; }
-      if (first) {
+      if (process_row_first(tok, j)) {
+        const int x = tok[j];
         const float v = row[x];
         row[x] = v < 0.f ? v * a.p : v * a.inv_p;
       }
@@ -74,26 +51,12 @@ __global__ __launch_bounds__(kThreads) void logits_process_kernel(ProcessArgs a)
 
   const int n = a.n;
   if (n > 0 && t + 1 >= n) {
-    const int tail = t + 1 - n;          // the row's last n - 1 tokens start here
-    for (int j = tid; j + n <= t; j += kThreads) {
-      bool same = true;
-      for (int k = 0; k < n - 1; ++k)
-        if (tok[j + k] != tok[tail + k]) { same = false; break; }
-      if (same) row[tok[j + n - 1]] = -INFINITY;
-    }
+    for (int j = tid; j + n <= t; j += kThreads)
+      if (process_row_ngram(tok, t, n, j)) row[tok[j + n - 1]] = -INFINITY;
   }
   for (int s = tid; s < a.n_bad; s += kThreads) {
-    const int b = a.bad_offsets[s], e = a.bad_offsets[s + 1];
-    if (b < 0 || e <= b) continue;       // an empty sequence: the packer refuses it
-    const int last = a.bad_tokens[e - 1], h = e - b - 1;
-    if (last < 0 || last >= a.V) continue;
-    bool ban = h == 0;
-    if (!ban && h <= a.R && h <= t) {
-      ban = true;
-      for (int k = 0; k < h; ++k)
-        if (tok[t - h + k] != a.bad_tokens[b + k]) { ban = false; break; }
-    }
-    if (ban) row[last] = -INFINITY;
+    const int last = process_row_bad_word(tok, t, a.V, a.R, a.bad_tokens, a.bad_offsets, s);
+    if (last >= 0) row[last] = -INFINITY;
   }
 }
 

@@ -6,6 +6,7 @@
 #include "kernels.h"
 #include "embed_row.h"
 #include "beam_fold.h"
+#include "beam_process.h"
 
 namespace {
 
@@ -598,7 +599,8 @@ __device__ __forceinline__ float wave_max_f32_dpp(float v) {
 // final result either way.
 template <int NV>
 __device__ __forceinline__ void wave_topk(const f32x4 (&x)[NV], int idx0, int chunks_left, int V, int ban, int k, int lane,
-                                          unsigned long long* cand) {
+                                          unsigned long long* cand, unsigned long long skip = 0ull) {
+  // skip: bit 4 j + e set -- element (j, e) is an edited token of a processed beam step, invalid like `ban` (and -inf in x)
   // idx0: index of x[0][0] of this thread; element (j, e) has index idx0 + 1024 j + e; valid iff j * 256 < chunks_left
   // (chunks_left = chunks_per_part - tid), index < V and != ban.  Invalid elements hold -inf (the caller masked them).
   float v1 = -INFINITY, v2 = -INFINITY;
@@ -652,7 +654,7 @@ __device__ __forceinline__ void wave_topk(const f32x4 (&x)[NV], int idx0, int ch
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = idx0 + 1024 * j + e;
-          unsigned long long key = (j * 256 < chunks_left && i < V && i != ban) ? topk_key(x[j][e], i) : 0ull;
+          unsigned long long key = (j * 256 < chunks_left && i < V && i != ban && !((skip >> (4 * j + e)) & 1ull)) ? topk_key(x[j][e], i) : 0ull;
           key = key < last ? key : 0ull;
           best = key > best ? key : best;
         }
@@ -666,12 +668,21 @@ __device__ __forceinline__ void wave_topk(const f32x4 (&x)[NV], int idx0, int ch
 #ifndef KMB_TOPK_OCC
 #define KMB_TOPK_OCC 4   // workgroups per CU the register budget is cut for (128 registers: no spills; 2, 4 and 5 measure alike)
 #endif
-template <int NV>   // float4 chunks per thread: chunks per part <= NV * 256
+// EDIT (a processed beam step): edit[r * ew + 0 .. ew) names the row's edited tokens (penalised or banned; -1: an
+// empty slot).  They leave the selection like `ban`, after the normalisation: an LDS bitmap over the part's own columns, one nibble
+// per float4 chunk.  The part's (max, sum-exp) describe the raw row.
+template <int NV, bool EDIT = false>   // float4 chunks per thread: chunks per part <= NV * 256
 __global__ __launch_bounds__(256, KMB_TOPK_OCC) void topk_part_kernel(const float* __restrict__ logits, int ldv, int V, int ban, int k,
-                                                                      int chunks_per_part, float* __restrict__ part) {
+                                                                      int chunks_per_part, float* __restrict__ part,
+                                                                      const int32_t* __restrict__ edit, int ew) {
   __shared__ float sh[8];
   __shared__ unsigned long long cand[4][TOPK_KMAX];
+  __shared__ uint32_t ebits[EDIT ? NV * 256 * 4 / 32 : 1];
   const int p = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (EDIT) {
+    for (int i = tid; i < NV * 256 * 4 / 32; i += 256) ebits[i] = 0u;
+    __syncthreads();
+  }
   const float* row = logits + (size_t)r * ldv;
   f32x4 x[NV];
   float m = -INFINITY;
@@ -682,6 +693,15 @@ __global__ __launch_bounds__(256, KMB_TOPK_OCC) void topk_part_kernel(const floa
     const int c = tid + 256 * j;
     const int i = (p * chunks_per_part + c) * 4;
     x[j] = *reinterpret_cast<const f32x4*>(row + ((c < chunks_per_part && i < ldv) ? i : 0));
+  }
+  if (EDIT) {   // behind the row's loads, which the first use below waits for anyway
+    const int32_t* er = edit + (size_t)r * ew;
+    const int col0 = p * chunks_per_part * 4, ncol = chunks_per_part * 4;
+    for (int i = tid; i < ew; i += 256) {
+      const int c = er[i] - col0;   // an empty slot is -1: below the part
+      if (c >= 0 && c < ncol) atomicOr(&ebits[c >> 5], 1u << (c & 31));
+    }
+    __syncthreads();
   }
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -716,7 +736,19 @@ __global__ __launch_bounds__(256, KMB_TOPK_OCC) void topk_part_kernel(const floa
       for (int e = 0; e < 4; ++e)
         if (idx0 + 1024 * j + e == ban) x[j][e] = -INFINITY;
   }
-  wave_topk<NV>(x, idx0, chunks_per_part - tid, V, ban, k, lane, cand[wave]);
+  unsigned long long skip = 0ull;
+  if (EDIT) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int c = tid + 256 * j;   // chunk c of the part: columns 4 c .. 4 c + 3, one nibble of word c / 8
+      const uint32_t nib = (ebits[c >> 3] >> ((c & 7) * 4)) & 0xfu;
+      skip |= (unsigned long long)nib << (4 * j);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((nib >> e) & 1u) x[j][e] = -INFINITY;
+    }
+  }
+  wave_topk<NV>(x, idx0, chunks_per_part - tid, V, ban, k, lane, cand[wave], skip);
   __syncthreads();
   if (wave == 0) {
     float* out = part + ((size_t)r * TOPK_PARTS + p) * TOPK_PW;
@@ -871,6 +903,101 @@ __global__ __launch_bounds__(1024) void beam_combine_merge_kernel(const float* _
   beam_embed_next(en, snext, b, nb, wave, lane);
 }
 
+// ---- the beam step with generate()'s score processors ----
+// The row's tokens split in two: the edited ones (beam_process.hip's list: penalised-and-not-banned, banned) and all others.
+// topk_part_kernel<13, true> left the best UNEDITED tokens of every part and the raw row's (max, sum-exp); here the penalised tokens join
+// them: logits[r][x] gathered, (v - lse) scaled by the penalty.  Candidates are ordered by their final score (value desc, token asc),
+// what torch.topk over the edited log-probabilities orders by -- the penalty does not keep the order of the logits.
+// One wave per row; up to KMB_PROCESS_MAX_T = 1024 penalised tokens, 16 per lane, every gather issued before the first use.
+__device__ __forceinline__ void topk_combine_row_edit(const float* __restrict__ part, int r, const float* __restrict__ add, int force_token,
+                                                      int k, float* val_row, int32_t* idx_row, int lane, const float* __restrict__ logits,
+                                                      int ldv, const KmbBeamEdit& ed) {
+  if (force_token >= 0) {   // log_softmax is exactly 0 at the forced token: the penalty leaves it, and no ban hits it (the caller's routing)
+    topk_combine_row(part, r, add, force_token, k, val_row, idx_row, lane);
+    return;
+  }
+  constexpr int NQ = KMB_PROCESS_MAX_T / 64;
+  const float a = add != nullptr ? add[r] : 0.f;
+  const float* rec = part + (size_t)r * TOPK_PARTS * TOPK_PW;
+  const int32_t* er = ed.edit + (size_t)r * ed.ew;   // slots [0, t): the penalised tokens, -1 for none
+  const float* row = logits + (size_t)r * ldv;
+  int xs[NQ];
+  float vs[NQ];
+  if (ed.penalise) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int j = lane + 64 * q;
+      const int x = er[j < ed.t ? j : 0];
+      xs[q] = j < ed.t ? x : -1;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) vs[q] = row[xs[q] >= 0 ? xs[q] : 0];
+  } else {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) { xs[q] = -1; vs[q] = 0.f; }
+  }
+  float M = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < TOPK_PARTS; ++q) M = fmaxf(M, rec[q * TOPK_PW]);
+  float S = 0.f;
+#pragma unroll
+  for (int q = 0; q < TOPK_PARTS; ++q) {
+    const float mq = rec[q * TOPK_PW];
+    if (mq != -INFINITY) S += rec[q * TOPK_PW + 1] * __expf(mq - M);
+  }
+  const float lse = M + __logf(S);
+  unsigned long long key = 0ull, pk[NQ];
+  if (lane < TOPK_PARTS * k) {
+    const float* c = rec + (lane / k) * TOPK_PW + 2 + 2 * (lane % k);
+    const int i = reinterpret_cast<const int32_t*>(c)[1];
+    if (i != 0x7fffffff) key = topk_key((c[0] - lse) + a, i);
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const float s = vs[q] - lse;
+    pk[q] = xs[q] >= 0 ? topk_key((s < 0.f ? s * ed.p : s * ed.inv_p) + a, xs[q]) : 0ull;
+  }
+  for (int jr = 0; jr < k; ++jr) {
+    unsigned long long best = key;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) best = pk[q] > best ? pk[q] : best;
+    const unsigned long long wk = wave_max_u64(best);
+    if (lane == 0) {
+      val_row[jr] = wk != 0ull ? topk_key_value(wk) : -INFINITY;
+      idx_row[jr] = wk != 0ull ? 0x7fffffff - (int)(uint32_t)wk : 0x7fffffff;
+    }
+    if (key == wk) key = 0ull;   // (a token is in one list only, once: the keys are distinct)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+      if (pk[q] == wk) pk[q] = 0ull;
+  }
+}
+// beam_combine_merge_kernel on the processed rows; the workgroup also moves the item's token histories on for the next step's edit:
+// ids_out[i][0 .. t) = ids_in[next_beam_idx[i]][0 .. t), ids_out[i][t] = next_tokens[i].
+__global__ __launch_bounds__(1024) void beam_combine_merge_edit_kernel(const float* __restrict__ part, const float* __restrict__ add,
+                                                                       int force_token, int nb, int k, int V, int32_t* __restrict__ out,
+                                                                       int eos, float* __restrict__ next_scores,
+                                                                       int64_t* __restrict__ next_tokens, int32_t* __restrict__ next_beam_idx,
+                                                                       const KmbHistGather hg, const KmbEmbedNext en,
+                                                                       const float* __restrict__ logits, int ldv, const KmbBeamEdit ed) {
+  __shared__ float sval[256];
+  __shared__ int32_t sidx[256];
+  __shared__ int32_t snext[32];
+  const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (wave < nb) topk_combine_row_edit(part, b * nb + wave, add, force_token, k, sval + wave * k, sidx + wave * k, lane, logits, ldv, ed);
+  __syncthreads();
+  if (wave == 0) {
+    beam_merge_item(sval, sidx, b, lane, nb, k, V, out, eos, next_scores, next_tokens, next_beam_idx, snext);
+    beam_hist_gather(hg, snext, b, nb, lane);
+  }
+  __syncthreads();   // snext was written by wave 0
+  const int w = ed.t + 1;
+  for (int e = threadIdx.x; e < nb * w; e += 64 * nb) {
+    const int i = e / w, j = e - i * w;
+    ed.ids_out[(size_t)(b * nb + i) * ed.ld_ids + j] = j < ed.t ? ed.ids_in[(size_t)snext[i] * ed.ld_ids + j] : (int64_t)snext[16 + i];
+  }
+  beam_embed_next(en, snext, b, nb, wave, lane);
+}
 
 // ---- the beam step behind the all-rows vocabulary projection's STATS epilogue (round 6) ----
 // gemm.hip's gemm_kernel_allrows<true> leaves, per row and 256-column block, the block's maximum logit and its sum of exp(v - maximum):
@@ -1292,7 +1419,8 @@ hipError_t kmb_logsoftmax_topk_launch(const float* logits, int ldv, int V, int r
   if (scratch != nullptr && scratch_floats >= kmb_logsoftmax_topk_scratch_floats(rows) && k >= 1 && k <= TOPK_KMAX &&
       (ldv & 3) == 0 && ((uintptr_t)logits & 15) == 0 && chunks <= 13 * 256 && rows <= 65535) {
     if (force_token < 0)
-      hipLaunchKernelGGL((topk_part_kernel<13>), dim3(TOPK_PARTS, rows), dim3(256), 0, stream, logits, ldv, V, ban_token, k, chunks, scratch);
+      hipLaunchKernelGGL((topk_part_kernel<13>), dim3(TOPK_PARTS, rows), dim3(256), 0, stream, logits, ldv, V, ban_token, k, chunks, scratch,
+                         nullptr, 0);
     hipLaunchKernelGGL(topk_combine_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, scratch, rows, add, force_token, k, out_val, out_idx);
     return hipGetLastError();
   }
@@ -1320,9 +1448,47 @@ hipError_t kmb_beam_step_launch(const float* logits, int ldv, int V, int B, int 
   KmbEmbedNext en = embed != nullptr && next_scores != nullptr ? *embed : KmbEmbedNext{};
   if (en.E != nullptr && ((en.D & 7) || en.D > 1024 || en.D <= 512)) return hipErrorInvalidValue;   // embed_ln_row<2>
   if (force_token < 0)
-    hipLaunchKernelGGL((topk_part_kernel<13>), dim3(TOPK_PARTS, rows), dim3(256), 0, stream, logits, ldv, V, ban_token, k, chunks, scratch);
+    hipLaunchKernelGGL((topk_part_kernel<13>), dim3(TOPK_PARTS, rows), dim3(256), 0, stream, logits, ldv, V, ban_token, k, chunks, scratch,
+                         nullptr, 0);
   hipLaunchKernelGGL(beam_combine_merge_kernel, dim3(B), dim3(64 * nb), 0, stream, scratch, add, force_token, nb, k, V, out, eos,
                      next_scores, next_tokens, next_beam_idx, hg, en);
+  return hipGetLastError();
+}
+
+// kmb_beam_step_launch with generate()'s score processors: the rows' edit sets (beam_process.hip, one launch), the part
+// kernel without the edited tokens, and the combine / merge launch that brings the penalised ones back and moves the token histories
+// on.  A forced step launches the last of the three only.  scratch: kmb_beam_step_processed_scratch_floats(rows, t, n_bad) words.
+size_t kmb_beam_step_processed_scratch_floats(int rows, int t, int n_bad) {
+  const size_t r = rows > 0 ? rows : 0;
+  return kmb_logsoftmax_topk_scratch_floats(rows) + r * kmb_beam_edit_words(t, n_bad);
+}
+hipError_t kmb_beam_step_processed_launch(const float* logits, int ldv, int V, int B, int nb, const float* add, int force_token,
+                                          int ban_token, int k, int32_t* out, int eos, float* next_scores, int64_t* next_tokens,
+                                          int32_t* next_beam_idx, float* scratch, size_t scratch_floats, const KmbBeamProcess& pr,
+                                          hipStream_t stream, const KmbHistGather* hist, const KmbEmbedNext* embed) {
+  if (B <= 0) return hipSuccess;
+  const int rows = B * nb;
+  const int chunks = (ldv / 4 + TOPK_PARTS - 1) / TOPK_PARTS;
+  if (!(scratch != nullptr && scratch_floats >= kmb_beam_step_processed_scratch_floats(rows, pr.t, pr.n_bad) && k >= 1 && k <= TOPK_KMAX &&
+        nb >= 1 && nb <= 16 && nb * k <= 256 && (ldv & 3) == 0 && ((uintptr_t)logits & 15) == 0 && chunks <= 13 * 256 && rows <= 65535 &&
+        V <= KMB_BEAM_EDIT_MAX_V && pr.t >= 1 && pr.t <= KMB_PROCESS_MAX_T))
+    return hipErrorNotSupported;
+  if (!next_scores || !next_tokens || !next_beam_idx || !pr.ids_in || !pr.ids_out) return hipErrorInvalidValue;
+  const KmbHistGather hg = hist != nullptr ? *hist : KmbHistGather{nullptr, nullptr, 0, 0};
+  KmbEmbedNext en = embed != nullptr ? *embed : KmbEmbedNext{};
+  if (en.E != nullptr && ((en.D & 7) || en.D > 1024 || en.D <= 512)) return hipErrorInvalidValue;   // embed_ln_row<2>
+  const int ew = kmb_beam_edit_words(pr.t, pr.n_bad);
+  int32_t* edit = reinterpret_cast<int32_t*>(scratch + kmb_logsoftmax_topk_scratch_floats(rows));
+  const KmbBeamEdit ed{edit, ew, pr.t, pr.repetition_penalty, 1.0f / pr.repetition_penalty, pr.repetition_penalty != 1.0f ? 1 : 0,
+                       pr.ids_in, pr.ids_out, pr.ld_ids};
+  if (force_token < 0) {
+    const hipError_t e = kmb_beam_edit_launch(pr, V, rows, ban_token, edit, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((topk_part_kernel<13, true>), dim3(TOPK_PARTS, rows), dim3(256), 0, stream, logits, ldv, V, ban_token, k, chunks,
+                       scratch, edit, ew);
+  }
+  hipLaunchKernelGGL(beam_combine_merge_edit_kernel, dim3(B), dim3(64 * nb), 0, stream, scratch, add, force_token, nb, k, V, out, eos,
+                     next_scores, next_tokens, next_beam_idx, hg, en, logits, ldv, ed);
   return hipGetLastError();
 }
 

@@ -179,6 +179,12 @@ PROTOTYPES = {
                                       c_p]),
     "kmb_logits_process": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
     "kmb_gen_logits_process": (C.c_int, [c_p, c_p, C.c_int, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
+    "kmb_beam_step_processed_scratch": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "kmb_beam_step_processed": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, c_p, c_p,
+                                          c_p, c_p, C.c_int64, c_p, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
+    "kmb_gen_beam_step_processed": (C.c_int, [c_p, c_p, C.c_int, C.c_int, c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, c_p, c_p, c_p,
+                                              c_p, C.c_int64, c_p, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, C.c_int,
+                                              c_p]),
     "kmb_beam_sample_step": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, f32, C.c_int, f32, C.c_int, c_p, C.c_int,
                                        C.c_int, c_p, C.c_int, c_p, c_p, c_p, c_p, C.c_int64, c_p]),
     "kmb_beam_sample_scratch": (C.c_int64, [C.c_int]),

@@ -875,6 +875,44 @@ class Engine:
             lambda: self.lib.kmb_beam_merge_select(ptr(val), ptr(idx), B, int(num_beams), int(k), int(self.config.vocab_size),
                                                    ptr(cand), int(eos_token), ptr(nscore), ptr(ntok), ptr(nidx), _stream()))
 
+    def beam_step_processed(self, logits, num_beams, k, add, ids_in, ids_out, t, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                            bad_words=None, force_token=-1, ban_token=-1, eos_token=-1, cand_out=None, reorder_step=-1):
+        """beam_step with generate()'s score processors applied to the rows' log-probabilities on the device
+        (kmb_beam_step_processed; its decode-loop form when `logits` are gen_step's): repetition penalty, no-repeat n-grams and
+        bad words from the beams' tokens ids_in[:, :t] (int64 [R, ld]); bad_words: (tokens int32, offsets int32 [n_bad + 1])
+        device tensors, the packed table, or None.  ids_out (int64 [R, ld], another buffer) receives the next beams' histories,
+        columns [0, t].  Returns beam_step's tuple; reorder_step as there.  Shapes outside the fused beam step's limits raise."""
+        R, V = logits.shape[0], int(self.config.vocab_size)
+        B = R // num_beams
+        assert logits.device == self.device and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1, \
+            "beam_step_processed: bad logits"
+        for x in (ids_in, ids_out):
+            assert x.device == self.device and x.dtype == torch.int64 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] == R, \
+                "beam_step_processed: bad ids"
+        assert ids_in.stride(0) == ids_out.stride(0) and ids_in.data_ptr() != ids_out.data_ptr(), "beam_step_processed: bad ids"
+        btok = boff = None
+        n_bad = 0
+        if bad_words is not None:
+            btok, boff = bad_words
+            for x in (btok, boff):
+                assert x.device == self.device and x.dtype == torch.int32 and x.is_contiguous(), "beam_step_processed: bad table"
+            n_bad = boff.numel() - 1
+            assert n_bad >= 0 and (n_bad == 0 or btok.numel() > 0)
+        outs = cand, nscore, ntok, nidx = self._beam_outputs(cand_out, B, k, R)
+        nscr = int(self.lib.kmb_beam_step_processed_scratch(R, int(t), n_bad))
+        scr = self.__dict__.get("_beam_process_scratch")
+        if scr is None or scr.numel() < nscr:
+            scr = self._beam_process_scratch = torch.empty(nscr, dtype=torch.float32, device=self.device)
+        head = (ptr(add), int(force_token), int(ban_token), int(k), ptr(cand), int(eos_token), ptr(nscore), ptr(ntok), ptr(nidx),
+                ptr(scr), scr.numel(), ptr(ids_in), ptr(ids_out), ids_in.stride(0), int(t), float(repetition_penalty),
+                int(no_repeat_ngram_size), ptr(btok) if n_bad > 0 else None, ptr(boff) if n_bad > 0 else None, n_bad)
+        return self._beam_call(
+            logits, outs, reorder_step,
+            lambda: self.lib.kmb_gen_beam_step_processed(self.h, ptr(logits), logits.stride(0), int(num_beams), *head,
+                                                         int(reorder_step), _stream()),
+            lambda: self.lib.kmb_beam_step_processed(ptr(logits), logits.stride(0), V, B, int(num_beams), *head, _stream()),
+            forced=force_token >= 0)
+
     def beam_sample_step(self, logits, num_beams, noise, add=None, temperature=1.0, top_k=0, top_p=1.0, ban_token=-1, eos_token=-1,
                          cand_out=None, reorder_step=-1):
         """One beam-sampling step (kmb_beam_sample_step): per row log_softmax, EOS ban, + add (the beam scores), / temperature,

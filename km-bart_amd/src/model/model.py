@@ -246,6 +246,27 @@ def _processors_on_device(num_beams, do_sample, processors_on, fp32, device_proc
     return max_length <= _PROCESS_MAX_T and table is not None
 
 
+def _beam_processors_on_device(num_beams, do_sample, processors_on, fp32, device_beam_processors, max_length, table, V, ld,
+                               no_repeat_ngram_size, bad_words_ids, bos_token_id, eos_token_id, decoder_start_token_id):
+    """Whether generate() runs a greedy beam search with score processors in the pipelined loop (Engine.beam_step_processed)
+    instead of the host loop: opt-in (device_beam_processors is model._device_beam_processors, falsy or absent: no), beams
+    without sampling, not in the fp32 validation mode, max_length <= 1024, the bad words packed (`table` as in
+    _processors_on_device), the fused beam step's shape limits (2 * num_beams <= 16 candidates, V <= 65536, row stride `ld` a
+    multiple of 4) -- and nothing that can ban a forced token (BOS on the first step, EOS on the last): no_repeat_ngram_size
+    1 bans the start token, a bad word may end in BOS or EOS, and an n-gram can only close on EOS when the decoder starts
+    with it.  A banned forced token leaves a row of -inf, whose order on the host is torch.topk's unspecified tie order."""
+    if not (processors_on and bool(device_beam_processors)) or num_beams <= 1 or do_sample or fp32:
+        return False
+    if max_length > _PROCESS_MAX_T or table is None:
+        return False
+    if 2 * num_beams > 16 or V > 65536 or ld % 4 != 0:
+        return False
+    if no_repeat_ngram_size == 1 or (eos_token_id is not None and decoder_start_token_id == eos_token_id):
+        return False
+    forced = {bos_token_id} | ({eos_token_id} if eos_token_id is not None else set())
+    return not any(int(seq[-1]) in forced for seq in (bad_words_ids or []))
+
+
 def _pack_bad_words(bad_words_ids, V):
     """bad_words_ids as kmb_logits_process reads them: (tokens, offsets), the sequences flattened and len + 1 ascending offsets
     (([], [0]) for None).  An empty inner list raises the reference's assertion (calc_banned_bad_words_ids).  None -- the torch
@@ -922,13 +943,18 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         # opt-in (model._device_processors): the one-beam device loops apply the processors themselves (kmb_logits_process between
         # the decode step and its tail), and the routing below sees a search without them
         device_processors = getattr(self, "_device_processors", False)
-        table = _pack_bad_words(bad_words_ids, V) if (processors_on and device_processors) else None
+        # ... and model._device_beam_processors the greedy beam search, in the pipelined loop (_beam_processors_on_device)
+        device_beam_processors = getattr(self, "_device_beam_processors", False)
+        table = _pack_bad_words(bad_words_ids, V) if (processors_on and (device_processors or device_beam_processors)) else None
         on_device = _processors_on_device(num_beams, do_sample, processors_on, fp32, device_processors,
                                           getattr(self, "_device_greedy", True), getattr(self, "_device_sampling", True),
                                           max_length, table)
-        host_processors = processors_on and not on_device
+        beams_on_device = _beam_processors_on_device(num_beams, do_sample, processors_on, fp32, device_beam_processors, max_length,
+                                                     table, V, eng.logits_ld, no_repeat_ngram_size, bad_words_ids, cfg.bos_token_id,
+                                                     eos_token_id, decoder_start_token_id)
+        host_processors = processors_on and not (on_device or beams_on_device)
         processors = None
-        if on_device:   # the table goes up once, before the loop
+        if on_device or beams_on_device:   # the table goes up once, before the loop
             bad = tuple(torch.tensor(x, dtype=torch.int32, device=dev) for x in table) if len(table[1]) > 1 else None
             processors = (float(repetition_penalty), int(no_repeat_ngram_size), bad)
         step_logits = None
@@ -958,7 +984,7 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             return self._one_beam_loop(eng, s, step_logits, want_scores, return_logprobs)
         book = _BeamBook(s)
         if route == "pipelined_beams":
-            self._pipelined_beam_loop(eng, s, book)
+            self._pipelined_beam_loop(eng, s, book, processors if beams_on_device else None)
         else:
             self._host_beam_loop(eng, s, book, step_logits)
         out, best_scores = book.best()
@@ -1054,16 +1080,21 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             return out, GenerationLogprobs(token_lps[:, :out.shape[1] - 1].contiguous(), scores)
         return (out, scores) if want_scores else out
 
-    def _pipelined_beam_loop(self, eng, s, book):
+    def _pipelined_beam_loop(self, eng, s, book, processors=None):
         """Greedy beam search and beam sampling on the device (kmb_beam_merge_select / kmb_beam_sample_step: the first num_beams
         non-EOS candidates, exactly what the bookkeeping sends on), so step t+1 is enqueued before the host has seen step t.  The
         host replays the reference's bookkeeping one step behind from the candidates (one small pinned copy per step):
         hypotheses, `done`, and the decision to stop -- a stop costs one decode step that is thrown away.  A `done` batch item
         keeps decoding on the device (the reference feeds it pad tokens); its rows feed nothing that is read.  Beam sampling
          draws the noise of torch.multinomial's exponential race here, [B, num_beams * V] on the default
-        generator as the torch path draws it."""
+        generator as the torch path draws it.  processors (model._device_beam_processors, greedy beam search only;
+        (repetition_penalty, no_repeat_ngram_size, packed bad words)): the beam step applies them to the rows' log-probabilities
+        itself (kmb_gen_beam_step_processed) from the beams' token histories, which the same launch moves on
+        between two id buffers; None: nothing more is allocated or enqueued."""
         dev = eng.device
         B, num_beams, k = s.B, s.num_beams, 2 * s.num_beams
+        if processors is not None:   # the beams' tokens so far, double-buffered: step t reads one, writes the other
+            ids = [torch.full((s.R, s.max_length), s.decoder_start_token_id, dtype=torch.long, device=dev) for _ in range(2)]
         last_tokens = torch.full((s.R,), s.decoder_start_token_id, dtype=torch.long, device=dev)
         eos = -1 if s.eos_token_id is None else int(s.eos_token_id)
         staging = eng.pinned((s.max_length, B, k, 2), torch.int32)
@@ -1104,9 +1135,15 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                 # the candidates land in the page-locked staging buffer straight from the kernel (no copy launch per step)
                 # ... and _reorder_cache (mixins.py:419-434) by the same call: the launch that picks the beams permutes the
                 # history index
-                cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step(
-                    logits, num_beams, k, beam_scores_dev, force_token=force, ban_token=ban, eos_token=eos,
-                    cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
+                if processors is not None:
+                    cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step_processed(
+                        logits, num_beams, k, beam_scores_dev, ids[(cur_len - 1) % 2], ids[cur_len % 2], cur_len, *processors,
+                        force_token=force, ban_token=ban, eos_token=eos, cand_out=staging[cur_len - 1],
+                        reorder_step=-1 if last else cur_len - 1)
+                else:
+                    cand, beam_scores_dev, last_tokens, beam_idx = eng.beam_step(
+                        logits, num_beams, k, beam_scores_dev, force_token=force, ban_token=ban, eos_token=eos,
+                        cand_out=staging[cur_len - 1], reorder_step=-1 if last else cur_len - 1)
             ev = torch.cuda.Event()
             ev.record()
             if pending is not None and replay(pending):

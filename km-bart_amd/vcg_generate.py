@@ -34,6 +34,8 @@ def main(args):
     model.to(device)
     if args.device_processors:
         model._device_processors = True
+    if args.device_beam_processors:
+        model._device_beam_processors = True
     tokenizer = IdTokenizer()
     loader = []
     if args.synthetic > 0:
@@ -80,6 +82,9 @@ def parse_args(argv=None):
     p.add_argument("--device_processors", action="store_true",
                    help="with --num_beams 1: apply the two options above on the device inside the pipelined decode loop "
                         "(model._device_processors) instead of taking the torch loop")
+    p.add_argument("--device_beam_processors", action="store_true",
+                   help="with --num_beams > 1 (no --do_sample): apply them on the device inside the pipelined beam loop "
+                        "(model._device_beam_processors) instead of taking the host beam loop")
     p.add_argument("--gpu_num", default=1, type=int)
     p.add_argument("--cpu", action="store_true")
     p.add_argument("--amp", action="store_true")
