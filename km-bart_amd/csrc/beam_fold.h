@@ -1,5 +1,5 @@
 // The work a beam step folds into the launch that has just chosen the next beams (the decode loop's reorder and embedding):
-// shared by loss.hip's beam steps and beam_sample.hip's beam sampling step.  snext: LDS, the item's nb chosen beam rows in
+// shared by beam_step.hip's beam steps and beam_sample.hip's beam sampling step.  snext: LDS, the item's nb chosen beam rows in
 // [0, 16), their tokens in [16, 32), written by lane 0 of wave 0.
 #pragma once
 #include "common.h"

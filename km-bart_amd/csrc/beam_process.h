@@ -1,5 +1,5 @@
 // The beam step with generate()'s score processors on the device (C-ABI kmb_beam_step_processed, kmb_gen_beam_step_processed;
-// DESIGN.md section 6n): csrc/beam_process.hip writes every beam row's edit set, csrc/loss.hip's EDIT forms of the beam step's two
+// DESIGN.md section 6n): csrc/beam_process.hip writes every beam row's edit set, csrc/beam_step.hip's EDIT forms of the beam step's two
 // launches consume it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,13 +36,9 @@ hipError_t kmb_beam_edit_launch(const KmbBeamProcess& pr, int V, int rows, int b
 size_t kmb_beam_step_processed_scratch_floats(int rows, int t, int n_bad);
 // kmb_beam_step_launch's arguments and contract (hist / embed: the decode loop's folded reorder and embedding) plus the processors.
 // hipErrorNotSupported: a shape outside kmb_beam_step's limits, V > 65536, or too little scratch.
-hipError_t kmb_beam_step_processed_launch(const float* logits, int ldv, int V, int B, int nb, const float* add, int force_token,
-                                          int ban_token, int k, int32_t* out, int eos, float* next_scores, int64_t* next_tokens,
-                                          int32_t* next_beam_idx, float* scratch, size_t scratch_floats, const KmbBeamProcess& pr,
-                                          hipStream_t stream, const KmbHistGather* hist = nullptr, const KmbEmbedNext* embed = nullptr);
+hipError_t kmb_beam_step_processed_launch(const KmbBeamStep& p, float* scratch, size_t scratch_floats, const KmbBeamProcess& pr,
+                                          hipStream_t stream);
 
 // The argument checks of kmb_beam_step_processed and kmb_gen_beam_step_processed (`who` names the caller in the message; capi_ops.cpp).
-int kmb_beam_step_processed_validate(const char* who, const float* logits, int ld, int V, int B, int num_beams, int force_token,
-                                     int ban_token, int k, const int32_t* out, int eos_token, const float* next_scores,
-                                     const int64_t* next_tokens, const int32_t* next_beam_idx, const float* scratch, int64_t scratch_floats,
+int kmb_beam_step_processed_validate(const char* who, const KmbBeamStep& p, const float* scratch, int64_t scratch_floats,
                                      const KmbBeamProcess& pr);

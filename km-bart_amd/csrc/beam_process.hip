@@ -1,7 +1,7 @@
 // The edit sets of a beam step with generate()'s score processors: for every beam row, which tokens the
 // repetition penalty scales and which the no-repeat n-grams, the bad words and min_length ban -- the row rule of logits_process.hip
 // (process_row.h), written out as a list instead of applied, because beam search edits log-probabilities: the beam step's part
-// kernel (loss.hip) drops the listed tokens from its selection and the combine launch brings the penalised ones back with their
+// kernel (beam_step.hip) drops the listed tokens from its selection and the combine launch brings the penalised ones back with their
 // scaled score.
 //
 // One workgroup of 256 lanes per row, the row's t tokens in LDS.  Bans first, into the list and into an LDS bitmap over the

@@ -107,8 +107,8 @@ int kmb_beam_step_stats(const float* logits, int ld, int V, int B, int num_beams
                         const float* stats, int stats_blocks, void* stream) {
   if (!logits || !out || !stats) return kmb_set_error("kmb_beam_step_stats: missing tensor");
   if (!next_scores || !next_tokens || !next_beam_idx) return kmb_set_error("kmb_beam_step_stats: missing output");
-  const hipError_t e = kmb_beam_step_stats_launch(logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
-                                                  next_tokens, next_beam_idx, stats, stats_blocks, (hipStream_t)stream);
+  const KmbBeamStep p{logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores, next_tokens, next_beam_idx};
+  const hipError_t e = kmb_beam_step_stats_launch(p, stats, stats_blocks, (hipStream_t)stream);
   if (e == hipErrorNotSupported)
     return kmb_set_error("kmb_beam_step_stats: unsupported shape (B * num_beams <= 320, k <= 16, num_beams <= 16, V %% 4 == 0, "
                          "stats_blocks == ceil(V / 256))");
@@ -334,9 +334,8 @@ int kmb_beam_step(const float* logits, int ld, int V, int B, int num_beams, cons
                   float* scratch, int64_t scratch_floats, void* stream) {
   if (!logits || !out || !scratch) return kmb_set_error("kmb_beam_step: missing tensor");
   if (!next_scores || !next_tokens || !next_beam_idx) return kmb_set_error("kmb_beam_step: missing output");
-  const hipError_t e = kmb_beam_step_launch(logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
-                                            next_tokens, next_beam_idx, scratch, scratch_floats > 0 ? (size_t)scratch_floats : 0,
-                                            (hipStream_t)stream);
+  const KmbBeamStep p{logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores, next_tokens, next_beam_idx};
+  const hipError_t e = kmb_beam_step_launch(p, scratch, scratch_floats > 0 ? (size_t)scratch_floats : 0, (hipStream_t)stream);
   if (e == hipErrorNotSupported)
     return kmb_set_error("kmb_beam_step: unsupported shape (k <= 16, num_beams <= 16, num_beams * k <= 256, ld %% 4 == 0, "
                          "scratch of kmb_logsoftmax_topk_scratch(B * num_beams) floats): use kmb_logsoftmax_topk_ws + kmb_beam_merge_select");
@@ -406,12 +405,9 @@ int kmb_beam_step_processed(const float* logits, int ld, int V, int B, int num_b
                             float repetition_penalty, int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets,
                             int n_bad, void* stream) {
   const KmbBeamProcess pr{ids_in, ids_out, ld_ids, t, repetition_penalty, no_repeat_ngram_size, bad_tokens, bad_offsets, n_bad};
-  if (kmb_beam_step_processed_validate("kmb_beam_step_processed", logits, ld, V, B, num_beams, force_token, ban_token, k, out, eos_token,
-                                       next_scores, next_tokens, next_beam_idx, scratch, scratch_floats, pr) != 0)
-    return -1;
-  return hipfail(kmb_beam_step_processed_launch(logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
-                                                next_tokens, next_beam_idx, scratch, (size_t)scratch_floats, pr, (hipStream_t)stream),
-                 "beam_step_processed");
+  const KmbBeamStep p{logits, ld, V, B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores, next_tokens, next_beam_idx};
+  if (kmb_beam_step_processed_validate("kmb_beam_step_processed", p, scratch, scratch_floats, pr) != 0) return -1;
+  return hipfail(kmb_beam_step_processed_launch(p, scratch, (size_t)scratch_floats, pr, (hipStream_t)stream), "beam_step_processed");
 }
 
 int64_t kmb_beam_sample_scratch(int rows) { return (int64_t)kmb_beam_sample_scratch_floats(rows); }
@@ -432,31 +428,29 @@ int kmb_beam_sample_step(const float* logits, int ld, int V, int B, int num_beam
 
 // The argument checks of kmb_beam_step_processed and kmb_gen_beam_step_processed (`who` names the caller in the message): the
 // processors' as kmb_logits_process_validate, the beam step's shape limits, and what the kernels index with.
-int kmb_beam_step_processed_validate(const char* who, const float* logits, int ld, int V, int B, int num_beams, int force_token,
-                                     int ban_token, int k, const int32_t* out, int eos_token, const float* next_scores,
-                                     const int64_t* next_tokens, const int32_t* next_beam_idx, const float* scratch, int64_t scratch_floats,
+int kmb_beam_step_processed_validate(const char* who, const KmbBeamStep& p, const float* scratch, int64_t scratch_floats,
                                      const KmbBeamProcess& pr) {
   char buf[256];
   auto bad = [&](const char* what) {
     snprintf(buf, sizeof(buf), "%s: %s", who, what);
     return kmb_set_error(buf);
   };
-  if (!logits || !out || !next_scores || !next_tokens || !next_beam_idx || !scratch || !pr.ids_in || !pr.ids_out)
+  if (!p.logits || !p.out || !p.next_scores || !p.next_tokens || !p.next_beam_idx || !scratch || !pr.ids_in || !pr.ids_out)
     return bad("logits, out, next_scores, next_tokens, next_beam_idx, scratch, ids_in and ids_out are required");
   if (pr.ids_in == pr.ids_out) return bad("ids_in and ids_out must be two buffers");
-  if (num_beams < 1 || num_beams > 16 || k < 1 || k > 16 || num_beams * k > 256)
+  if (p.nb < 1 || p.nb > 16 || p.k < 1 || p.k > 16 || p.nb * p.k > 256)
     return bad("need 1 <= k <= 16, 1 <= num_beams <= 16 and num_beams * k <= 256");
-  if (V < 1 || V > KMB_BEAM_EDIT_MAX_V || B < 0 || ld < V || (ld & 3) || ld > 4 * 4 * 13 * 256 || ((uintptr_t)logits & 15) ||
-      (int64_t)B * num_beams > 65535)
+  if (p.V < 1 || p.V > KMB_BEAM_EDIT_MAX_V || p.B < 0 || p.ld < p.V || (p.ld & 3) || p.ld > 4 * 4 * 13 * 256 || ((uintptr_t)p.logits & 15) ||
+      (int64_t)p.B * p.nb > 65535)
     return bad("need 1 <= V <= 65536, B >= 0, B * num_beams <= 65535, V <= ld <= 53248, ld % 4 == 0 and 16-byte aligned logits");
-  if (B > 0 && kmb_logits_process_validate(who, logits, ld, V, B * num_beams, pr.ids_in, pr.ld_ids, pr.t, pr.repetition_penalty,
-                                           pr.no_repeat_ngram_size, pr.bad_tokens, pr.bad_offsets, pr.n_bad) != 0)
+  if (p.B > 0 && kmb_logits_process_validate(who, p.logits, p.ld, p.V, p.B * p.nb, pr.ids_in, pr.ld_ids, pr.t, pr.repetition_penalty,
+                                             pr.no_repeat_ngram_size, pr.bad_tokens, pr.bad_offsets, pr.n_bad) != 0)
     return -1;
   if (pr.ld_ids <= pr.t) return bad("need ld_ids > t (column t is written)");
-  if (force_token < -1 || force_token >= V) return bad("force_token must be -1 or a token id < V");
-  if (ban_token < -1 || ban_token >= V) return bad("ban_token must be -1 or a token id < V");
-  if (eos_token < -1 || eos_token >= V) return bad("eos_token must be -1 or a token id < V");
-  if (scratch_floats < 0 || (size_t)scratch_floats < kmb_beam_step_processed_scratch_floats(B * num_beams, pr.t, pr.n_bad))
+  if (p.force_token < -1 || p.force_token >= p.V) return bad("force_token must be -1 or a token id < V");
+  if (p.ban_token < -1 || p.ban_token >= p.V) return bad("ban_token must be -1 or a token id < V");
+  if (p.eos < -1 || p.eos >= p.V) return bad("eos_token must be -1 or a token id < V");
+  if (scratch_floats < 0 || (size_t)scratch_floats < kmb_beam_step_processed_scratch_floats(p.B * p.nb, pr.t, pr.n_bad))
     return bad("scratch needs kmb_beam_step_processed_scratch(B * num_beams, t, n_bad) floats");
   return 0;
 }

@@ -1,5 +1,5 @@
 // One wave: a row of the multimodal embedding -- (token | region) vector * scale + learned position, LayerNorm (+ dropout) -- shared by
-// embed.hip's embed_ln_fwd_kernel and by the decode loop's beam step (loss.hip), which embeds the tokens it has just chosen for the next
+// embed.hip's embed_ln_fwd_kernel and by the decode loop's beam step (beam_step.hip), which embeds the tokens it has just chosen for the next
 // decode step in the same launch (round 6).  Same code, same order of operations: bit-identical rows either way.
 // Reference: src/model/modules.py:89-102 (_embed_multi_modal), :133-137 (pos + LN + dropout).
 #pragma once

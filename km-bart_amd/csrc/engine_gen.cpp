@@ -351,15 +351,12 @@ int kmb_gen_beam_step(kmb_handle* h, const float* logits, int ld, int num_beams,
   const bool fold = reorder_step >= 0;
   const KmbHistGather hg = gen_fold_hist(h, reorder_step);
   const GenEmbedPlan ep = gen_embed_plan(h, fold ? reorder_step + 1 : -1, true);
+  const KmbBeamStep p{logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores, next_tokens,
+                      next_beam_idx, fold ? &hg : nullptr, ep.arg()};
   hipError_t e = hipErrorNotSupported;
   if (force_token < 0 && G.head_stats_blocks > 0 && G.head_stats_for == logits)
-    e = kmb_beam_step_stats_launch(logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
-                                   next_tokens, next_beam_idx, G.L.head_stats, G.head_stats_blocks, s, fold ? &hg : nullptr,
-                                   ep.arg());
-  if (e == hipErrorNotSupported)
-    e = kmb_beam_step_launch(logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores, next_tokens,
-                             next_beam_idx, scratch, scratch_floats > 0 ? (size_t)scratch_floats : 0, s, fold ? &hg : nullptr,
-                             ep.arg());
+    e = kmb_beam_step_stats_launch(p, G.L.head_stats, G.head_stats_blocks, s);
+  if (e == hipErrorNotSupported) e = kmb_beam_step_launch(p, scratch, scratch_floats > 0 ? (size_t)scratch_floats : 0, s);
   if (e == hipErrorNotSupported) return fail("kmb_gen_beam_step: unsupported shape (k <= 16, num_beams <= 16, num_beams * k <= 256)");
   HIPCHK(e);
   gen_embed_done(h, ep);
@@ -381,15 +378,14 @@ int kmb_gen_beam_step_processed(kmb_handle* h, const float* logits, int ld, int 
   if (reorder_step >= G.Tmax) return fail("kmb_gen_beam_step_processed: reorder_step %d outside the cache (Tmax=%d)", reorder_step, G.Tmax);
   // the stateless form's argument checks, before anything is launched or the generation state changes
   const KmbBeamProcess pr{ids_in, ids_out, ld_ids, t, repetition_penalty, no_repeat_ngram_size, bad_tokens, bad_offsets, n_bad};
-  if (kmb_beam_step_processed_validate("kmb_gen_beam_step_processed", logits, ld, h->V, G.B, num_beams, force_token, ban_token, k, out,
-                                       eos_token, next_scores, next_tokens, next_beam_idx, scratch, scratch_floats, pr) != 0)
-    return -1;
+  KmbBeamStep p{logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores, next_tokens, next_beam_idx};
+  if (kmb_beam_step_processed_validate("kmb_gen_beam_step_processed", p, scratch, scratch_floats, pr) != 0) return -1;
   const bool fold = reorder_step >= 0;
   const KmbHistGather hg = gen_fold_hist(h, reorder_step);
   const GenEmbedPlan ep = gen_embed_plan(h, fold ? reorder_step + 1 : -1, true);
-  HIPCHK(kmb_beam_step_processed_launch(logits, ld, h->V, G.B, num_beams, add, force_token, ban_token, k, out, eos_token, next_scores,
-                                        next_tokens, next_beam_idx, scratch, (size_t)scratch_floats, pr, (hipStream_t)stream,
-                                        fold ? &hg : nullptr, ep.arg()));
+  p.hist = fold ? &hg : nullptr;
+  p.embed = ep.arg();
+  HIPCHK(kmb_beam_step_processed_launch(p, scratch, (size_t)scratch_floats, pr, (hipStream_t)stream));
   gen_embed_done(h, ep);
   return fold ? gen_reordered(h, next_beam_idx, (hipStream_t)stream) : 0;
 }

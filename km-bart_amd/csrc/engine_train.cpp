@@ -356,7 +356,7 @@ int encoder_forward(kmb_handle* h, const EncoderBufs& eb, const kmb_batch& bt, b
 // (gemm.hip "All rows" kernel: 58 -> 47 us at 320 rows, tools/allrows_time.py; at <= 192 rows the 128x128 tiles already read
 // the matrix once or twice and are faster: 31 against 39 us).  Bit-identical either way; KMB_GEMM_ALLROWS=0: always the tuner's pick.
 // stats / stats_blocks (a generation step): the all-rows kernel also leaves every row's per-block (maximum, sum-exp) pairs there and
-// *stats_blocks = their number, for the beam step that follows (loss.hip beam_stats_merge_kernel); 0 when another kernel ran.
+// *stats_blocks = their number, for the beam step that follows (beam_step.hip beam_stats_merge_kernel); 0 when another kernel ran.
 int run_vocab_gemm(const KmbGemm& g, hipStream_t s, float* stats, int* stats_blocks) {
   static const bool allrows_ok = !(KMB_DIAG_ENV("KMB_GEMM_ALLROWS") && KMB_DIAG_ENV("KMB_GEMM_ALLROWS")[0] == '0');
   if (stats_blocks) *stats_blocks = 0;

@@ -1138,7 +1138,7 @@ __global__ __launch_bounds__(512) void gemm_kernel_allrows(const KmbGemm p, floa
     }
   } else {
     // STATS (round 6, the beam step's first stage folded in): besides the logits, every row's (maximum, sum of exp(v - maximum)) over
-    // this workgroup's 256 columns -> stats[(row * blocks + block) * 2 + 0 / 1].  The step's selection kernel (loss.hip
+    // this workgroup's 256 columns -> stats[(row * blocks + block) * 2 + 0 / 1].  The step's selection kernel (beam_step.hip
     // beam_stats_merge_kernel) gets the row's log-sum-exp from the 197 pairs and reads only the blocks whose maximum can hold one of
     // the k best, instead of streaming the 64 MB of logits a second time.  The exps run between the stores (the epilogue is bound by
     // the store issue rate, the vector ALUs idle).  Columns >= N count as -inf.

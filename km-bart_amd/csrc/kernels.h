@@ -139,24 +139,9 @@ hipError_t kmb_ce_bf16_launch(const bf16_t* logits, int ldv, int V, const int64_
 // loss[0] = sum(loss_rows) / count
 hipError_t kmb_loss_finish_launch(const float* loss_rows, int rows, const int32_t* count, float* loss,
                                   hipStream_t stream);
+
+// ------------------------------------------------------------ beam_step.hip
 // generation: per row log_softmax over V then top-k of (logp + add[row]); writes k (value, index) pairs
-// hist (optional, needs next_*): the launch that picks the next beams also gathers the self-attention caches' history index for them:
-// dst[r][t] = src[next_beam_idx[r]][t], t < nt, rows of ld ints (kmb_gather_hist_launch's work, one launch less per decode step)
-struct KmbHistGather { const int32_t* src; int32_t* dst; int ld, nt; };
-// embed (optional, needs next_*; 512 < D <= 1024): ... and embeds the tokens it has chosen for the next decode step: row r of y [rows, D] bf16 =
-// LayerNorm(E[next_tokens[r]] * scale + prow) (kmb_embed_ln_fwd_launch's work on those tokens, bit-identical rows; E == nullptr: no)
-struct KmbEmbedNext { const float* E = nullptr; const float* prow = nullptr; const float* gamma = nullptr; const float* beta = nullptr;
-                      bf16_t* y = nullptr; float scale = 1.f; int D = 0; float eps = 0.f; int V = 0; };   // V: rows of E
-hipError_t kmb_beam_step_launch(const float* logits, int ldv, int V, int B, int nb, const float* add, int force_token, int ban_token,
-                                int k, int32_t* out, int eos, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
-                                float* scratch, size_t scratch_floats, hipStream_t stream, const KmbHistGather* hist = nullptr,
-                                const KmbEmbedNext* embed = nullptr);
-hipError_t kmb_beam_step_stats_launch(const float* logits, int ldv, int V, int B, int nb, const float* add, int force_token, int ban_token,
-                                      int k, int32_t* out, int eos, float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx,
-                                      const float* stats, int nblk, hipStream_t stream, const KmbHistGather* hist = nullptr,
-                                      const KmbEmbedNext* embed = nullptr);
-hipError_t kmb_beam_merge_launch(const float* val, const int32_t* idx, int B, int nb, int k, int V, int32_t* out, int eos,
-                                 float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, hipStream_t stream);
 // ban_token >= 0: that token's score is -inf AFTER the normalisation (min_length, transformers 3.0.2
 // postprocess_next_token_scores)
 // scratch (optional, kmb_logsoftmax_topk_scratch_floats(rows) floats): rows are split over four workgroups each and
@@ -165,6 +150,28 @@ size_t kmb_logsoftmax_topk_scratch_floats(int rows);
 hipError_t kmb_logsoftmax_topk_launch(const float* logits, int ldv, int V, int rows, const float* add,
                                       int force_token, int ban_token, int k, float* out_val, int32_t* out_idx,
                                       float* scratch, size_t scratch_floats, hipStream_t stream);
+hipError_t kmb_beam_merge_launch(const float* val, const int32_t* idx, int B, int nb, int k, int V, int32_t* out, int eos,
+                                 float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, hipStream_t stream);
+// hist (optional, needs next_*): the launch that picks the next beams also gathers the self-attention caches' history index for them:
+// dst[r][t] = src[next_beam_idx[r]][t], t < nt, rows of ld ints (kmb_gather_hist_launch's work, one launch less per decode step)
+struct KmbHistGather { const int32_t* src; int32_t* dst; int ld, nt; };
+// embed (optional, needs next_*; 512 < D <= 1024): ... and embeds the tokens it has chosen for the next decode step: row r of y [rows, D] bf16 =
+// LayerNorm(E[next_tokens[r]] * scale + prow) (kmb_embed_ln_fwd_launch's work on those tokens, bit-identical rows; E == nullptr: no)
+struct KmbEmbedNext { const float* E = nullptr; const float* prow = nullptr; const float* gamma = nullptr; const float* beta = nullptr;
+                      bf16_t* y = nullptr; float scale = 1.f; int D = 0; float eps = 0.f; int V = 0; };   // V: rows of E
+// A fused beam step (kmb_beam_step's arguments): logits [B * nb, ld] fp32, the rows' beam scores `add`, the k best per batch item
+// into `out`, the next step's beams into next_* (all three or none).
+struct KmbBeamStep {
+  const float* logits; int ld, V, B, nb;
+  const float* add; int force_token, ban_token, k;
+  int32_t* out; int eos;
+  float* next_scores; int64_t* next_tokens; int32_t* next_beam_idx;
+  const KmbHistGather* hist = nullptr; const KmbEmbedNext* embed = nullptr;
+};
+// B <= 0: nothing to do.  hipErrorNotSupported: the shape is outside this form's limits (checked before anything else);
+// the processed form (beam_process.h) takes the same struct
+hipError_t kmb_beam_step_launch(const KmbBeamStep& p, float* scratch, size_t scratch_floats, hipStream_t stream);
+hipError_t kmb_beam_step_stats_launch(const KmbBeamStep& p, const float* stats, int nblk, hipStream_t stream);
 
 // ---------------------------------------------------------------- optim.hip
 // transformers-3.0.2 AdamW on a flat fp32 arena; also refreshes the bf16 mirror of the parameters

@@ -1,4 +1,4 @@
-"""GPU: kmb_beam_step_processed (csrc/beam_process.hip + the EDIT forms of csrc/loss.hip's beam step), stateless form through
+"""GPU: kmb_beam_step_processed (csrc/beam_process.hip + the EDIT forms of csrc/beam_step.hip's beam step), stateless form through
 ctypes, against tests/beam_process_ref.py: candidates, scores, the next beams and the moved token histories with the three
 processors at once; bit-equality with kmb_beam_step when nothing is edited and on a forced step; a token that is both penalised
 and banned; the argument checks."""

@@ -1,5 +1,5 @@
 """The decode step's vocabulary projection with its statistics epilogue (csrc/gemm.hip gemm_kernel_allrows<true>) and the beam
-step that selects from those statistics (csrc/loss.hip beam_stats_merge_kernel; C-ABI kmb_gen_step + kmb_gen_beam_step, op-level
+step that selects from those statistics (csrc/beam_step.hip beam_stats_merge_kernel; C-ABI kmb_gen_step + kmb_gen_beam_step, op-level
 kmb_op_gemm_allrows_stats + kmb_beam_step_stats) against the two-launch beam step over the logits (kmb_beam_step), which the
 oracle tests pin (tests/test_ops_gpu.py, tests/test_decode_fused_gpu.py).  Reference: one step of transformers 3.0.2
 _generate_beam_search as reached from /root/reference/src/model/mixins.py:336-361 (scores: mixins.py:386-417).

@@ -469,7 +469,7 @@ class _TopkWithScratch:
 
 @pytest.mark.parametrize("ws", [False, True])
 def test_logsoftmax_topk_degenerate_rows(ws):
-    """Rows on which the split form's threshold selection has to give up (csrc/loss.hip wave_topk: more than 16 elements at
+    """Rows on which the split form's threshold selection has to give up (csrc/beam_step.hip wave_topk: more than 16 elements at
     or above the k-th value of a wave, or fewer than k finite values) -- the exact path; order = (value desc, index asc)."""
     lib = _lib.load()
     V, ld, k = 50320, 50432, 10
