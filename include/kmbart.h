@@ -219,6 +219,19 @@ int kmb_activation_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* th
  * keeps it; kept elements are multiplied by 1 / (1 - thr16 / 65536). */
 int kmb_set_classif_dropout(kmb_handle* h, float p);
 int kmb_classif_dropout_site(kmb_handle* h, int head, int which, uint32_t* thr16, uint32_t* seed);
+/* Label smoothing of the LM cross-entropy (fairseq's label_smoothed_cross_entropy / torch's CrossEntropyLoss(label_smoothing = eps)):
+ *   loss = mean over rows with a label in [0, V) of  lse(v_r) - (1 - eps) v_r[label_r] - eps mean_{j < V} v_rj
+ * and its gradient (softmax - (1 - eps) onehot - eps / V) / count.  A run-time setting of the handle like the dropout settings above
+ * (kmb_config keeps its layout); 0 <= eps < 1, anything else (NaN included) is refused with a message.  It applies to every forward
+ * with labels from the next one on -- kmb_forward*, kmb_forward_pretrain* (the LM term), train and eval alike, whichever head form runs.
+ * kmb_score and generation are untouched.  With the fused tied head the smoothing terms never touch the [rows, V] matrix: with
+ * wsum = sum_{j < V} E_j and bsum = sum_{j < V} b_j the row mean is (h_r . wsum + bsum) / V, the label's entry of the stored matrix becomes
+ * bf16(1 - (1 - eps) S_r), the uniform part is dH_r -= beta_r wsum and dE_j -= u for every j < V with beta_r = eps lm_factor / (count V) and
+ * u = sum_r beta_r h_r.  eps = 0 (the default) runs exactly the launches it ran without the setting.
+ * kmb_last_head_form: which head the last forward with labels took -- 0 fp32 logits + cross-entropy, 1 bf16 logits turned into their
+ * gradient in place, 2 the fused head (no logits pass); -1 before the first such forward. */
+int kmb_set_label_smoothing(kmb_handle* h, float eps);
+int kmb_last_head_form(const kmb_handle* h);
 int kmb_abi_sizeof_attn(void);   /* sizeof(KmbAttn) as the library was compiled: a binding checks its own layout against it */
 
 /* gradient buckets for data-parallel overlap (DDP reducer, vcg_train.py:98): bucket i is complete
@@ -747,6 +760,33 @@ int kmb_op_ce_rows_finish(const float* row_sums, int ld_sums, int nparts, const 
                           float* alpha, kmb_bf16* ah, kmb_bf16* P, int ldp, void* stream);
 /* out[r] = bf16(alpha[r] * sum over s < nslabs of slab[s * stride + r * d ...]) */
 int kmb_op_ce_dgrad_finish(const float* slab, int nslabs, int64_t stride, const float* alpha, kmb_bf16* out, int rows, int d, void* stream);
+/* Label smoothing (kmb_set_label_smoothing), piece by piece.  With eps = 0 each of these leaves the bits of its counterpart above.
+ * kmb_op_ce_smooth / kmb_op_ce_bf16_smooth: loss_rows[r] = lse - (1 - eps) logit[label] - eps mean_{j < V} logit[j],
+ * dlogits = (softmax - (1 - eps) onehot - eps / V) grad_scale / count, rounded once; pad columns and ignored rows stay zero. */
+int kmb_op_ce_smooth(const float* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                     float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, void* stream);
+int kmb_op_ce_bf16_smooth(const kmb_bf16* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                          float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, int32_t* status, void* stream);
+/* wsum[0, d) = sum_{j < V} E[j] in fp32, wsum[d] = sum_{j < V} bias[j] (wsum: d + 8 floats; d, lde multiples of 8).  Deterministic: workgroups
+ * leave partial rows in scratch (kmb_op_ce_vocab_sum_scratch(V, d) floats), one pass sums them in a fixed order. */
+int64_t kmb_op_ce_vocab_sum_scratch(int V, int d);
+int kmb_op_ce_vocab_sum(const kmb_bf16* E, int lde, const float* bias, int V, int d, float* wsum, float* scratch, void* stream);
+/* kmb_op_ce_rows_finish with smoothing: shift (required) is kmb_op_ce_label_logit's; wsum as above.  loss_rows = log S - pick +
+ * eps (shift - (H . wsum + wsum[d]) / V), P[r][label] := bf16(exp(pick) - (1 - eps) S), beta[r] = eps lm_factor / (count[0] V) on valid rows
+ * (0 elsewhere), neg_u[0, d) = -sum_r beta[r] H[r] (optional, with scratch of kmb_op_ce_rows_finish_smooth_scratch(rows, d) floats:
+ * per-workgroup partial sums, finished in a fixed order).  H is always required here. */
+int64_t kmb_op_ce_rows_finish_smooth_scratch(int rows, int d);
+int kmb_op_ce_rows_finish_smooth(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift, const int64_t* labels,
+                                 const int32_t* count, float lm_factor, float eps, int rows, int d, int V, const kmb_bf16* H, int ldh,
+                                 const float* wsum, float* loss_rows, float* srow, float* alpha, float* beta, kmb_bf16* ah, kmb_bf16* P,
+                                 int ldp, float* neg_u, float* scratch, void* stream);
+/* out[r] = bf16(alpha[r] * sum over s < nslabs of slab[s * stride + r * d ...] - beta[r] * wsum): one rounding */
+int kmb_op_ce_dgrad_finish_smooth(const float* slab, int nslabs, int64_t stride, const float* alpha, const float* beta, const float* wsum,
+                                  kmb_bf16* out, int rows, int d, void* stream);
+/* out[M, N] (fp32) = beta * out + sum over s < nslabs of slabs[s * stride ...] + rowvec[column]: the slab reduction of a split weight
+ * gradient with a row vector added to every row (the tied matrix's -u); M * N and stride multiples of 4, N a multiple of 4 */
+int kmb_op_reduce_slabs_rowvec(const float* slabs, int nslabs, int64_t stride, float* out, int M, int N, float beta, const float* rowvec,
+                               void* stream);
 /* pre-training heads (csrc/heads.hip).  loss_rows[r] = KL(target[r] || softmax(logits[r, :C])); dlogits (optional, bf16, row stride
  * ldd, columns C..ldd-1 zeroed) = (sum(target[r]) softmax - target[r]) grad_scale / rows */
 int kmb_op_kl_div(const float* logits, int ld, int C, const float* target, int ldt, int rows, float grad_scale, float* loss_rows,

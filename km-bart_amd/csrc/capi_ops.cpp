@@ -236,6 +236,77 @@ int kmb_op_ce_dgrad_finish(const float* slab, int nslabs, int64_t stride, const 
   if ((d & 7) || (stride & 3)) return kmb_set_error("kmb_op_ce_dgrad_finish: d must be a multiple of 8, stride of 4");
   return hipfail(kmb_ce_dgrad_finish_launch(slab, nslabs, (size_t)stride, alpha, out, rows, d, (hipStream_t)stream), "ce_dgrad_finish");
 }
+// ---- label smoothing (kmb_set_label_smoothing), piece by piece
+static bool eps_ok(float eps) { return eps >= 0.f && eps < 1.f; }   // (NaN fails both)
+int kmb_op_ce_smooth(const float* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                     float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, void* stream) {
+  if (!logits || !labels || !loss_rows || !count || !loss || rows <= 0 || V <= 0 || ldv < V) return kmb_set_error("kmb_op_ce_smooth: bad arguments");
+  if (!eps_ok(eps)) return kmb_set_error("kmb_op_ce_smooth: eps must be in [0, 1)");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = hipfail(kmb_count_valid_launch(labels, rows, V, count, nullptr, s), "count_valid");
+  if (rc) return rc;
+  rc = hipfail(kmb_ce_launch(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, s, eps), "ce_smooth");
+  if (rc) return rc;
+  return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, s), "loss_finish");
+}
+int kmb_op_ce_bf16_smooth(const kmb_bf16* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                          float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, int32_t* status, void* stream) {
+  if (!logits || !labels || !loss_rows || !count || !loss || rows <= 0 || V <= 0 || ldv < V)
+    return kmb_set_error("kmb_op_ce_bf16_smooth: bad arguments");
+  if ((ldv & 7) || ldv > 65536) return kmb_set_error("kmb_op_ce_bf16_smooth: ldv must be a multiple of 8 and at most 65536");
+  if (!eps_ok(eps)) return kmb_set_error("kmb_op_ce_bf16_smooth: eps must be in [0, 1)");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = hipfail(kmb_count_valid_launch(labels, rows, V, count, status, s), "count_valid");
+  if (rc) return rc;
+  rc = hipfail(kmb_ce_bf16_launch(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, s, eps), "ce_bf16_smooth");
+  if (rc) return rc;
+  return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, s), "loss_finish");
+}
+int64_t kmb_op_ce_vocab_sum_scratch(int V, int d) {
+  if (V <= 0 || d <= 0) return 0;
+  return (int64_t)kmb_ce_vocab_sum_slots(V, d) * kmb_ce_vocab_sum_ld(d);
+}
+int kmb_op_ce_vocab_sum(const kmb_bf16* E, int lde, const float* bias, int V, int d, float* wsum, float* scratch, void* stream) {
+  if (!E || !bias || !wsum || !scratch || V <= 0 || d <= 0 || lde < d) return kmb_set_error("kmb_op_ce_vocab_sum: bad arguments");
+  if ((d & 7) || (lde & 7) || ((uintptr_t)E & 15) || ((uintptr_t)wsum & 15))
+    return kmb_set_error("kmb_op_ce_vocab_sum: d and lde must be multiples of 8, E and wsum 16-byte aligned");
+  return hipfail(kmb_ce_vocab_sum_launch(E, lde, bias, V, d, scratch, wsum, (hipStream_t)stream), "ce_vocab_sum");
+}
+int64_t kmb_op_ce_rows_finish_smooth_scratch(int rows, int d) {
+  if (rows <= 0 || d <= 0) return 0;
+  return (int64_t)kmb_ce_rows_slots(rows) * d;
+}
+int kmb_op_ce_rows_finish_smooth(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift, const int64_t* labels,
+                                 const int32_t* count, float lm_factor, float eps, int rows, int d, int V, const kmb_bf16* H, int ldh,
+                                 const float* wsum, float* loss_rows, float* srow, float* alpha, float* beta, kmb_bf16* ah, kmb_bf16* P,
+                                 int ldp, float* neg_u, float* scratch, void* stream) {
+  if (!row_sums || !shift || !labels || !count || !H || !wsum || !loss_rows || !srow || !alpha || !beta || rows <= 0 || nparts <= 0 ||
+      ld_sums < nparts || V <= 0 || (P && ldp < V) || (neg_u && !scratch))
+    return kmb_set_error("kmb_op_ce_rows_finish_smooth: bad arguments");
+  if (d <= 0 || (d & 7) || (ldh & 7) || ldh < d || d > 4096 || ((uintptr_t)wsum & 15))
+    return kmb_set_error("kmb_op_ce_rows_finish_smooth: d and ldh must be multiples of 8, ldh >= d, d <= 4096, wsum 16-byte aligned");
+  if (!eps_ok(eps)) return kmb_set_error("kmb_op_ce_rows_finish_smooth: eps must be in [0, 1)");
+  return hipfail(kmb_ce_rows_finish_ls_launch(row_sums, ld_sums, nparts, pick, shift, labels, count, lm_factor, eps, rows, d, V, H, ldh, wsum,
+                                              loss_rows, srow, alpha, beta, ah, P, ldp, neg_u ? scratch : nullptr, neg_u, (hipStream_t)stream),
+                 "ce_rows_finish_smooth");
+}
+int kmb_op_ce_dgrad_finish_smooth(const float* slab, int nslabs, int64_t stride, const float* alpha, const float* beta, const float* wsum,
+                                  kmb_bf16* out, int rows, int d, void* stream) {
+  if (!slab || !alpha || !beta || !wsum || !out || rows <= 0 || nslabs < 1 || d <= 0 || stride < 0)
+    return kmb_set_error("kmb_op_ce_dgrad_finish_smooth: bad arguments");
+  if ((d & 7) || (stride & 3) || ((uintptr_t)wsum & 15))
+    return kmb_set_error("kmb_op_ce_dgrad_finish_smooth: d must be a multiple of 8, stride of 4, wsum 16-byte aligned");
+  return hipfail(kmb_ce_dgrad_finish_ls_launch(slab, nslabs, (size_t)stride, alpha, beta, wsum, out, rows, d, (hipStream_t)stream),
+                 "ce_dgrad_finish_smooth");
+}
+int kmb_op_reduce_slabs_rowvec(const float* slabs, int nslabs, int64_t stride, float* out, int M, int N, float beta, const float* rowvec,
+                               void* stream) {
+  if (!slabs || !out || !rowvec || nslabs < 1 || stride < 0 || M <= 0 || N <= 0) return kmb_set_error("kmb_op_reduce_slabs_rowvec: bad arguments");
+  if ((N & 3) || (stride & 3) || ((uintptr_t)rowvec & 15) || ((uintptr_t)out & 15) || ((uintptr_t)slabs & 15))
+    return kmb_set_error("kmb_op_reduce_slabs_rowvec: N and stride must be multiples of 4, the pointers 16-byte aligned");
+  return hipfail(kmb_reduce_slabs_rowvec_launch(slabs, nslabs, (size_t)stride, out, (size_t)M * N, beta, rowvec, N, (hipStream_t)stream),
+                 "reduce_slabs_rowvec");
+}
 int kmb_op_kl_div(const float* logits, int ld, int C, const float* target, int ldt, int rows, float grad_scale, float* loss_rows,
                   kmb_bf16* dlogits, int ldd, void* stream) {
   if (!logits || !target || !loss_rows || rows <= 0 || C <= 0 || ld < C || ldt < C || (dlogits && ldd < C))

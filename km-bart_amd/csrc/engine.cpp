@@ -224,7 +224,10 @@ int run_wgrad(kmb_handle* h, KmbGemm g, hipStream_t s, float* slab, size_t slab_
   if (S <= 1 || slab == nullptr || g.ld_out_f32 != g.N || ((size_t)g.M * g.N & 3)) return run_gemm(g, s);
   float* out = g.out_f32;
   const float beta = g.beta;
-  g.split_k = S; g.slab = slab; g.out_f32 = nullptr; g.beta = 0.f;
+  // a bias on a weight gradient is a row vector added to every row of dW (the tied matrix's -u under label smoothing, engine_train.cpp
+  // head_fused_ce): the un-split launch above adds it in its epilogue, a split one where the slabs are summed
+  const float* rowvec = g.bias;
+  g.split_k = S; g.slab = slab; g.out_f32 = nullptr; g.beta = 0.f; g.bias = nullptr;
   KCHK(run_gemm(g, s));
   // KMB_SKIP_SLAB_REDUCE=1 (diagnostic build, TIMING ONLY -- the gradients are never written): what the 63 reduction launches of a
   // step cost where they run (b = 256: 0.62 of 15.85 ms, b = 512: 0.6 of 27.0, b = 1024: 0.6 of 49.7, b = 64: nothing).  Folding the
@@ -234,7 +237,8 @@ int run_wgrad(kmb_handle* h, KmbGemm g, hipStream_t s, float* slab, size_t slab_
   // past the L2 cost several times what the pass over L2- / Infinity-Cache-resident slabs costs (profiles/r05_grouped_weight_gradients.md)
   static const bool skip_reduce = KMB_DIAG_ENV("KMB_SKIP_SLAB_REDUCE") != nullptr;
   if (skip_reduce) return 0;
-  HIPCHK(kmb_reduce_slabs_launch(slab, S, (size_t)g.M * g.N, out, (size_t)g.M * g.N, beta, s));
+  if (rowvec) HIPCHK(kmb_reduce_slabs_rowvec_launch(slab, S, (size_t)g.M * g.N, out, (size_t)g.M * g.N, beta, rowvec, g.N, s));
+  else HIPCHK(kmb_reduce_slabs_launch(slab, S, (size_t)g.M * g.N, out, (size_t)g.M * g.N, beta, s));
   return 0;
 }
 
@@ -654,6 +658,15 @@ int kmb_set_classif_dropout(kmb_handle* h, float p) {
   h->cls_p = p;
   return 0;
 }
+
+int kmb_set_label_smoothing(kmb_handle* h, float eps) {
+  if (!h) return fail("kmb_set_label_smoothing: null handle");
+  if (!(eps >= 0.f && eps < 1.f)) return fail("kmb_set_label_smoothing: eps must be in [0, 1), got %g", (double)eps);   // (NaN fails both)
+  h->label_smoothing = eps;
+  return 0;
+}
+
+int kmb_last_head_form(const kmb_handle* h) { return h ? h->last_head_form : -1; }
 
 int kmb_classif_dropout_site(kmb_handle* h, int head, int which, uint32_t* thr16, uint32_t* seed) {
   if (!h || !thr16 || !seed) return fail("kmb_classif_dropout_site: null argument");

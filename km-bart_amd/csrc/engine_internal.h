@@ -133,6 +133,9 @@ struct TrainLayout {
   bf16_t *hx = nullptr, *hy = nullptr, *hdy = nullptr, *hdx = nullptr, *hdlg = nullptr; float *hlg = nullptr, *hloss = nullptr, *dhead = nullptr;
   bf16_t* hyd = nullptr;   // [n, d]: the hidden activations hy under their classif_dropout mask (what out_proj and its weight gradient read)
   float* head_slab = nullptr; size_t head_slab_floats = 0;  // split-K partials of the pre-training heads' weight gradients (caller's stream)
+  // label smoothing in the fused head (kmb_set_label_smoothing; loss.hip "Label smoothing as rank-one terms"): wsum | bsum, -u, beta per row and
+  // the partial slots of the two deterministic sums (the vocabulary sum's, then the row finish's)
+  float *ls_wsum = nullptr, *ls_negu = nullptr, *ls_beta = nullptr, *ls_parts = nullptr;
   EncoderBufs encoder() const { return {status, xf, img_emb, img_src, ze0, me0, re0, xe.data(), ea.data(), false}; }
 };
 
@@ -283,6 +286,9 @@ struct kmb_handle {
   // cls_used[head][which]: what the LAST training forward launched with (zeros: none, or the head had no rows), for kmb_classif_dropout_site.
   static constexpr uint64_t CLS_SITE_BASE = 0x50000000ull;
   float cls_p = 0.f;
+  // Label smoothing of the LM cross-entropy (kmb_set_label_smoothing): the fourth run-time setting; lm_head hands it to whichever head form runs.
+  float label_smoothing = 0.f;
+  int last_head_form = -1;   // 0 fp32, 1 bf16 two-kernel, 2 fused: the head the last forward with labels took (kmb_last_head_form)
   KmbDrop cls_used[3][2] = {{{0u, 0u, 1.f}, {0u, 0u, 1.f}}, {{0u, 0u, 1.f}, {0u, 0u, 1.f}}, {{0u, 0u, 1.f}, {0u, 0u, 1.f}}};
   KmbDrop cls_drop_site(int head, int which, bool train) {
     const KmbDrop dr = site_drop(cls_p, CLS_SITE_BASE + (uint64_t)(2 * head + which), train, true);

@@ -141,6 +141,12 @@ size_t layout_train(const kmb_handle* h, char* base, size_t cap, int B, int S, i
     L.head_slab = bp.take<float>(L.head_slab_floats);
     L.hyd = bp.act(n * d);   // (carved last: every other buffer stays where it was)
   }
+  {   // label smoothing in the fused head (behind everything else, for the same reason): wsum | bsum, -u, beta, and the partial slots of whichever
+      // of the two deterministic sums is running (the vocabulary sum's are consumed before the row finish writes its own)
+    const size_t vs = (size_t)kmb_ce_vocab_sum_slots(h->V, d) * kmb_ce_vocab_sum_ld(d), us = (size_t)kmb_ce_rows_slots((int)Md) * d;
+    L.ls_wsum = bp.take<float>(kmb_ce_vocab_sum_ld(d)); L.ls_negu = bp.take<float>(d); L.ls_beta = bp.take<float>(Md);
+    L.ls_parts = bp.take<float>(vs > us ? vs : us);
+  }
   if (out) *out = std::move(L);
   return bp.used();
 }
@@ -397,9 +403,12 @@ static int head_dgrad_split(const kmb_handle* h, int Md) {
 
 // dE[V, d] = dlogits^T rows_operand (overwrites: the embedding scatter-adds of backward come on top), on the side stream: it overlaps
 // the start of backward, whose embedding scatter-adds wait for head_wgrad_done
-static int head_wgrad_on_side(kmb_handle* h, const bf16_t* dlogits, const bf16_t* rows_operand, hipStream_t s) {
+// rowvec (label smoothing, the fused head's -u): added to every one of the V rows where the gradient is written (run_wgrad)
+static int head_wgrad_on_side(kmb_handle* h, const bf16_t* dlogits, const bf16_t* rows_operand, hipStream_t s, const float* rowvec = nullptr) {
   KCHK(ensure_side(h));
-  KCHK(wgrad_side(h, lin_wgrad(dlogits, h->Vpad, rows_operand, h->d, h->gf(h->shared), h->Md, h->V, h->d, 0.f), s));
+  KmbGemm gw = lin_wgrad(dlogits, h->Vpad, rows_operand, h->d, h->gf(h->shared), h->Md, h->V, h->d, 0.f);
+  gw.bias = rowvec;
+  KCHK(wgrad_side(h, gw, s));
   if (h->side_on && h->side) {
     HIPCHK(hipEventRecord(h->head_wgrad_done, h->side));
     h->head_wgrad_pending = true;
@@ -428,8 +437,19 @@ static int head_fused_ce(kmb_handle* h, const bf16_t* hdec, const int64_t* label
   g.act = 5; g.out_bf16 = L.dlogits_c; g.ld_out_bf16 = h->Vpad;
   g.row_shift = L.ce_shift; g.row_sums = L.logits_c; g.row_sums_ld = nparts; g.pick_col = nullptr; g.pick_out = nullptr;   // the shift is the label's logit itself: v[label] - shift = 0 up to summation order
   KCHK(run_gemm(g, s));
-  HIPCHK(kmb_ce_rows_finish_launch(L.logits_c, nparts, nparts, nullptr, labels, L.count, lmf, Md, d, h->V, hdec, d, L.loss_rows, L.ce_srow,
-                                   L.ce_alpha, need_grad ? L.ce_ah : nullptr, need_grad ? L.dlogits_c : nullptr, h->Vpad, s));
+  // Label smoothing (loss.hip "Label smoothing as rank-one terms"): one read of the tied matrix for wsum | bsum, then the row finish, the
+  // data-gradient finish and the weight gradient each take one more operand.  eps == 0: the launches below are the ones there always were.
+  const float eps = h->label_smoothing;
+  if (eps > 0.f) {
+    HIPCHK(kmb_ce_vocab_sum_launch(h->wb(h->shared), d, h->flb, h->V, d, L.ls_parts, L.ls_wsum, s));
+    HIPCHK(kmb_ce_rows_finish_ls_launch(L.logits_c, nparts, nparts, nullptr, L.ce_shift, labels, L.count, lmf, eps, Md, d, h->V, hdec, d, L.ls_wsum,
+                                        L.loss_rows, L.ce_srow, L.ce_alpha, L.ls_beta, need_grad ? L.ce_ah : nullptr,
+                                        need_grad ? L.dlogits_c : nullptr, h->Vpad, need_grad ? L.ls_parts : nullptr,
+                                        need_grad ? L.ls_negu : nullptr, s));
+  } else {
+    HIPCHK(kmb_ce_rows_finish_launch(L.logits_c, nparts, nparts, nullptr, labels, L.count, lmf, Md, d, h->V, hdec, d, L.loss_rows, L.ce_srow,
+                                     L.ce_alpha, need_grad ? L.ce_ah : nullptr, need_grad ? L.dlogits_c : nullptr, h->Vpad, s));
+  }
   if (!need_grad) return 0;
   // dH_r = a_r sum_j P'_rj E_j: the GEMM on P' into fp32 slabs (the row sums in that buffer were consumed by the launch above), then the finish
   KmbGemm gd = lin_dgrad(L.dlogits_c, h->Vpad, h->wb(h->shared), Md, h->Vpad, d);
@@ -437,6 +457,10 @@ static int head_fused_ce(kmb_handle* h, const bf16_t* hdec, const int64_t* label
   if (S > 1) { gd.split_k = S; gd.slab = L.logits_c; }
   else { gd.out_f32 = L.logits_c; gd.ld_out_f32 = d; }
   KCHK(run_gemm(gd, s));
+  if (eps > 0.f) {
+    HIPCHK(kmb_ce_dgrad_finish_ls_launch(L.logits_c, S, (size_t)Md * d, L.ce_alpha, L.ls_beta, L.ls_wsum, L.dhdec, Md, d, s));
+    return head_wgrad_on_side(h, L.dlogits_c, L.ce_ah, s, L.ls_negu);   // dE[j] = (P'^T (a . H))[j] - u for j < V
+  }
   HIPCHK(kmb_ce_dgrad_finish_launch(L.logits_c, S, (size_t)Md * d, L.ce_alpha, L.dhdec, Md, d, s));
   return head_wgrad_on_side(h, L.dlogits_c, L.ce_ah, s);   // dE = P'^T (a . H)
 }
@@ -448,7 +472,8 @@ static int head_bf16(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, f
   KmbGemm g = lin_fwd(hdec, h->d, h->wb(h->shared), h->flb, h->Md, h->V, h->d);
   g.out_bf16 = L.dlogits_c; g.ld_out_bf16 = h->Vpad;
   KCHK(run_gemm(g, s));
-  HIPCHK(kmb_ce_bf16_launch(L.dlogits_c, h->Vpad, h->V, labels, h->Md, L.count, lmf, L.loss_rows, need_grad ? L.dlogits_c : nullptr, s));
+  HIPCHK(kmb_ce_bf16_launch(L.dlogits_c, h->Vpad, h->V, labels, h->Md, L.count, lmf, L.loss_rows, need_grad ? L.dlogits_c : nullptr, s,
+                            h->label_smoothing));
   return 0;
 }
 
@@ -468,7 +493,7 @@ static int head_fp32(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, f
     KCHK(run_gemm(g, s));
     if (!labels) continue;
     HIPCHK(kmb_ce_launch(lg, h->Vpad, h->V, labels + r0, rows, L.count, lmf, L.loss_rows + r0,
-                         need_grad ? L.dlogits_c + (size_t)r0 * h->Vpad : nullptr, s));
+                         need_grad ? L.dlogits_c + (size_t)r0 * h->Vpad : nullptr, s, h->label_smoothing));
   }
   return 0;
 }
@@ -505,6 +530,7 @@ static int lm_head(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, flo
   const int nparts = h->Vpad / 64;
   const bool fused_ce = bf16_head && labels && fused_ce_env && (Md % 256) == 0 && (h->Vpad % 256) == 0 && (d % 64) == 0 &&
                         d >= 128 && (long)(Md / 256) * (h->Vpad / 256) >= 128 && (size_t)Md * nparts <= h->tl.logits_c_floats;
+  if (labels) h->last_head_form = fused_ce ? 2 : bf16_head ? 1 : 0;
   if (fused_ce) KCHK(head_fused_ce(h, hdec, labels, lmf, need_grad, s));
   else if (bf16_head) KCHK(head_bf16(h, hdec, labels, lmf, need_grad, s));
   else KCHK(head_fp32(h, hdec, labels, lmf, need_grad, logits_out, s));

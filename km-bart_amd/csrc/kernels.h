@@ -78,6 +78,9 @@ hipError_t kmb_reduce_slabs_bf16_launch(const float* slabs, int nslabs, size_t s
                                         hipStream_t stream);
 hipError_t kmb_reduce_slabs_launch(const float* slabs, int nslabs, size_t stride, float* out, size_t n, float beta,
                                    hipStream_t stream);
+// the same over an [n / N, N] matrix with a row vector added to every row: out[i] = beta*out[i] + sum_s slabs[s][i] + rowvec[i % N]   (N % 4 == 0)
+hipError_t kmb_reduce_slabs_rowvec_launch(const float* slabs, int nslabs, size_t stride, float* out, size_t n, float beta,
+                                          const float* rowvec, int N, hipStream_t stream);
 // out[M, N] (bf16, row stride ld_out) = dropout((sum of slabs + bias) * q-scale) + residual   (N % 8 == 0)
 hipError_t kmb_reduce_slabs_epi_launch(const float* slabs, int nslabs, size_t stride, const float* bias, float col_scale,
                                        int col_scale_n, KmbDrop drop, const bf16_t* residual, int ld_res, bf16_t* out,
@@ -130,12 +133,32 @@ hipError_t kmb_ce_dgrad_finish_launch(const float* slab, int nslabs, size_t stri
                                       hipStream_t stream);
 // per row: loss_rows[r] = lse - logit[label] (0 if ignored); dlogits (bf16, ld = ldv, pad columns zeroed)
 //          = (softmax - onehot) * grad_scale / count   (0 rows if ignored).  dlogits may be null.
+// eps > 0 (label smoothing): loss_rows[r] = lse - (1 - eps) logit[label] - eps mean_{j < V} logit[j],
+//          dlogits = (softmax - (1 - eps) onehot - eps / V) * grad_scale / count; eps == 0 launches the kernels it always did
 hipError_t kmb_ce_launch(const float* logits, int ldv, int V, const int64_t* labels, int rows,
                          const int32_t* count, float grad_scale, float* loss_rows, bf16_t* dlogits,
-                         hipStream_t stream);
+                         hipStream_t stream, float eps = 0.f);
 // the same on bf16 logits (ldv <= 65536), dlogits may alias logits (in place)
 hipError_t kmb_ce_bf16_launch(const bf16_t* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count,
-                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream);
+                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps = 0.f);
+// ---- label smoothing in the fused tied head (loss.hip "Label smoothing as rank-one terms")
+// wsum[0, d) = sum_{j < V} E[j] (bf16 rows, fp32 sums), wsum[d] = sum_{j < V} bias[j]: kmb_ce_vocab_sum_slots(V, d) workgroups leave one partial row
+// of kmb_ce_vocab_sum_ld(d) floats each in `partials`, one pass sums them in slot order.  wsum holds kmb_ce_vocab_sum_ld(d) floats.
+int kmb_ce_vocab_sum_slots(int V, int d);
+int kmb_ce_vocab_sum_ld(int d);
+hipError_t kmb_ce_vocab_sum_launch(const bf16_t* E, int lde, const float* bias, int V, int d, float* partials, float* wsum, hipStream_t stream);
+// kmb_ce_rows_finish_launch with smoothing: loss_r = log S_r - pick_r + eps (shift_r - zbar_r), zbar_r = (H_r . wsum + wsum[d]) / V;
+// P[r][label_r] := exp(pick_r) - (1 - eps) S_r; beta_r = eps lm_factor / (count V) on valid rows, 0 elsewhere; kmb_ce_rows_slots(rows) workgroups
+// leave partial sums of -beta_r H_r in u_partials ([slots][d]), one pass sums them in slot order into neg_u[0, d) = -sum_r beta_r H_r.
+// u_partials / neg_u may both be null (no gradient wanted).
+int kmb_ce_rows_slots(int rows);
+hipError_t kmb_ce_rows_finish_ls_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift,
+                                        const int64_t* labels, const int32_t* count, float lm_factor, float eps, int rows, int d, int V,
+                                        const bf16_t* H, int ldh, const float* wsum, float* loss_rows, float* srow, float* alpha, float* beta,
+                                        bf16_t* ah, bf16_t* P, int ldp, float* u_partials, float* neg_u, hipStream_t stream);
+// out[r] = bf16(alpha[r] * sum_s slab[s][r] - beta[r] * wsum)
+hipError_t kmb_ce_dgrad_finish_ls_launch(const float* slab, int nslabs, size_t stride, const float* alpha, const float* beta,
+                                         const float* wsum, bf16_t* out, int rows, int d, hipStream_t stream);
 // loss[0] = sum(loss_rows) / count
 hipError_t kmb_loss_finish_launch(const float* loss_rows, int rows, const int32_t* count, float* loss,
                                   hipStream_t stream);

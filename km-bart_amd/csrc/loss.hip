@@ -50,11 +50,16 @@ __global__ __launch_bounds__(1024) void count_valid_kernel(const int64_t* __rest
   }
 }
 
+// LS (label smoothing, eps > 0): the target is (1 - eps) onehot + eps / V over the V real columns, so
+//   loss_r = lse - (1 - eps) v_label - eps mean_{j < V} v_j,   gradient row = (p - (1 - eps) onehot - eps / V) * scale / n, rounded once;
+// pad columns and ignored rows stay exactly zero.  LS = false is the code it was (eps is not read).
+template <bool LS>
 __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logits, int ldv, int V,
                                                  const int64_t* __restrict__ labels, const int32_t* __restrict__ count,
                                                  float grad_scale, float* __restrict__ loss_rows,
-                                                 bf16_t* __restrict__ dlogits) {
+                                                 bf16_t* __restrict__ dlogits, float eps) {
   __shared__ float sh[8];
+  __shared__ float shz[LS ? 4 : 1];
   const int r = blockIdx.x, tid = threadIdx.x;
   const float* row = logits + (size_t)r * ldv;
   const int64_t label = labels[r];
@@ -62,8 +67,22 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
   float m = 0.f, s = 1.f;
   if (valid) row_lse(row, V, sh, m, s);  // block-uniform branch
   const float lse = m + __logf(s);
-  if (tid == 0) loss_rows[r] = valid ? (lse - row[label]) : 0.f;
+  float zmean = 0.f;
+  if (LS && valid) {   // block-uniform: the row's mean logit (a third read of the row, from L2 like the second)
+    float z = 0.f;
+    for (int i = tid; i < V; i += 256) z += row[i];
+    z = wave_sum(z);
+    if ((tid & 63) == 0) shz[tid >> 6] = z;
+    __syncthreads();
+    zmean = ((shz[0] + shz[1]) + (shz[2] + shz[3])) / (float)V;
+  }
+  if (LS) {
+    if (tid == 0) loss_rows[r] = valid ? (lse - (1.f - eps) * row[label] - eps * zmean) : 0.f;
+  } else {
+    if (tid == 0) loss_rows[r] = valid ? (lse - row[label]) : 0.f;
+  }
   if (dlogits == nullptr) return;
+  const float uni = LS ? eps / (float)V : 0.f, hot = LS ? 1.f - eps : 1.f;
   bf16_t* drow = dlogits + (size_t)r * ldv;
   const int n = count[0];
   const float gs = (valid && n > 0) ? grad_scale / (float)n : 0.f;
@@ -76,7 +95,8 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
         float p = 0.f;
         if (c < V) {
           p = __expf(row[c] - lse);
-          if (c == (int)label) p -= 1.f;
+          if (LS) p -= uni;
+          if (c == (int)label) p -= hot;
         }
         o[e] = p * gs;
       }
@@ -90,12 +110,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
 
 // Register-resident form for rows of up to NV * 4096 columns: 1024 threads hold the whole fp32 row (NV float4 each),
 // so the logits are read from memory once (max, sum-exp and the gradient all come from registers).
-template <int NV>
+template <int NV, bool LS>
 __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ logits, int ldv, int V,
                                                       const int64_t* __restrict__ labels,
                                                       const int32_t* __restrict__ count, float grad_scale,
-                                                      float* __restrict__ loss_rows, bf16_t* __restrict__ dlogits) {
-  __shared__ float sh[32];
+                                                      float* __restrict__ loss_rows, bf16_t* __restrict__ dlogits, float eps) {
+  __shared__ float sh[LS ? 48 : 32];
   const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float* row = logits + (size_t)r * ldv;
   const int64_t label = labels[r];
@@ -144,12 +164,31 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ 
   }
   s = wave_sum(s);
   if (lane == 0) sh[16 + wave] = s;
+  if (LS) {   // the row's mean logit over the V real columns, from the registers
+    float z = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if ((tid + 1024 * j) * 4 + e < V) z += x[j][e];
+    z = wave_sum(z);
+    if (lane == 0) sh[32 + wave] = z;
+  }
   __syncthreads();
   s = 0.f;
 #pragma unroll
   for (int w = 0; w < 16; ++w) s += sh[16 + w];
   const float lse = m + __logf(s);
-  if (tid == 0) loss_rows[r] = lse - row[label];
+  float uni = 0.f, hot = 1.f;
+  if (LS) {
+    float z = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) z += sh[32 + w];
+    uni = eps / (float)V; hot = 1.f - eps;
+    if (tid == 0) loss_rows[r] = lse - hot * row[label] - eps * (z / (float)V);
+  } else {
+    if (tid == 0) loss_rows[r] = lse - row[label];
+  }
   if (dlogits == nullptr) return;
   const int n = count[0];
   const float gs = n > 0 ? grad_scale / (float)n : 0.f;
@@ -162,7 +201,8 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float p = __expf(x[j][e] - lse);  // exp(-inf) = 0 in the pad columns
-        if (i + e == (int)label) p -= 1.f;
+        if (LS && i + e < V) p -= uni;    // (the pad columns stay exactly zero)
+        if (i + e == (int)label) p -= hot;
         o[e] = p * gs;
       }
       const u32x2 pk = {pack2bf(o[0], o[1]), pack2bf(o[2], o[3])};
@@ -202,12 +242,12 @@ __global__ __launch_bounds__(1024) void loss_finish_kernel(const float* __restri
 // is written back IN PLACE over the logits (dlogits == logits is allowed: every element is read before the first
 // store of its thread, and a thread only rewrites what it read).  Halves the head GEMM's store and the CE's read
 // against fp32 logits: 3.3 GB -> 1.65 GB each per step at the benchmark batch.
-template <int NV8>
+template <int NV8, bool LS>
 __global__ __launch_bounds__(1024) void ce_kernel_reg_bf16(const bf16_t* logits, int ldv, int V,
                                                            const int64_t* __restrict__ labels,
                                                            const int32_t* __restrict__ count, float grad_scale,
-                                                           float* __restrict__ loss_rows, bf16_t* dlogits) {
-  __shared__ float sh[33];
+                                                           float* __restrict__ loss_rows, bf16_t* dlogits, float eps) {
+  __shared__ float sh[LS ? 56 : 33];
   const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const bf16_t* row = logits + (size_t)r * ldv;
   const int64_t label = labels[r];
@@ -260,12 +300,31 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg_bf16(const bf16_t* logits,
   }
   s = wave_sum(s);
   if (lane == 0) sh[16 + wave] = s;
+  if (LS) {   // the row's mean logit over the V real columns, from the registers
+    float z = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV8; ++j)
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if ((tid + 1024 * j) * 8 + e < V) z += x[j][e];
+    z = wave_sum(z);
+    if (lane == 0) sh[40 + wave] = z;
+  }
   __syncthreads();
   s = 0.f;
 #pragma unroll
   for (int w = 0; w < 16; ++w) s += sh[16 + w];
   const float lse = m + __logf(s);
-  if (tid == 0) loss_rows[r] = lse - sh[32];
+  float uni = 0.f, hot = 1.f;
+  if (LS) {
+    float z = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) z += sh[40 + w];
+    uni = eps / (float)V; hot = 1.f - eps;
+    if (tid == 0) loss_rows[r] = lse - hot * sh[32] - eps * (z / (float)V);
+  } else {
+    if (tid == 0) loss_rows[r] = lse - sh[32];
+  }
   if (dlogits == nullptr) return;
   const int n = count[0];
   const float gs = n > 0 ? grad_scale / (float)n : 0.f;
@@ -278,7 +337,8 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg_bf16(const bf16_t* logits,
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         float p = __expf(x[j][e] - lse);  // exp(-inf) = 0 in the pad columns
-        if (i + e == (int)label) p -= 1.f;
+        if (LS && i + e < V) p -= uni;    // (the pad columns stay exactly zero)
+        if (i + e == (int)label) p -= hot;
         o[e] = p * gs;
       }
       *reinterpret_cast<u32x4*>(drow + i) = pack8(o);
@@ -396,6 +456,166 @@ __global__ __launch_bounds__(256) void ce_dgrad_finish_kernel(const float* __res
   *reinterpret_cast<u32x4*>(out + (size_t)r * d + c) = pack8(v);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Label smoothing as rank-one terms (kmb_set_label_smoothing).  The target row is (1 - eps) onehot + eps / V over
+// the V real columns.  With the tied head v_r = h_r E^T + b every smoothing term is rank one:
+//   wsum = sum_{j < V} E_j,  bsum = sum_{j < V} b_j,     zbar_r = mean_{j < V} v_rj = (h_r . wsum + bsum) / V       (no sum over the row)
+//   loss_r = log S_r - pick_r + eps (c_r - zbar_r)       (c_r: the row shift = the label's logit, S_r: the act 5 epilogue's row sum)
+//   dlogits_rj = g (softmax_rj - (1 - eps) [j == label_r] - eps / V),   g = lm_factor / n
+// The label's entry of the stored matrix becomes P'[r][label_r] = bf16(exp(pick_r) - (1 - eps) S_r) -- a_r P' then carries the softmax and
+// the onehot part -- and the uniform part never touches the matrix: with beta_r = eps g / V on valid rows (0 elsewhere)
+//   dH_r -= beta_r wsum      (the data-gradient finish, before its one bf16 rounding)
+//   dE_j -= u for j < V,     u = sum_r beta_r h_r      (the weight-gradient launch's bias operand, or its slab reduction's row vector)
+// Both d-wide sums are deterministic: a fixed grid leaves per-workgroup partial rows, kmb_reduce_parts_launch sums them in slot order.
+
+// wsum | bsum: workgroup w sums rows [w * rpw, (w + 1) * rpw) of E and of the bias.  A row is d / 8 16-byte chunks; the 256 threads are
+// CW = min(d / 8, 256) column lanes x 256 / CW row lanes (d = 768: 96 x 2), four rows in flight per thread; the row lanes meet in LDS.
+constexpr int VS_MAX_SLOTS = 512;
+__global__ __launch_bounds__(256) void ce_vocab_sum_kernel(const bf16_t* __restrict__ E, int lde, const float* __restrict__ bias, int V, int d,
+                                                           int rpw, int ldp, float* __restrict__ partials) {
+  extern __shared__ float vs_red[];   // [256 / CW][8 * CW]
+  const int nch = d >> 3, cw = nch < 256 ? nch : 256, rl = 256 / cw;
+  const int tid = threadIdx.x, cl = tid % cw, rlane = tid / cw;
+  const int r0 = blockIdx.x * rpw, r1 = (r0 + rpw) < V ? (r0 + rpw) : V;
+  float* out = partials + (size_t)blockIdx.x * ldp;
+  for (int c0 = 0; c0 < nch; c0 += cw) {   // one trip unless d > 2048
+    const int ch = c0 + cl;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (rlane < rl && ch < nch) {
+      const bf16_t* col = E + (size_t)ch * 8;
+      int r = r0 + rlane;
+      for (; r + 3 * rl < r1; r += 4 * rl) {
+        u32x4 q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = *reinterpret_cast<const u32x4*>(col + (size_t)(r + k * rl) * lde);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float x[8];
+          unpack8(q[k], x);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] += x[e];
+        }
+      }
+      for (; r < r1; r += rl) {
+        float x[8];
+        unpack8(*reinterpret_cast<const u32x4*>(col + (size_t)r * lde), x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += x[e];
+      }
+    }
+    __syncthreads();   // (the previous trip's readers are done)
+    if (rlane < rl) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vs_red[(size_t)rlane * 8 * cw + cl * 8 + e] = acc[e];
+    }
+    __syncthreads();
+    for (int i = tid; i < 8 * cw; i += 256) {
+      const int col = c0 * 8 + i;
+      if (col < d) {
+        float t = 0.f;
+        for (int k = 0; k < rl; ++k) t += vs_red[(size_t)k * 8 * cw + i];
+        out[col] = t;
+      }
+    }
+  }
+  // the bias of the same rows: wave 0, lane-strided, butterfly
+  if (tid < 64) {
+    float b = 0.f;
+    for (int r = r0 + tid; r < r1; r += 64) b += bias[r];
+    b = wave_sum(b);
+    if (tid == 0) out[d] = b;
+  }
+}
+
+// ce_rows_finish_kernel with smoothing.  One wave per row, four rows per trip, a fixed grid (kmb_ce_rows_slots) walking the rows with its
+// stride; each wave keeps sum -beta_r h_r of its rows in its own LDS row, the four meet at the end: u_part[workgroup][d].
+__global__ __launch_bounds__(256) void ce_rows_finish_ls_kernel(const float* __restrict__ row_sums, int ld_sums, int nparts,
+                                                                const float* __restrict__ pick, const float* __restrict__ shift,
+                                                                const int64_t* __restrict__ labels, const int32_t* __restrict__ count,
+                                                                float lm_factor, float eps, int rows, int d, int V,
+                                                                const bf16_t* __restrict__ H, int ldh, const float* __restrict__ wsum,
+                                                                float* __restrict__ loss_rows, float* __restrict__ srow,
+                                                                float* __restrict__ alpha, float* __restrict__ beta, bf16_t* __restrict__ ah,
+                                                                bf16_t* __restrict__ P, int ldp, float* __restrict__ u_part) {
+  extern __shared__ float ls_acc[];   // [4][d]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float* acc = ls_acc + (size_t)wave * d;
+  if (u_part != nullptr)
+    for (int i = lane; i < d; i += 64) acc[i] = 0.f;
+  __syncthreads();   // (below, element lane * 8 + k + 512 t of the wave's row belongs to that one lane in every trip)
+  const int n = count[0];
+  const float bsum = wsum[d], invV = 1.f / (float)V;
+  for (int r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
+    const long long lab = labels[r];
+    const bool valid = lab != -100 && lab >= 0 && lab < V;
+    float s = 0.f;
+    for (int i = lane; i < nparts; i += 64) s += row_sums[(size_t)r * ld_sums + i];
+    s = wave_sum(s);
+    const float a = (valid && n > 0 && s > 0.f) ? lm_factor / ((float)n * s) : 0.f;
+    const float b = (valid && n > 0) ? eps * lm_factor / ((float)n * (float)V) : 0.f;
+    float dot = 0.f;
+    for (int i = lane * 8; i < d; i += 512) {
+      float x[8];
+      unpack8(*reinterpret_cast<const u32x4*>(H + (size_t)r * ldh + i), x);
+      const f32x4 w0 = *reinterpret_cast<const f32x4*>(wsum + i), w1 = *reinterpret_cast<const f32x4*>(wsum + i + 4);
+      const float w[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+#pragma unroll
+      for (int k = 0; k < 8; ++k) dot = fmaf(x[k], w[k], dot);
+      if (u_part != nullptr && b != 0.f) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[i + k] -= b * x[k];
+      }
+      if (ah != nullptr) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] *= a;
+        *reinterpret_cast<u32x4*>(ah + (size_t)r * d + i) = pack8(x);
+      }
+    }
+    dot = wave_sum(dot);
+    if (lane == 0) {
+      const float pk = pick != nullptr ? pick[r] : 0.f;
+      const float zbar = (dot + bsum) * invV;
+      loss_rows[r] = valid ? __logf(s) - pk + eps * (shift[r] - zbar) : 0.f;
+      srow[r] = valid ? s : 0.f;
+      alpha[r] = a;
+      beta[r] = b;
+      if (valid && P != nullptr) P[(size_t)r * ldp + lab] = f2bf(__expf(pk) - (1.f - eps) * s);
+    }
+  }
+  if (u_part == nullptr) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < d; i += 256)
+    u_part[(size_t)blockIdx.x * d + i] = ((ls_acc[i] + ls_acc[d + i]) + ls_acc[2 * d + i]) + ls_acc[3 * d + i];
+}
+
+// ce_dgrad_finish_kernel with the vector term: dH_r = a_r * sum_s slab[s][r] - beta_r * wsum, one rounding
+__global__ __launch_bounds__(256) void ce_dgrad_finish_ls_kernel(const float* __restrict__ slab, int nslabs, size_t stride,
+                                                                 const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                                 const float* __restrict__ wsum, bf16_t* __restrict__ out, int rows, int d) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;   // chunk of 8 columns
+  const int per_row = d >> 3;
+  const int r = (int)(idx / per_row);
+  if (r >= rows) return;
+  const int c = (int)(idx - (size_t)r * per_row) * 8;
+  const float a = alpha[r], b = beta[r];
+  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (a != 0.f) {
+    const float* src = slab + (size_t)r * d + c;
+    f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
+    add_slabs2<4>(lo, hi, src, stride, nslabs);
+    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] *= a;
+  }
+  if (b != 0.f) {
+    const f32x4 w0 = *reinterpret_cast<const f32x4*>(wsum + c), w1 = *reinterpret_cast<const f32x4*>(wsum + c + 4);
+    const float w[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] -= b * w[k];
+  }
+  *reinterpret_cast<u32x4*>(out + (size_t)r * d + c) = pack8(v);
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // Scoring a given target sequence (kmb_score; reference scripts/filter_reason.py:24-52: log_softmax over the [B, T, V] logits,
@@ -480,6 +700,51 @@ hipError_t kmb_ce_dgrad_finish_launch(const float* slab, int nslabs, size_t stri
   return hipGetLastError();
 }
 
+int kmb_ce_vocab_sum_ld(int d) { return d + 8; }
+int kmb_ce_vocab_sum_slots(int V, int d) {
+  // >= 32 rows per row lane and workgroup (eight trips of four rows in flight), at most VS_MAX_SLOTS workgroups: 50320 x 768 -> 512 slots of 99 rows
+  const int nch = d >> 3, cw = nch < 256 ? nch : 256, rl = cw > 0 ? 256 / cw : 1;
+  int slots = (V + 32 * rl - 1) / (32 * rl);
+  if (slots > VS_MAX_SLOTS) slots = VS_MAX_SLOTS;
+  return slots < 1 ? 1 : slots;
+}
+hipError_t kmb_ce_vocab_sum_launch(const bf16_t* E, int lde, const float* bias, int V, int d, float* partials, float* wsum, hipStream_t stream) {
+  if (V <= 0 || d <= 0 || (d & 7) || (lde & 7) || lde < d || ((uintptr_t)E & 15) || ((uintptr_t)wsum & 15)) return hipErrorInvalidValue;
+  const int slots = kmb_ce_vocab_sum_slots(V, d), ld = kmb_ce_vocab_sum_ld(d);
+  const int rpw = (V + slots - 1) / slots;
+  const int nch = d >> 3, cw = nch < 256 ? nch : 256, rl = 256 / cw;
+  hipLaunchKernelGGL(ce_vocab_sum_kernel, dim3(slots), dim3(256), (size_t)rl * 8 * cw * sizeof(float), stream, E, lde, bias, V, d, rpw, ld, partials);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return kmb_reduce_parts_launch(partials, slots, ld, wsum, d + 1, stream);
+}
+int kmb_ce_rows_slots(int rows) {
+  const int wgs = (rows + 3) / 4;
+  return wgs < 1024 ? (wgs < 1 ? 1 : wgs) : 1024;   // 1024 workgroups: eight rows per wave at the benchmark batch, 3 MB of partial rows at d = 768
+}
+hipError_t kmb_ce_rows_finish_ls_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift,
+                                        const int64_t* labels, const int32_t* count, float lm_factor, float eps, int rows, int d, int V,
+                                        const bf16_t* H, int ldh, const float* wsum, float* loss_rows, float* srow, float* alpha, float* beta,
+                                        bf16_t* ah, bf16_t* P, int ldp, float* u_partials, float* neg_u, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
+  if (d <= 0 || (d & 7) || (ldh & 7) || d > 4096 || ((uintptr_t)wsum & 15) || (u_partials == nullptr) != (neg_u == nullptr)) return hipErrorInvalidValue;
+  const int slots = kmb_ce_rows_slots(rows);
+  hipLaunchKernelGGL(ce_rows_finish_ls_kernel, dim3(slots), dim3(256), (size_t)4 * d * sizeof(float), stream, row_sums, ld_sums, nparts, pick, shift,
+                     labels, count, lm_factor, eps, rows, d, V, H, ldh, wsum, loss_rows, srow, alpha, beta, ah, P, ldp, u_partials);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || neg_u == nullptr) return e;
+  return kmb_reduce_parts_launch(u_partials, slots, d, neg_u, d, stream);
+}
+hipError_t kmb_ce_dgrad_finish_ls_launch(const float* slab, int nslabs, size_t stride, const float* alpha, const float* beta,
+                                         const float* wsum, bf16_t* out, int rows, int d, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
+  if ((d & 7) || (stride & 3) || ((uintptr_t)wsum & 15)) return hipErrorInvalidValue;
+  const size_t chunks = (size_t)rows * (d >> 3);
+  hipLaunchKernelGGL(ce_dgrad_finish_ls_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, slab, nslabs, stride, alpha,
+                     beta, wsum, out, rows, d);
+  return hipGetLastError();
+}
+
 hipError_t kmb_score_rows_finish_launch(const float* stats, int nblk, const float* label_logit, const int64_t* labels, int rows, int V,
                                         float* logp, hipStream_t stream) {
   if (rows <= 0) return hipSuccess;
@@ -500,24 +765,34 @@ hipError_t kmb_count_valid_launch(const int64_t* labels, int n, int V, int32_t* 
 }
 
 hipError_t kmb_ce_launch(const float* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count,
-                         float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream) {
+                         float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps) {
   if (rows <= 0) return hipSuccess;
-  if ((ldv & 7) || ((uintptr_t)logits & 15)) return hipErrorInvalidValue;
-  if (ldv <= 13 * 4096)
-    hipLaunchKernelGGL((ce_kernel_reg<13>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits);
+  if ((ldv & 7) || ((uintptr_t)logits & 15) || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
+  if (eps > 0.f) {
+    if (ldv <= 13 * 4096)
+      hipLaunchKernelGGL((ce_kernel_reg<13, true>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
+    else
+      hipLaunchKernelGGL(ce_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
+  } else if (ldv <= 13 * 4096)
+    hipLaunchKernelGGL((ce_kernel_reg<13, false>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
   else
-    hipLaunchKernelGGL(ce_kernel, dim3(rows), dim3(256), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits);
+    hipLaunchKernelGGL(ce_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
   return hipGetLastError();
 }
 
 hipError_t kmb_ce_bf16_launch(const bf16_t* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count,
-                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream) {
+                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps) {
   if (rows <= 0) return hipSuccess;
-  if ((ldv & 7) || ((uintptr_t)logits & 15) || ldv > 8 * 8192) return hipErrorInvalidValue;
-  if (ldv <= 7 * 8192)
-    hipLaunchKernelGGL((ce_kernel_reg_bf16<7>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits);
+  if ((ldv & 7) || ((uintptr_t)logits & 15) || ldv > 8 * 8192 || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
+  if (eps > 0.f) {
+    if (ldv <= 7 * 8192)
+      hipLaunchKernelGGL((ce_kernel_reg_bf16<7, true>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
+    else
+      hipLaunchKernelGGL((ce_kernel_reg_bf16<8, true>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
+  } else if (ldv <= 7 * 8192)
+    hipLaunchKernelGGL((ce_kernel_reg_bf16<7, false>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
   else
-    hipLaunchKernelGGL((ce_kernel_reg_bf16<8>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits);
+    hipLaunchKernelGGL((ce_kernel_reg_bf16<8, false>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
   return hipGetLastError();
 }
 

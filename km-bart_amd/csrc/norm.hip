@@ -396,6 +396,22 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
     reinterpret_cast<f32x4*>(out)[i] = a;
   }
 }
+// ... with a row vector added to every row of the [n / N, N] result (the tied matrix's split weight gradient under label smoothing: -u)
+__global__ __launch_bounds__(256) void reduce_slabs_rowvec_kernel(const float* __restrict__ slabs, int nslabs, size_t stride,
+                                                                  float* __restrict__ out, size_t n4, float beta,
+                                                                  const float* __restrict__ rowvec, int N4) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    f32x4 a = reinterpret_cast<const f32x4*>(slabs)[i];
+    add_slabs<8>(a, slabs + 4 * i, stride, nslabs);
+    const f32x4 v = reinterpret_cast<const f32x4*>(rowvec)[i % (size_t)N4];
+    a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
+    if (beta != 0.f) {
+      const f32x4 o = reinterpret_cast<const f32x4*>(out)[i];
+      a[0] += beta * o[0]; a[1] += beta * o[1]; a[2] += beta * o[2]; a[3] += beta * o[3];
+    }
+    reinterpret_cast<f32x4*>(out)[i] = a;
+  }
+}
 
 // the same sum stored as bf16 (a split-K data gradient): n % 8 == 0
 __global__ __launch_bounds__(256) void reduce_slabs_bf16_kernel(const float* __restrict__ slabs, int nslabs, size_t stride,
@@ -574,6 +590,16 @@ hipError_t kmb_reduce_slabs_launch(const float* slabs, int nslabs, size_t stride
   size_t blocks = (n / 4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slabs, nslabs, stride, out, n / 4, beta);
+  return hipGetLastError();
+}
+
+hipError_t kmb_reduce_slabs_rowvec_launch(const float* slabs, int nslabs, size_t stride, float* out, size_t n, float beta,
+                                          const float* rowvec, int N, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  if ((n & 3) || (stride & 3) || N <= 0 || (N & 3) || (n % (size_t)N) || ((uintptr_t)rowvec & 15)) return hipErrorInvalidValue;
+  size_t blocks = (n / 4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(reduce_slabs_rowvec_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, slabs, nslabs, stride, out, n / 4, beta, rowvec, N / 4);
   return hipGetLastError();
 }
 

@@ -117,7 +117,9 @@ PROTOTYPES = {
     "kmb_activation_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
     "kmb_set_classif_dropout": (C.c_int, [c_p, f32]),
     "kmb_classif_dropout_site": (C.c_int, [c_p, C.c_int, C.c_int, C.POINTER(u32), C.POINTER(u32)]),
-    "kmb_abi_sizeof_attn": (C.c_int, []),
+    "kmb_set_label_smoothing": (C.c_int, [c_p, f32]),
+    "kmb_last_head_form": (C.c_int, [c_p]),
+    "kmb_abi_sizeof_attn":(C.c_int, []),
     "kmb_bucket_count": (C.c_int, [c_p]),
     "kmb_bucket_range": (C.c_int, [c_p, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
     "kmb_stream_wait_bucket": (C.c_int, [c_p, C.c_int, c_p]),
@@ -246,7 +248,16 @@ PROTOTYPES = {
     "kmb_op_ce_rows_finish": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p, c_p, f32, C.c_int, C.c_int, C.c_int, c_p, C.c_int, c_p, c_p,
                                         c_p, c_p, c_p, C.c_int, c_p]),
     "kmb_op_ce_dgrad_finish": (C.c_int, [c_p, C.c_int, i64, c_p, c_p, C.c_int, C.c_int, c_p]),
-    "kmb_op_kl_div": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, c_p, c_p, C.c_int, c_p]),
+    "kmb_op_ce_smooth": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, f32, f32, c_p, c_p, c_p, c_p, c_p]),
+    "kmb_op_ce_bf16_smooth": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, f32, f32, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "kmb_op_ce_vocab_sum_scratch": (i64, [C.c_int, C.c_int]),
+    "kmb_op_ce_vocab_sum": (C.c_int, [c_p, C.c_int, c_p, C.c_int, C.c_int, c_p, c_p, c_p]),
+    "kmb_op_ce_rows_finish_smooth_scratch": (i64, [C.c_int, C.c_int]),
+    "kmb_op_ce_rows_finish_smooth": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p, f32, f32, C.c_int, C.c_int, C.c_int, c_p, C.c_int,
+                                               c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.c_int, c_p, c_p, c_p]),
+    "kmb_op_ce_dgrad_finish_smooth": (C.c_int, [c_p, C.c_int, i64, c_p, c_p, c_p, c_p, C.c_int, C.c_int, c_p]),
+    "kmb_op_reduce_slabs_rowvec": (C.c_int, [c_p, C.c_int, i64, c_p, C.c_int, C.c_int, f32, c_p, c_p]),
+    "kmb_op_kl_div":(C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, c_p, c_p, C.c_int, c_p]),
     "kmb_op_gather_rows_bf16": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p]),
     "kmb_op_gather_rows_drop_bf16": (C.c_int, [c_p, C.c_int, c_p, c_p, c_p, C.c_int, C.c_int, C.c_int, C.POINTER(KmbDrop), c_p]),
     "kmb_op_scatter_add_rows": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, c_p]),

@@ -111,6 +111,7 @@ class Engine:
         self.set_attention_dropout(float(getattr(config, "attention_dropout", 0.0)))
         self.set_activation_dropout(float(getattr(config, "activation_dropout", 0.0)))
         self.set_classif_dropout(float(getattr(config, "classif_dropout", 0.0)))   # (without heads there is nothing to drop: no effect)
+        self.set_label_smoothing(float(getattr(config, "label_smoothing", 0.0)))
         with torch.cuda.device(self.device):
             n = self.lib.kmb_arena_elems(h)
             nb = self.lib.kmb_bf16_arena_elems(h)
@@ -204,6 +205,17 @@ class Engine:
         next training-mode pre-training forward on; eval forwards, score() and generation never drop."""
         check(self.lib.kmb_set_classif_dropout(self.h, C.c_float(float(p))))
         self.classif_dropout = float(p)
+
+    def set_label_smoothing(self, eps):
+        """Label smoothing of the LM cross-entropy (torch's CrossEntropyLoss(label_smoothing=eps)), 0 <= eps < 1, from the next forward
+        with labels on, in train and eval mode alike; score() and generation are untouched.  0 runs exactly what ran without it."""
+        check(self.lib.kmb_set_label_smoothing(self.h, C.c_float(float(eps))))
+        self.label_smoothing = float(eps)
+
+    def last_head_form(self):
+        """Which LM head the last forward with labels took: 0 fp32 logits, 1 bf16 logits turned into their gradient in place, 2 the fused
+        head (no pass over the logits); -1 before the first."""
+        return int(self.lib.kmb_last_head_form(self.h))
 
     def classif_dropout_site(self, head, which):
         """(thr16, seed) the last training forward used at a head site (head 0 masked-region, 1 attribute, 2 relation; which 0 the

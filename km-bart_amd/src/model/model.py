@@ -449,6 +449,13 @@ class _EncoderHandle:
     forward = __call__
 
 
+def _check_label_smoothing(eps):
+    eps = float(eps)
+    if not (0.0 <= eps < 1.0):   # (NaN fails both)
+        raise ValueError("label_smoothing must be in [0, 1), got %r" % (eps,))
+    return eps
+
+
 class MultiModalBartForConditionalGeneration(nn.Module):
     base_model_prefix = "model"
     config_class = MultiModalBartConfig
@@ -478,6 +485,19 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         self._anchor = None
         self._post_backward = None  # set by the data-parallel wrapper
         self._dec_hidden_for_logits = None
+        self._label_smoothing = _check_label_smoothing(getattr(config, "label_smoothing", 0.0))
+
+    @property
+    def label_smoothing(self):
+        """eps of the LM criterion, CrossEntropyLoss(label_smoothing=eps): part of every forward(labels=...), in train and eval mode
+        (score() stays the exact log-probabilities).  Starts from config.label_smoothing (0.0 when the config has none)."""
+        return self._label_smoothing
+
+    @label_smoothing.setter
+    def label_smoothing(self, eps):
+        self._label_smoothing = _check_label_smoothing(eps)
+        if self._engine is not None:
+            self._engine.set_label_smoothing(self._label_smoothing)
 
     # ------------------------------------------------------------------ nn.Module surface
     def named_parameters(self, prefix="", recurse=True, remove_duplicate=True):
@@ -540,6 +560,7 @@ class MultiModalBartForConditionalGeneration(nn.Module):
                 raise RuntimeError("model already lives on %s" % self._engine.device)
             return self
         eng = Engine(self.config, device, with_heads=self._with_heads)
+        eng.set_label_smoothing(self._label_smoothing)
         with torch.no_grad():
             for n in self._names:
                 eng.view(eng.params, n).copy_(self._p[n].detach().to(device))

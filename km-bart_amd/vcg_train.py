@@ -82,6 +82,8 @@ def main(rank, args):
                                                                        error_on_mismatch=False)
     else:
         model = MultiModalBartForConditionalGeneration(config=config)
+    if args.label_smoothing > 0.0:
+        model.label_smoothing = args.label_smoothing
     model.to(device)
     if distributed:
         model = DistributedDataParallel(model, device_ids=[rank], find_unused_parameters=True)
@@ -139,6 +141,8 @@ def parse_args(argv=None):
                    help="skip an optimizer step whose gradients hold a NaN or Inf (decided on the device, no synchronisation)")
     p.add_argument("--accumulation_steps", default=1, type=int,
                    help="optimizer step every N batches on the sum of their gradients, each batch's loss divided by N (default 1)")
+    p.add_argument("--label_smoothing", default=0.0, type=float,
+                   help="label smoothing of the LM cross-entropy, in [0, 1) (default 0.0: the model config's value, if it has one, stays)")
     p.add_argument("--master_port", type=str, default="12355")
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--num_workers", type=int, default=0)
@@ -152,6 +156,8 @@ def parse_args(argv=None):
         raise ValueError("--cpu: this build has no CPU path (the hot path runs on MI355X only)")
     if args.accumulation_steps < 1:
         raise ValueError("--accumulation_steps must be >= 1, got %d" % args.accumulation_steps)
+    if not (0.0 <= args.label_smoothing < 1.0):
+        raise ValueError("--label_smoothing must be in [0, 1), got %r" % (args.label_smoothing,))
     if args.checkpoint is None and args.model_config is None:
         raise ValueError("--model_config and --checkpoint cannot be empty at the same time")
     if args.synthetic <= 0 and args.data_dir is None:
