@@ -727,6 +727,26 @@ int64_t kmb_op_ln_bwd_scratch(int M, int D);
 int kmb_op_ln_bwd(const kmb_bf16* dy, const kmb_bf16* z, const float* mean, const float* rstd, const float* gamma,
                   kmb_bf16* dz, kmb_bf16* out2, const KmbDrop* dy_drop, const KmbDrop* out2_drop, float* dgamma,
                   float* dbeta, float* scratch, int M, int D, void* stream);
+/* Test entry points of the row kernels between the GEMMs (tests/test_row_kernels_gpu.py).  Each refuses, with a message, what its
+ * kernel cannot take: a null required pointer, a misaligned one, a ragged width or stride.
+ * kmb_op_ln_bwd_sub: kmb_op_ln_bwd reduced as a training step reduces it, in ONE launch: dgamma | dbeta are one 2 D-wide output
+ * (dbeta == dgamma + D, as in the gradient arena), dsub [D] receives the kernel's third partial: the column sums of the sub-layer
+ * gradient (of out2's fp32 values under out2_drop when out2 is given, of dz's otherwise; summed before the bf16 rounding). */
+int kmb_op_ln_bwd_sub(const kmb_bf16* dy, const kmb_bf16* z, const float* mean, const float* rstd, const float* gamma,
+                      kmb_bf16* dz, kmb_bf16* out2, const KmbDrop* dy_drop, const KmbDrop* out2_drop, float* dgamma,
+                      float* dbeta, float* dsub, float* scratch, int M, int D, void* stream);
+/* y = LayerNorm(bf16((slab 0 + slab 1 + ... in slice order) + bias + residual)); slabs [nslabs][stride] floats, rows of D; bias may be
+ * NULL, residual is required; D % 8 == 0, D <= 1024, stride % 4 == 0, ld_res % 8 == 0 */
+int kmb_op_ln_fwd_slabs(const float* slabs, int nslabs, int64_t stride, const float* bias, const kmb_bf16* residual, int ld_res,
+                        const float* gamma, const float* beta, kmb_bf16* y, int M, int D, float eps, void* stream);
+/* out[i] = beta * out[i] + slab 0 [i] + slab 1 [i] + ... (slice order); n % 4 == 0 (fp32 out), n % 8 == 0 (bf16 out), stride % 4 == 0 */
+int kmb_op_reduce_slabs(const float* slabs, int nslabs, int64_t stride, float* out, int64_t n, float beta, void* stream);
+int kmb_op_reduce_slabs_bf16(const float* slabs, int nslabs, int64_t stride, kmb_bf16* out, int64_t n, void* stream);
+/* out[r][c] = bf16(drop((sum of the slabs + bias[c]) * (c < col_scale_n ? col_scale : 1)) + residual[r][c]); bias, drop and residual
+ * may be NULL; the mask is kmb_op_dropout_mask(seed, thr16 / 65536, M, N); N, ld_res and ld_out multiples of 8 */
+int kmb_op_reduce_slabs_epi(const float* slabs, int nslabs, int64_t stride, const float* bias, float col_scale, int col_scale_n,
+                            const KmbDrop* drop, const kmb_bf16* residual, int ld_res, kmb_bf16* out, int ld_out, int M, int N,
+                            void* stream);
 int64_t kmb_op_colsum_scratch(int M, int N);
 int kmb_op_colsum(const kmb_bf16* X, int ld, int M, int N, float* out, float* scratch, void* stream);
 int kmb_op_img_rowmap(const int64_t* ids, const int32_t* feat_off, int B, int S, int64_t img_feat_id, int64_t cls_id,

@@ -153,6 +153,68 @@ int kmb_op_ln_bwd(const kmb_bf16* dy, const kmb_bf16* z, const float* mean, cons
   if (rc) return rc;
   return hipfail(kmb_reduce_parts_launch(scratch + D, np, 3 * D, dbeta, D, s), "ln_bwd reduce");
 }
+// the same kernel reduced as the engine reduces it (engine_train.cpp ln_backward with a bias slot): ONE kmb_reduce_parts2_launch sends
+// columns [0, 2 D) of the partial rows to dgamma | dbeta (adjacent, as in the arena) and the third partial, the column sums of the
+// sub-layer gradient, to dsub
+int kmb_op_ln_bwd_sub(const kmb_bf16* dy, const kmb_bf16* z, const float* mean, const float* rstd, const float* gamma,
+                      kmb_bf16* dz, kmb_bf16* out2, const KmbDrop* dy_drop, const KmbDrop* out2_drop, float* dgamma,
+                      float* dbeta, float* dsub, float* scratch, int M, int D, void* stream) {
+  if (!dy || !z || !mean || !rstd || !gamma || !dz || !dgamma || !dbeta || !dsub || !scratch || M <= 0 || D <= 0)
+    return kmb_set_error("kmb_op_ln_bwd_sub: dy, z, mean, rstd, gamma, dz, dgamma, dbeta, dsub and scratch are required, M and D positive");
+  if ((D & 7) || D > 2048) return kmb_set_error("kmb_op_ln_bwd_sub: D must be a multiple of 8 and at most 2048");
+  if (dbeta != dgamma + D) return kmb_set_error("kmb_op_ln_bwd_sub: dbeta must be dgamma + D (one 2 D-wide output, as in the gradient arena)");
+  if ((((uintptr_t)dy | (uintptr_t)z | (uintptr_t)dz | (uintptr_t)out2) & 7) ||
+      (((uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)gamma | (uintptr_t)dgamma | (uintptr_t)dsub | (uintptr_t)scratch) & 3))
+    return kmb_set_error("kmb_op_ln_bwd_sub: dy, z, dz and out2 must be 8-byte aligned, the float pointers 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const KmbDrop none{0u, 0u, 1.f};
+  const int rc = hipfail(kmb_ln_bwd_launch(dy, z, mean, rstd, gamma, dz, out2, dy_drop ? *dy_drop : none,
+                                           out2_drop ? *out2_drop : none, scratch, M, D, s), "ln_bwd");
+  if (rc) return rc;
+  return hipfail(kmb_reduce_parts2_launch(scratch, kmb_ln_bwd_parts(M), 3 * D, dgamma, 2 * D, dsub, D, s), "ln_bwd reduce2");
+}
+// the decode step's residual projection behind a split-K GEMM: slabs summed in slice order, + bias + residual, bf16, LayerNorm
+int kmb_op_ln_fwd_slabs(const float* slabs, int nslabs, int64_t stride, const float* bias, const kmb_bf16* residual, int ld_res,
+                        const float* gamma, const float* beta, kmb_bf16* y, int M, int D, float eps, void* stream) {
+  if (!slabs || !residual || !gamma || !beta || !y || nslabs < 1 || stride < 0 || M <= 0 || D <= 0 || ld_res < D)
+    return kmb_set_error("kmb_op_ln_fwd_slabs: slabs, residual (the kernel always reads it), gamma, beta and y are required, "
+                         "nslabs >= 1, stride >= 0, M and D positive, ld_res >= D");
+  if ((D & 7) || D > 1024) return kmb_set_error("kmb_op_ln_fwd_slabs: D must be a multiple of 8 and at most 1024");
+  if ((stride & 3) || (ld_res & 7)) return kmb_set_error("kmb_op_ln_fwd_slabs: stride must be a multiple of 4, ld_res of 8");
+  if ((((uintptr_t)slabs | (uintptr_t)residual | (uintptr_t)y) & 15) || (((uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta) & 3))
+    return kmb_set_error("kmb_op_ln_fwd_slabs: slabs, residual and y must be 16-byte aligned, bias, gamma and beta 4-byte aligned");
+  return hipfail(kmb_ln_fwd_slabs_launch(slabs, nslabs, (size_t)stride, bias, residual, ld_res, gamma, beta, y, M, D, eps,
+                                         (hipStream_t)stream), "ln_fwd_slabs");
+}
+// out[i] = beta * out[i] + sum over s < nslabs of slabs[s * stride + i], in slice order (a split weight gradient)
+int kmb_op_reduce_slabs(const float* slabs, int nslabs, int64_t stride, float* out, int64_t n, float beta, void* stream) {
+  if (!slabs || !out || nslabs < 1 || stride < 0 || n <= 0) return kmb_set_error("kmb_op_reduce_slabs: bad arguments");
+  if ((n & 3) || (stride & 3) || (((uintptr_t)slabs | (uintptr_t)out) & 15))
+    return kmb_set_error("kmb_op_reduce_slabs: n and stride must be multiples of 4, the pointers 16-byte aligned");
+  return hipfail(kmb_reduce_slabs_launch(slabs, nslabs, (size_t)stride, out, (size_t)n, beta, (hipStream_t)stream), "reduce_slabs");
+}
+// the same sum stored as bf16 (a split data gradient)
+int kmb_op_reduce_slabs_bf16(const float* slabs, int nslabs, int64_t stride, kmb_bf16* out, int64_t n, void* stream) {
+  if (!slabs || !out || nslabs < 1 || stride < 0 || n <= 0) return kmb_set_error("kmb_op_reduce_slabs_bf16: bad arguments");
+  if ((n & 7) || (stride & 3) || (((uintptr_t)slabs | (uintptr_t)out) & 15))
+    return kmb_set_error("kmb_op_reduce_slabs_bf16: n must be a multiple of 8, stride of 4, the pointers 16-byte aligned");
+  return hipfail(kmb_reduce_slabs_bf16_launch(slabs, nslabs, (size_t)stride, out, (size_t)n, (hipStream_t)stream), "reduce_slabs_bf16");
+}
+// ... with a linear layer's epilogue: out = bf16(drop((sum + bias) * (column < col_scale_n ? col_scale : 1)) + residual)
+int kmb_op_reduce_slabs_epi(const float* slabs, int nslabs, int64_t stride, const float* bias, float col_scale, int col_scale_n,
+                            const KmbDrop* drop, const kmb_bf16* residual, int ld_res, kmb_bf16* out, int ld_out, int M, int N,
+                            void* stream) {
+  if (!slabs || !out || nslabs < 1 || stride < 0 || M <= 0 || N <= 0 || ld_out < N || (residual && ld_res < N))
+    return kmb_set_error("kmb_op_reduce_slabs_epi: slabs and out are required, nslabs >= 1, stride >= 0, M and N positive, ld_out and ld_res >= N");
+  if ((N & 7) || (stride & 3) || (ld_out & 7) || (residual && (ld_res & 7)))
+    return kmb_set_error("kmb_op_reduce_slabs_epi: N, ld_out and ld_res must be multiples of 8, stride of 4");
+  if ((((uintptr_t)slabs | (uintptr_t)out | (uintptr_t)residual) & 15) || ((uintptr_t)bias & 3))
+    return kmb_set_error("kmb_op_reduce_slabs_epi: slabs, out and residual must be 16-byte aligned, bias 4-byte aligned");
+  const KmbDrop dr = drop ? *drop : KmbDrop{0u, 0u, 1.f};
+  if (dr.thr16 > 65535u) return kmb_set_error("kmb_op_reduce_slabs_epi: thr16 must be at most 65535");
+  return hipfail(kmb_reduce_slabs_epi_launch(slabs, nslabs, (size_t)stride, bias, col_scale, col_scale_n, dr, residual, ld_res, out,
+                                             ld_out, M, N, (hipStream_t)stream), "reduce_slabs_epi");
+}
 int64_t kmb_op_colsum_scratch(int M, int N) { return (int64_t)kmb_colsum_parts(M) * N; }
 int kmb_op_colsum(const kmb_bf16* X, int ld, int M, int N, float* out, float* scratch, void* stream) {
   hipStream_t s = (hipStream_t)stream;

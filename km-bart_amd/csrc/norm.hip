@@ -356,10 +356,12 @@ __global__ __launch_bounds__(256, NQ <= 3 ? 4 : 1) void ln_bwd_kernel(const bf16
   }
 }
 
-// out[c] = beta*out[c] + sum_p partials[p*stride + c].  Two shapes of the same reduction:
-//  (a) many partial rows, few columns (LayerNorm / bias gradients): 32 columns x 8 part-lanes per block
-// (out2 != nullptr: columns [n, n + n2) of the partial rows go to out2 -- LayerNorm's dgamma | dbeta and the bias gradient
-//  of the sub-layer in ONE launch)
+// Two shapes of the same reduction over partial results:
+//  (a) many partial rows, few columns (LayerNorm / bias gradients): out[c] = sum_p partials[p*stride + c], the destination is
+//      OVERWRITTEN (no beta: nothing is read from out); 32 columns x PL part-lanes per block, part-lane l adds rows l, l + PL, ...
+//      in order and the PL sums are added in lane order
+// (out2 != nullptr: columns [n1, n_all) of the partial rows go to out2[0, n_all - n1) -- LayerNorm's dgamma | dbeta and the bias
+//  gradient of the sub-layer in ONE launch)
 template <int PL>  // part-lanes per block: 32 columns x PL part-lanes
 __global__ __launch_bounds__(32 * PL) void reduce_parts_kernel(const float* __restrict__ partials, int nparts,
                                                                size_t stride, float* __restrict__ out, int n_all,

@@ -232,6 +232,13 @@ PROTOTYPES = {
     "kmb_op_ln_bwd_scratch": (i64, [C.c_int, C.c_int]),
     "kmb_op_ln_bwd": (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(KmbDrop), C.POINTER(KmbDrop), c_p, c_p,
                                 c_p, C.c_int, C.c_int, c_p]),
+    "kmb_op_ln_bwd_sub": (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(KmbDrop), C.POINTER(KmbDrop), c_p, c_p,
+                                    c_p, c_p, C.c_int, C.c_int, c_p]),
+    "kmb_op_ln_fwd_slabs": (C.c_int, [c_p, C.c_int, i64, c_p, c_p, C.c_int, c_p, c_p, c_p, C.c_int, C.c_int, f32, c_p]),
+    "kmb_op_reduce_slabs": (C.c_int, [c_p, C.c_int, i64, c_p, i64, f32, c_p]),
+    "kmb_op_reduce_slabs_bf16": (C.c_int, [c_p, C.c_int, i64, c_p, i64, c_p]),
+    "kmb_op_reduce_slabs_epi": (C.c_int, [c_p, C.c_int, i64, c_p, f32, C.c_int, C.POINTER(KmbDrop), c_p, C.c_int, c_p, C.c_int,
+                                          C.c_int, C.c_int, c_p]),
     "kmb_op_colsum_scratch": (i64, [C.c_int, C.c_int]),
     "kmb_op_colsum": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p]),
     "kmb_op_img_rowmap": (C.c_int, [c_p, c_p, C.c_int, C.c_int, i64, i64, c_p, c_p, c_p]),
