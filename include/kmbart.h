@@ -276,7 +276,16 @@ typedef struct kmb_forward_opts {
   const kmb_bf16* encoder_states;   /* [B*S, d_model] or NULL: skip the encoder and use these states (model.py:76-83) */
   kmb_bf16* decoder_states_out;     /* [B*T, d_model] or NULL: copy of the last decoder hidden states (model.py:87-103) */
   int32_t skip_head;                /* 1: stop after the decoder (no logits, no loss): MultiModalBartModel.forward */
+  /* Per-row weights of the LM cross-entropy: L = sum_r w_r nll_r / D over the rows with a valid label, nll_r with
+   * the label-smoothing term when that is on; the logits-gradient row is w_r lm_factor / D (softmax - target).  Negative and zero weights
+   * are legal; a row whose label is -100 or out of range contributes exactly zero loss and an exactly zero gradient row whatever its
+   * weight holds (NaN included: it is not read).  Honoured by all three head forms and by the fp32 validation mode's loss; only the LM
+   * term is weighted (kmb_forward_pretrain_ex: lm_factor multiplies the weighted term, the other heads are untouched).  row_weights
+   * without labels is refused.  NULL and loss_reduction 0 run exactly the launches kmb_forward runs. */
+  const float* row_weights;         /* [B*T] fp32 on the device, indexed like labels, or NULL */
+  int32_t loss_reduction;           /* 0 mean: D = the number of valid labels (NaN without one); 1 sum: D = 1 (exactly 0 without one) */
 } kmb_forward_opts;
+int kmb_abi_sizeof_forward_opts(void);   /* sizeof(kmb_forward_opts) as the library was compiled (cf. kmb_abi_sizeof_attn) */
 /* kmb_forward with those options.  With encoder_states AND need_grad the following kmb_backward stops at the given states:
  * the encoder's parameter gradients are zero, dL / d states comes from kmb_encoder_states_grad (the reference's
  * `forward(encoder_outputs=...)` with a tensor that requires grad, src/model/model.py:76-83).  In the fp32 validation mode the
@@ -803,6 +812,23 @@ int kmb_op_ce_rows_finish_smooth(const float* row_sums, int ld_sums, int nparts,
 /* out[r] = bf16(alpha[r] * sum over s < nslabs of slab[s * stride + r * d ...] - beta[r] * wsum): one rounding */
 int kmb_op_ce_dgrad_finish_smooth(const float* slab, int nslabs, int64_t stride, const float* alpha, const float* beta, const float* wsum,
                                   kmb_bf16* out, int rows, int d, void* stream);
+/* Per-row loss weights (kmb_forward_opts.row_weights / loss_reduction), piece by piece.  weights: [rows] fp32 or NULL; reduction 0 mean,
+ * 1 sum.  loss_rows[r] and the row's gradient factor are multiplied by weights[r] (read only in rows with a valid label); with reduction 1
+ * the denominator is 1 (0 without a valid label) and loss[0] the plain sum.  `count` holds TWO words here: count[0] the number of valid
+ * labels, count[1] the 0 / 1 denominator word that reduction 1 uses.  eps = 0 runs the plain instance, eps > 0 the label-smoothing one.
+ * NULL weights with reduction 0 launch what kmb_op_ce / kmb_op_ce_bf16 / kmb_op_ce_rows_finish (or their _smooth forms) launch. */
+int kmb_op_ce_weighted(const float* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                       const float* weights, int reduction, float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, void* stream);
+int kmb_op_ce_bf16_weighted(const kmb_bf16* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                            const float* weights, int reduction, float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss,
+                            int32_t* status, void* stream);
+/* kmb_op_ce_rows_finish (eps = 0: shift, wsum, beta, neg_u and scratch are not used and may be NULL) or kmb_op_ce_rows_finish_smooth
+ * (eps > 0) with weights: loss_rows, alpha, the a . H copy, beta and neg_u carry weights[r]; srow and the label's entry of P do not.
+ * count[0] is the caller's (kmb_op_count_valid); with reduction 1 the entry writes count[1] and divides by it. */
+int kmb_op_ce_rows_finish_weighted(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift,
+                                   const int64_t* labels, int32_t* count, float lm_factor, float eps, const float* weights, int reduction,
+                                   int rows, int d, int V, const kmb_bf16* H, int ldh, const float* wsum, float* loss_rows, float* srow,
+                                   float* alpha, float* beta, kmb_bf16* ah, kmb_bf16* P, int ldp, float* neg_u, float* scratch, void* stream);
 /* out[M, N] (fp32) = beta * out + sum over s < nslabs of slabs[s * stride ...] + rowvec[column]: the slab reduction of a split weight
  * gradient with a row vector added to every row (the tied matrix's -u); M * N and stride multiples of 4, N a multiple of 4 */
 int kmb_op_reduce_slabs_rowvec(const float* slabs, int nslabs, int64_t stride, float* out, int M, int N, float beta, const float* rowvec,

@@ -361,6 +361,69 @@ int kmb_op_ce_dgrad_finish_smooth(const float* slab, int nslabs, int64_t stride,
   return hipfail(kmb_ce_dgrad_finish_ls_launch(slab, nslabs, (size_t)stride, alpha, beta, wsum, out, rows, d, (hipStream_t)stream),
                  "ce_dgrad_finish_smooth");
 }
+// ---- per-row loss weights and the "sum" reduction (kmb_forward_opts.row_weights / loss_reduction), piece by piece
+// the denominator word the kernels divide by: count[0] for the mean; for the sum count[1] = count[0] > 0, written here
+static int weighted_den(int32_t* count, int reduction, hipStream_t s, const int32_t** den) {
+  *den = count;
+  if (reduction == 0) return 0;
+  *den = count + 1;
+  return hipfail(kmb_count_flag_launch(count, count + 1, s), "count_flag");
+}
+int kmb_op_ce_weighted(const float* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                       const float* weights, int reduction, float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss, void* stream) {
+  if (!logits || !labels || !loss_rows || !count || !loss || rows <= 0 || V <= 0 || ldv < V) return kmb_set_error("kmb_op_ce_weighted: bad arguments");
+  if (!eps_ok(eps)) return kmb_set_error("kmb_op_ce_weighted: eps must be in [0, 1)");
+  if (reduction != 0 && reduction != 1) return kmb_set_error("kmb_op_ce_weighted: reduction must be 0 (mean) or 1 (sum)");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = hipfail(kmb_count_valid_launch(labels, rows, V, count, nullptr, s), "count_valid");
+  if (rc) return rc;
+  const int32_t* den;
+  if ((rc = weighted_den(count, reduction, s, &den))) return rc;
+  rc = hipfail(kmb_ce_launch(logits, ldv, V, labels, rows, den, grad_scale, loss_rows, dlogits, s, eps, weights), "ce_weighted");
+  if (rc) return rc;
+  return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, s, reduction == 1), "loss_finish");
+}
+int kmb_op_ce_bf16_weighted(const kmb_bf16* logits, int ldv, int V, const int64_t* labels, int rows, float grad_scale, float eps,
+                            const float* weights, int reduction, float* loss_rows, kmb_bf16* dlogits, int32_t* count, float* loss,
+                            int32_t* status, void* stream) {
+  if (!logits || !labels || !loss_rows || !count || !loss || rows <= 0 || V <= 0 || ldv < V)
+    return kmb_set_error("kmb_op_ce_bf16_weighted: bad arguments");
+  if ((ldv & 7) || ldv > 65536) return kmb_set_error("kmb_op_ce_bf16_weighted: ldv must be a multiple of 8 and at most 65536");
+  if (!eps_ok(eps)) return kmb_set_error("kmb_op_ce_bf16_weighted: eps must be in [0, 1)");
+  if (reduction != 0 && reduction != 1) return kmb_set_error("kmb_op_ce_bf16_weighted: reduction must be 0 (mean) or 1 (sum)");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = hipfail(kmb_count_valid_launch(labels, rows, V, count, status, s), "count_valid");
+  if (rc) return rc;
+  const int32_t* den;
+  if ((rc = weighted_den(count, reduction, s, &den))) return rc;
+  rc = hipfail(kmb_ce_bf16_launch(logits, ldv, V, labels, rows, den, grad_scale, loss_rows, dlogits, s, eps, weights), "ce_bf16_weighted");
+  if (rc) return rc;
+  return hipfail(kmb_loss_finish_launch(loss_rows, rows, count, loss, s, reduction == 1), "loss_finish");
+}
+int kmb_op_ce_rows_finish_weighted(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift,
+                                   const int64_t* labels, int32_t* count, float lm_factor, float eps, const float* weights, int reduction,
+                                   int rows, int d, int V, const kmb_bf16* H, int ldh, const float* wsum, float* loss_rows, float* srow,
+                                   float* alpha, float* beta, kmb_bf16* ah, kmb_bf16* P, int ldp, float* neg_u, float* scratch, void* stream) {
+  if (!row_sums || !labels || !count || !loss_rows || !srow || !alpha || rows <= 0 || nparts <= 0 || ld_sums < nparts || V <= 0 ||
+      (ah && !H) || (P && ldp < V))
+    return kmb_set_error("kmb_op_ce_rows_finish_weighted: bad arguments");
+  if (!eps_ok(eps)) return kmb_set_error("kmb_op_ce_rows_finish_weighted: eps must be in [0, 1)");
+  if (reduction != 0 && reduction != 1) return kmb_set_error("kmb_op_ce_rows_finish_weighted: reduction must be 0 (mean) or 1 (sum)");
+  hipStream_t s = (hipStream_t)stream;
+  const int32_t* den;
+  if (int rc = weighted_den(count, reduction, s, &den)) return rc;
+  if (eps > 0.f) {
+    if (!shift || !H || !wsum || !beta || (neg_u && !scratch)) return kmb_set_error("kmb_op_ce_rows_finish_weighted: eps > 0 needs shift, H, wsum and beta");
+    if (d <= 0 || (d & 7) || (ldh & 7) || ldh < d || d > 4096 || ((uintptr_t)wsum & 15))
+      return kmb_set_error("kmb_op_ce_rows_finish_weighted: d and ldh must be multiples of 8, ldh >= d, d <= 4096, wsum 16-byte aligned");
+    return hipfail(kmb_ce_rows_finish_ls_launch(row_sums, ld_sums, nparts, pick, shift, labels, den, lm_factor, eps, rows, d, V, H, ldh, wsum,
+                                                loss_rows, srow, alpha, beta, ah, P, ldp, neg_u ? scratch : nullptr, neg_u, s, weights),
+                   "ce_rows_finish_weighted");
+  }
+  if (ah && (d <= 0 || (d & 7) || (ldh & 7) || ldh < d)) return kmb_set_error("kmb_op_ce_rows_finish_weighted: d and ldh must be multiples of 8, ldh >= d");
+  return hipfail(kmb_ce_rows_finish_launch(row_sums, ld_sums, nparts, pick, labels, den, lm_factor, rows, ah ? d : 0, V, H, ldh, loss_rows,
+                                           srow, alpha, ah, P, ldp, s, weights), "ce_rows_finish_weighted");
+}
 int kmb_op_reduce_slabs_rowvec(const float* slabs, int nslabs, int64_t stride, float* out, int M, int N, float beta, const float* rowvec,
                                void* stream) {
   if (!slabs || !out || !rowvec || nslabs < 1 || stride < 0 || M <= 0 || N <= 0) return kmb_set_error("kmb_op_reduce_slabs_rowvec: bad arguments");

@@ -678,6 +678,7 @@ int kmb_classif_dropout_site(kmb_handle* h, int head, int which, uint32_t* thr16
 }
 
 int kmb_abi_sizeof_attn(void) { return (int)sizeof(KmbAttn); }
+int kmb_abi_sizeof_forward_opts(void) { return (int)sizeof(kmb_forward_opts); }
 
 int kmb_sync_params(kmb_handle* h, void* stream) {
   hipStream_t s = (hipStream_t)stream;

@@ -429,7 +429,15 @@ static int head_padded_setup(kmb_handle* h, const bf16_t* hdec, const int64_t* l
 // Cross-entropy without a pass over the logits (loss.hip "Tied-head cross-entropy WITHOUT a pass over the logits"):
 // the head GEMM stores exp(logit - label's logit) and per-row sums, the data- and weight-gradient GEMMs run on that
 // matrix with per-row factors applied outside.
-static int head_fused_ce(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, hipStream_t s) {
+// What kmb_forward_opts adds to the LM criterion: the per-row weights (null: none) and the denominator word every
+// head form divides by -- the number of valid labels ("mean"), or the 0 / 1 word of kmb_count_flag_launch ("sum").
+struct LmLoss {
+  const float* weights;
+  const int32_t* den;
+  bool sum;
+};
+
+static int head_fused_ce(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, const LmLoss& lw, hipStream_t s) {
   const int d = h->d, Md = h->Md, nparts = h->Vpad / 64;
   const TrainLayout& L = h->tl;
   KmbGemm g;
@@ -442,13 +450,13 @@ static int head_fused_ce(kmb_handle* h, const bf16_t* hdec, const int64_t* label
   const float eps = h->label_smoothing;
   if (eps > 0.f) {
     HIPCHK(kmb_ce_vocab_sum_launch(h->wb(h->shared), d, h->flb, h->V, d, L.ls_parts, L.ls_wsum, s));
-    HIPCHK(kmb_ce_rows_finish_ls_launch(L.logits_c, nparts, nparts, nullptr, L.ce_shift, labels, L.count, lmf, eps, Md, d, h->V, hdec, d, L.ls_wsum,
+    HIPCHK(kmb_ce_rows_finish_ls_launch(L.logits_c, nparts, nparts, nullptr, L.ce_shift, labels, lw.den, lmf, eps, Md, d, h->V, hdec, d, L.ls_wsum,
                                         L.loss_rows, L.ce_srow, L.ce_alpha, L.ls_beta, need_grad ? L.ce_ah : nullptr,
                                         need_grad ? L.dlogits_c : nullptr, h->Vpad, need_grad ? L.ls_parts : nullptr,
-                                        need_grad ? L.ls_negu : nullptr, s));
+                                        need_grad ? L.ls_negu : nullptr, s, lw.weights));
   } else {
-    HIPCHK(kmb_ce_rows_finish_launch(L.logits_c, nparts, nparts, nullptr, labels, L.count, lmf, Md, d, h->V, hdec, d, L.loss_rows, L.ce_srow,
-                                     L.ce_alpha, need_grad ? L.ce_ah : nullptr, need_grad ? L.dlogits_c : nullptr, h->Vpad, s));
+    HIPCHK(kmb_ce_rows_finish_launch(L.logits_c, nparts, nparts, nullptr, labels, lw.den, lmf, Md, d, h->V, hdec, d, L.loss_rows, L.ce_srow,
+                                     L.ce_alpha, need_grad ? L.ce_ah : nullptr, need_grad ? L.dlogits_c : nullptr, h->Vpad, s, lw.weights));
   }
   if (!need_grad) return 0;
   // dH_r = a_r sum_j P'_rj E_j: the GEMM on P' into fp32 slabs (the row sums in that buffer were consumed by the launch above), then the finish
@@ -467,20 +475,21 @@ static int head_fused_ce(kmb_handle* h, const bf16_t* hdec, const int64_t* label
 
 // Two-kernel bf16 head (product path without whole tiles, KMB_FUSED_CE=0): ONE GEMM writes bf16 logits into dlogits_c and the CE kernel
 // turns them into the gradient in place.  (Taken only without logits_out, so with labels.)
-static int head_bf16(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, hipStream_t s) {
+static int head_bf16(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, const LmLoss& lw, hipStream_t s) {
   const TrainLayout& L = h->tl;
   KmbGemm g = lin_fwd(hdec, h->d, h->wb(h->shared), h->flb, h->Md, h->V, h->d);
   g.out_bf16 = L.dlogits_c; g.ld_out_bf16 = h->Vpad;
   KCHK(run_gemm(g, s));
-  HIPCHK(kmb_ce_bf16_launch(L.dlogits_c, h->Vpad, h->V, labels, h->Md, L.count, lmf, L.loss_rows, need_grad ? L.dlogits_c : nullptr, s,
-                            h->label_smoothing));
+  HIPCHK(kmb_ce_bf16_launch(L.dlogits_c, h->Vpad, h->V, labels, h->Md, lw.den, lmf, L.loss_rows, need_grad ? L.dlogits_c : nullptr, s,
+                            h->label_smoothing, lw.weights));
   return 0;
 }
 
 // fp32 head (logits requested by the caller / fp32 validation mode / very wide vocabularies / KMB_FP32_HEAD=1) in row chunks of lm_chunk
 // (8192) rows that bound the fp32 buffer: one launch at the benchmark batch.  Smaller chunks (KMB_LM_CHUNK) keep the fp32 logits on-die but
 // quantise the tile count worse: 512-row chunks measured 0.8 % slower end to end.
-static int head_fp32(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, float* logits_out, hipStream_t s) {
+static int head_fp32(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, float* logits_out, const LmLoss& lw,
+                     hipStream_t s) {
   const int d = h->d, Md = h->Md;
   const TrainLayout& L = h->tl;
   const int CH = Md < h->lm_chunk ? Md : h->lm_chunk;
@@ -492,8 +501,8 @@ static int head_fp32(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, f
     g.out_f32 = lg; g.ld_out_f32 = h->Vpad;
     KCHK(run_gemm(g, s));
     if (!labels) continue;
-    HIPCHK(kmb_ce_launch(lg, h->Vpad, h->V, labels + r0, rows, L.count, lmf, L.loss_rows + r0,
-                         need_grad ? L.dlogits_c + (size_t)r0 * h->Vpad : nullptr, s, h->label_smoothing));
+    HIPCHK(kmb_ce_launch(lg, h->Vpad, h->V, labels + r0, rows, lw.den, lmf, L.loss_rows + r0,
+                         need_grad ? L.dlogits_c + (size_t)r0 * h->Vpad : nullptr, s, h->label_smoothing, lw.weights ? lw.weights + r0 : nullptr));
   }
   return 0;
 }
@@ -517,7 +526,7 @@ static int head_grads_from_dlogits(kmb_handle* h, const bf16_t* hdec, hipStream_
 }
 
 static int lm_head(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, float lmf, bool need_grad, float* loss_out, float* logits_out,
-                   hipStream_t s) {
+                   const float* row_weights, bool sum, hipStream_t s) {
   const int d = h->d, Md = h->Md;
   // KMB_FP32_HEAD=1 forces the fp32 head (chunked fp32 logits + ce_kernel_reg) in the product mode as well: the bf16 head
   // rounds logits of magnitude 10-20 to 8 significant bits before the softmax (the reference's AMP path holds fp16
@@ -531,12 +540,18 @@ static int lm_head(kmb_handle* h, const bf16_t* hdec, const int64_t* labels, flo
   const bool fused_ce = bf16_head && labels && fused_ce_env && (Md % 256) == 0 && (h->Vpad % 256) == 0 && (d % 64) == 0 &&
                         d >= 128 && (long)(Md / 256) * (h->Vpad / 256) >= 128 && (size_t)Md * nparts <= h->tl.logits_c_floats;
   if (labels) h->last_head_form = fused_ce ? 2 : bf16_head ? 1 : 0;
-  if (fused_ce) KCHK(head_fused_ce(h, hdec, labels, lmf, need_grad, s));
-  else if (bf16_head) KCHK(head_bf16(h, hdec, labels, lmf, need_grad, s));
-  else KCHK(head_fp32(h, hdec, labels, lmf, need_grad, logits_out, s));
+  // "sum": the third word of the count block holds the 0 / 1 denominator; "mean" without weights: the arguments there always were
+  LmLoss lw{row_weights, h->tl.count, sum};
+  if (labels && sum) {
+    HIPCHK(kmb_count_flag_launch(h->tl.count, h->tl.count + 2, s));
+    lw.den = h->tl.count + 2;
+  }
+  if (fused_ce) KCHK(head_fused_ce(h, hdec, labels, lmf, need_grad, lw, s));
+  else if (bf16_head) KCHK(head_bf16(h, hdec, labels, lmf, need_grad, lw, s));
+  else KCHK(head_fp32(h, hdec, labels, lmf, need_grad, logits_out, lw, s));
   if (labels && need_grad && !fused_ce) KCHK(head_grads_from_dlogits(h, hdec, s));
   if (labels) {
-    HIPCHK(kmb_loss_finish_launch(h->tl.loss_rows, Md, h->tl.count, h->tl.loss_dev, s));
+    HIPCHK(kmb_loss_finish_launch(h->tl.loss_rows, Md, h->tl.count, h->tl.loss_dev, s, sum));
     if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, h->tl.loss_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
   }
   return 0;
@@ -571,6 +586,11 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
     return fail("kmb_forward: sequence longer than max_position_embeddings");
   if (need_grad && !bt.labels && !extra) return fail("kmb_forward: need_grad requires labels");
   if (need_grad && (!h->G)) return fail("kmb_forward: gradient arena is not bound");
+  const float* row_weights = opts ? opts->row_weights : nullptr;
+  const int loss_reduction = opts ? opts->loss_reduction : 0;
+  if (row_weights && !bt.labels) return fail("kmb_forward: row_weights weigh the rows' cross-entropy and need labels");
+  if (loss_reduction != 0 && loss_reduction != 1) return fail("kmb_forward: loss_reduction must be 0 (mean) or 1 (sum), got %d", loss_reduction);
+  if (row_weights && opts->skip_head) return fail("kmb_forward: row_weights with skip_head: there is no loss to weigh");
   {
     TrainLayout tl;
     const size_t need = layout_train(h, h->ws, h->ws_bytes, bt.B, bt.S, bt.T, bt.n_features, &tl);
@@ -640,7 +660,8 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
 
   // ---- tied LM head + CE (src/model/model.py:397-403)
   if (bt.labels) HIPCHK(kmb_count_valid_launch(bt.labels, Md, h->V, h->tl.count, h->tl.status, s));
-  if (bt.labels || logits_out) KCHK(lm_head(h, hdec, bt.labels, extra ? extra->lm_factor : 1.f, need_grad != 0, loss_out, logits_out, s));
+  if (bt.labels || logits_out) KCHK(lm_head(h, hdec, bt.labels, extra ? extra->lm_factor : 1.f, need_grad != 0, loss_out, logits_out,
+                                           row_weights, loss_reduction == 1, s));
   if (extra && need_grad && !bt.labels) {
     // no LM term (src/model/model.py:293-302 allows labels=None beside head labels): the decoder-state gradient and the
     // tied matrix's gradient start from zero; the heads add into the former, backward's embedding scatter-adds into the latter

@@ -114,6 +114,11 @@ hipError_t kmb_pos_bwd_launch(const bf16_t* dz, int B, int S, int D, float* dP, 
 // ----------------------------------------------------------------- loss.hip
 // count[0] = number of labels in [0, V); labels that are neither -100 nor in range set bit 1 of status[0] (status may be null)
 hipError_t kmb_count_valid_launch(const int64_t* labels, int n, int V, int32_t* count, int32_t* status, hipStream_t stream);
+// Per-row loss weights and the "sum" reduction.  Every cross-entropy launcher below takes `weights` ([rows] fp32 on the
+// device, or null): loss_r and the row's gradient factor are multiplied by weights[r], read only in rows with a valid label; null launches the
+// kernels there always were.  The denominator D is whatever word `count` points to: kmb_count_valid_launch's for "mean", for "sum" the word
+// of kmb_count_flag_launch: flag[0] = count[0] > 0 ? 1 : 0.
+hipError_t kmb_count_flag_launch(const int32_t* count, int32_t* flag, hipStream_t stream);
 // tied-head cross-entropy without a pass over the logits (loss.hip, KmbGemm act 5)
 hipError_t kmb_ce_label_logit_launch(const bf16_t* H, int ldh, const bf16_t* E, int lde, const float* bias, const int64_t* labels,
                                      int rows, int d, int V, float* shift, hipStream_t stream);
@@ -121,7 +126,8 @@ hipError_t kmb_ce_pad_bias_launch(const float* bias, int V, int Vpad, float* out
 // S_r, loss_r, a_r = lm_factor / (count S_r), ah = a . H (bf16, may be null), and P[r][label_r] := exp(pick_r) - S_r (P may be null)
 hipError_t kmb_ce_rows_finish_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const int64_t* labels,
                                      const int32_t* count, float lm_factor, int rows, int d, int V, const bf16_t* H, int ldh,
-                                     float* loss_rows, float* srow, float* alpha, bf16_t* ah, bf16_t* P, int ldp, hipStream_t stream);
+                                     float* loss_rows, float* srow, float* alpha, bf16_t* ah, bf16_t* P, int ldp, hipStream_t stream,
+                                     const float* weights = nullptr);
 // scoring (kmb_score): logp[r] = label_logit[r] - lse(stats row r), 0 in rows whose label is -100 / out of range; stats as kmb_gemm_score_launch leaves them
 hipError_t kmb_score_rows_finish_launch(const float* stats, int nblk, const float* label_logit, const int64_t* labels, int rows, int V,
                                         float* logp, hipStream_t stream);
@@ -137,10 +143,11 @@ hipError_t kmb_ce_dgrad_finish_launch(const float* slab, int nslabs, size_t stri
 //          dlogits = (softmax - (1 - eps) onehot - eps / V) * grad_scale / count; eps == 0 launches the kernels it always did
 hipError_t kmb_ce_launch(const float* logits, int ldv, int V, const int64_t* labels, int rows,
                          const int32_t* count, float grad_scale, float* loss_rows, bf16_t* dlogits,
-                         hipStream_t stream, float eps = 0.f);
+                         hipStream_t stream, float eps = 0.f, const float* weights = nullptr);
 // the same on bf16 logits (ldv <= 65536), dlogits may alias logits (in place)
 hipError_t kmb_ce_bf16_launch(const bf16_t* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count,
-                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps = 0.f);
+                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps = 0.f,
+                              const float* weights = nullptr);
 // ---- label smoothing in the fused tied head (loss.hip "Label smoothing as rank-one terms")
 // wsum[0, d) = sum_{j < V} E[j] (bf16 rows, fp32 sums), wsum[d] = sum_{j < V} bias[j]: kmb_ce_vocab_sum_slots(V, d) workgroups leave one partial row
 // of kmb_ce_vocab_sum_ld(d) floats each in `partials`, one pass sums them in slot order.  wsum holds kmb_ce_vocab_sum_ld(d) floats.
@@ -155,13 +162,14 @@ int kmb_ce_rows_slots(int rows);
 hipError_t kmb_ce_rows_finish_ls_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift,
                                         const int64_t* labels, const int32_t* count, float lm_factor, float eps, int rows, int d, int V,
                                         const bf16_t* H, int ldh, const float* wsum, float* loss_rows, float* srow, float* alpha, float* beta,
-                                        bf16_t* ah, bf16_t* P, int ldp, float* u_partials, float* neg_u, hipStream_t stream);
+                                        bf16_t* ah, bf16_t* P, int ldp, float* u_partials, float* neg_u, hipStream_t stream,
+                                        const float* weights = nullptr);
 // out[r] = bf16(alpha[r] * sum_s slab[s][r] - beta[r] * wsum)
 hipError_t kmb_ce_dgrad_finish_ls_launch(const float* slab, int nslabs, size_t stride, const float* alpha, const float* beta,
                                          const float* wsum, bf16_t* out, int rows, int d, hipStream_t stream);
-// loss[0] = sum(loss_rows) / count
+// loss[0] = sum(loss_rows) / count (NaN when count is 0); sum: loss[0] = sum(loss_rows), count is not read
 hipError_t kmb_loss_finish_launch(const float* loss_rows, int rows, const int32_t* count, float* loss,
-                                  hipStream_t stream);
+                                  hipStream_t stream, bool sum = false);
 
 // ------------------------------------------------------------ beam_step.hip
 // generation: per row log_softmax over V then top-k of (logp + add[row]); writes k (value, index) pairs

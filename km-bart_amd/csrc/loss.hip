@@ -50,20 +50,32 @@ __global__ __launch_bounds__(1024) void count_valid_kernel(const int64_t* __rest
   }
 }
 
+// The denominator word of loss_reduction "sum": 1 with at least one valid label, 0 without (the kernels' n > 0 guards stay as they are)
+__global__ void count_flag_kernel(const int32_t* __restrict__ count, int32_t* __restrict__ flag) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) flag[0] = count[0] > 0 ? 1 : 0;
+}
+
 // LS (label smoothing, eps > 0): the target is (1 - eps) onehot + eps / V over the V real columns, so
 //   loss_r = lse - (1 - eps) v_label - eps mean_{j < V} v_j,   gradient row = (p - (1 - eps) onehot - eps / V) * scale / n, rounded once;
 // pad columns and ignored rows stay exactly zero.  LS = false is the code it was (eps is not read).
-template <bool LS>
+// W (per-row loss weights): loss_r and the gradient row are multiplied by weights[r] -- ONE multiply of the row's
+// loss and of the row's factor gs, so that a weight of 1.0f changes no bit; the weight is read only in rows with a valid label (an ignored
+// row's weight may hold anything, NaN included) and is block-uniform like the label.  W = false is the code it was (weights is not read).
+// `count` is the denominator word: the number of valid labels ("mean"), or kmb_count_flag_launch's 0 / 1 word ("sum").
+template <bool LS, bool W>
 __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logits, int ldv, int V,
                                                  const int64_t* __restrict__ labels, const int32_t* __restrict__ count,
                                                  float grad_scale, float* __restrict__ loss_rows,
-                                                 bf16_t* __restrict__ dlogits, float eps) {
+                                                 bf16_t* __restrict__ dlogits, float eps,
+                                                 const float* __restrict__ weights) {
   __shared__ float sh[8];
   __shared__ float shz[LS ? 4 : 1];
   const int r = blockIdx.x, tid = threadIdx.x;
   const float* row = logits + (size_t)r * ldv;
   const int64_t label = labels[r];
   const bool valid = label >= 0 && label < V;   // ignored: -100; out of range: flagged by count_valid
+  float w = 1.f;
+  if (W && valid) w = weights[r];   // issued in front of the row's loads, consumed behind them
   float m = 0.f, s = 1.f;
   if (valid) row_lse(row, V, sh, m, s);  // block-uniform branch
   const float lse = m + __logf(s);
@@ -77,15 +89,22 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
     zmean = ((shz[0] + shz[1]) + (shz[2] + shz[3])) / (float)V;
   }
   if (LS) {
-    if (tid == 0) loss_rows[r] = valid ? (lse - (1.f - eps) * row[label] - eps * zmean) : 0.f;
+    if (tid == 0) {
+      const float l = valid ? (lse - (1.f - eps) * row[label] - eps * zmean) : 0.f;
+      loss_rows[r] = (W && valid) ? w * l : l;
+    }
   } else {
-    if (tid == 0) loss_rows[r] = valid ? (lse - row[label]) : 0.f;
+    if (tid == 0) {
+      const float l = valid ? (lse - row[label]) : 0.f;
+      loss_rows[r] = (W && valid) ? w * l : l;
+    }
   }
   if (dlogits == nullptr) return;
   const float uni = LS ? eps / (float)V : 0.f, hot = LS ? 1.f - eps : 1.f;
   bf16_t* drow = dlogits + (size_t)r * ldv;
   const int n = count[0];
-  const float gs = (valid && n > 0) ? grad_scale / (float)n : 0.f;
+  float gs = (valid && n > 0) ? grad_scale / (float)n : 0.f;
+  if (W && valid) gs *= w;
   for (int i = tid * 8; i < ldv; i += 2048) {
     float o[8];
     if (valid) {
@@ -110,11 +129,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
 
 // Register-resident form for rows of up to NV * 4096 columns: 1024 threads hold the whole fp32 row (NV float4 each),
 // so the logits are read from memory once (max, sum-exp and the gradient all come from registers).
-template <int NV, bool LS>
+template <int NV, bool LS, bool W>
 __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ logits, int ldv, int V,
                                                       const int64_t* __restrict__ labels,
                                                       const int32_t* __restrict__ count, float grad_scale,
-                                                      float* __restrict__ loss_rows, bf16_t* __restrict__ dlogits, float eps) {
+                                                      float* __restrict__ loss_rows, bf16_t* __restrict__ dlogits, float eps,
+                                                      const float* __restrict__ weights) {
   __shared__ float sh[LS ? 48 : 32];
   const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float* row = logits + (size_t)r * ldv;
@@ -133,6 +153,8 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ 
     }
     return;
   }
+  float w = 1.f;
+  if (W) w = weights[r];   // valid rows only; block-uniform, issued with the label in front of the row's loads and consumed behind them
   f32x4 x[NV];
   float m = -INFINITY;
 #pragma unroll
@@ -185,13 +207,20 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ 
 #pragma unroll
     for (int w = 0; w < 16; ++w) z += sh[32 + w];
     uni = eps / (float)V; hot = 1.f - eps;
-    if (tid == 0) loss_rows[r] = lse - hot * row[label] - eps * (z / (float)V);
+    if (tid == 0) {
+      const float l = lse - hot * row[label] - eps * (z / (float)V);
+      loss_rows[r] = W ? w * l : l;
+    }
   } else {
-    if (tid == 0) loss_rows[r] = lse - row[label];
+    if (tid == 0) {
+      const float l = lse - row[label];
+      loss_rows[r] = W ? w * l : l;
+    }
   }
   if (dlogits == nullptr) return;
   const int n = count[0];
-  const float gs = n > 0 ? grad_scale / (float)n : 0.f;
+  float gs = n > 0 ? grad_scale / (float)n : 0.f;
+  if (W) gs *= w;
   bf16_t* drow = dlogits + (size_t)r * ldv;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -211,6 +240,8 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg(const float* __restrict__ 
   }
 }
 
+// SUM (loss_reduction "sum"): the rows' sum itself -- exactly 0 without a valid label, every row being 0 then; count is not read
+template <bool SUM>
 __global__ __launch_bounds__(1024) void loss_finish_kernel(const float* __restrict__ loss_rows, int rows,
                                                            const int32_t* __restrict__ count, float* __restrict__ loss) {
   __shared__ float sh[16];
@@ -227,12 +258,16 @@ __global__ __launch_bounds__(1024) void loss_finish_kernel(const float* __restri
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const int n = count[0];
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) t += sh[k];
-    // torch CrossEntropyLoss(mean) over zero valid targets is NaN
-    loss[0] = n > 0 ? t / (float)n : __uint_as_float(0x7fc00000u);
+    if (SUM) {
+      loss[0] = t;
+    } else {
+      const int n = count[0];
+      // torch CrossEntropyLoss(mean) over zero valid targets is NaN
+      loss[0] = n > 0 ? t / (float)n : __uint_as_float(0x7fc00000u);
+    }
   }
 }
 
@@ -242,11 +277,12 @@ __global__ __launch_bounds__(1024) void loss_finish_kernel(const float* __restri
 // is written back IN PLACE over the logits (dlogits == logits is allowed: every element is read before the first
 // store of its thread, and a thread only rewrites what it read).  Halves the head GEMM's store and the CE's read
 // against fp32 logits: 3.3 GB -> 1.65 GB each per step at the benchmark batch.
-template <int NV8, bool LS>
+template <int NV8, bool LS, bool W>
 __global__ __launch_bounds__(1024) void ce_kernel_reg_bf16(const bf16_t* logits, int ldv, int V,
                                                            const int64_t* __restrict__ labels,
                                                            const int32_t* __restrict__ count, float grad_scale,
-                                                           float* __restrict__ loss_rows, bf16_t* dlogits, float eps) {
+                                                           float* __restrict__ loss_rows, bf16_t* dlogits, float eps,
+                                                           const float* __restrict__ weights) {
   __shared__ float sh[LS ? 56 : 33];
   const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const bf16_t* row = logits + (size_t)r * ldv;
@@ -264,6 +300,8 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg_bf16(const bf16_t* logits,
     }
     return;
   }
+  float w = 1.f;
+  if (W) w = weights[r];   // valid rows only; block-uniform, issued with the label in front of the row's loads and consumed behind them
   float x[NV8][8];
   float m = -INFINITY;
 #pragma unroll
@@ -321,13 +359,20 @@ __global__ __launch_bounds__(1024) void ce_kernel_reg_bf16(const bf16_t* logits,
 #pragma unroll
     for (int w = 0; w < 16; ++w) z += sh[40 + w];
     uni = eps / (float)V; hot = 1.f - eps;
-    if (tid == 0) loss_rows[r] = lse - hot * sh[32] - eps * (z / (float)V);
+    if (tid == 0) {
+      const float l = lse - hot * sh[32] - eps * (z / (float)V);
+      loss_rows[r] = W ? w * l : l;
+    }
   } else {
-    if (tid == 0) loss_rows[r] = lse - sh[32];
+    if (tid == 0) {
+      const float l = lse - sh[32];
+      loss_rows[r] = W ? w * l : l;
+    }
   }
   if (dlogits == nullptr) return;
   const int n = count[0];
-  const float gs = n > 0 ? grad_scale / (float)n : 0.f;
+  float gs = n > 0 ? grad_scale / (float)n : 0.f;
+  if (W) gs *= w;
   bf16_t* drow = dlogits + (size_t)r * ldv;
 #pragma unroll
   for (int j = 0; j < NV8; ++j) {
@@ -402,24 +447,31 @@ __global__ __launch_bounds__(256) void ce_pad_bias_kernel(const float* __restric
 // P[r, label_r] - S_r (so that a_r P'[r, :] IS the softmax gradient row and both gradient GEMMs need no correction term;
 // the entry is exp(pick_r) ~ 1 against S_r >= 1: one bf16 rounding of the difference, the same relative error the bf16
 // gradient row of the two-kernel path carries at the label); one wave per row
+// W: weights[r] (read in valid rows only) multiplies loss_r and a_r once; S_r and the label's entry of P' are weight-free
+template <bool W>
 __global__ __launch_bounds__(256) void ce_rows_finish_kernel(const float* __restrict__ row_sums, int ld_sums, int nparts,
                                                              const float* __restrict__ pick, const int64_t* __restrict__ labels,
                                                              const int32_t* __restrict__ count, float lm_factor, int rows, int d, int V,
                                                              const bf16_t* __restrict__ H, int ldh, float* __restrict__ loss_rows,
                                                              float* __restrict__ srow, float* __restrict__ alpha,
-                                                             bf16_t* __restrict__ ah, bf16_t* __restrict__ P, int ldp) {
+                                                             bf16_t* __restrict__ ah, bf16_t* __restrict__ P, int ldp,
+                                                             const float* __restrict__ weights) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (r >= rows) return;
   const long long lab = labels[r];
   const bool valid = lab != -100 && lab >= 0 && lab < V;
+  float w = 1.f;
+  if (W && valid) w = weights[r];
   float s = 0.f;
   for (int i = lane; i < nparts; i += 64) s += row_sums[(size_t)r * ld_sums + i];
   s = wave_sum(s);
   const int n = count[0];
-  const float a = (valid && n > 0 && s > 0.f) ? lm_factor / ((float)n * s) : 0.f;
+  float a = (valid && n > 0 && s > 0.f) ? lm_factor / ((float)n * s) : 0.f;
+  if (W && valid) a *= w;
   if (lane == 0) {
     const float pk = pick != nullptr ? pick[r] : 0.f;   // v_r[label] - c_r: 0 up to summation order when c_r is the label's logit
-    loss_rows[r] = valid ? __logf(s) - pk : 0.f;
+    const float l = valid ? __logf(s) - pk : 0.f;
+    loss_rows[r] = (W && valid) ? w * l : l;
     srow[r] = valid ? s : 0.f;
     alpha[r] = a;
     if (valid && P != nullptr) P[(size_t)r * ldp + lab] = f2bf(__expf(pk) - s);
@@ -529,6 +581,8 @@ __global__ __launch_bounds__(256) void ce_vocab_sum_kernel(const bf16_t* __restr
 
 // ce_rows_finish_kernel with smoothing.  One wave per row, four rows per trip, a fixed grid (kmb_ce_rows_slots) walking the rows with its
 // stride; each wave keeps sum -beta_r h_r of its rows in its own LDS row, the four meet at the end: u_part[workgroup][d].
+// W: as in ce_rows_finish_kernel, and beta_r carries the weight too (so u = sum_r beta_r h_r does)
+template <bool W>
 __global__ __launch_bounds__(256) void ce_rows_finish_ls_kernel(const float* __restrict__ row_sums, int ld_sums, int nparts,
                                                                 const float* __restrict__ pick, const float* __restrict__ shift,
                                                                 const int64_t* __restrict__ labels, const int32_t* __restrict__ count,
@@ -536,7 +590,8 @@ __global__ __launch_bounds__(256) void ce_rows_finish_ls_kernel(const float* __r
                                                                 const bf16_t* __restrict__ H, int ldh, const float* __restrict__ wsum,
                                                                 float* __restrict__ loss_rows, float* __restrict__ srow,
                                                                 float* __restrict__ alpha, float* __restrict__ beta, bf16_t* __restrict__ ah,
-                                                                bf16_t* __restrict__ P, int ldp, float* __restrict__ u_part) {
+                                                                bf16_t* __restrict__ P, int ldp, float* __restrict__ u_part,
+                                                                const float* __restrict__ weights) {
   extern __shared__ float ls_acc[];   // [4][d]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float* acc = ls_acc + (size_t)wave * d;
@@ -548,11 +603,14 @@ __global__ __launch_bounds__(256) void ce_rows_finish_ls_kernel(const float* __r
   for (int r = blockIdx.x * 4 + wave; r < rows; r += gridDim.x * 4) {
     const long long lab = labels[r];
     const bool valid = lab != -100 && lab >= 0 && lab < V;
+    float w = 1.f;
+    if (W && valid) w = weights[r];
     float s = 0.f;
     for (int i = lane; i < nparts; i += 64) s += row_sums[(size_t)r * ld_sums + i];
     s = wave_sum(s);
-    const float a = (valid && n > 0 && s > 0.f) ? lm_factor / ((float)n * s) : 0.f;
-    const float b = (valid && n > 0) ? eps * lm_factor / ((float)n * (float)V) : 0.f;
+    float a = (valid && n > 0 && s > 0.f) ? lm_factor / ((float)n * s) : 0.f;
+    float b = (valid && n > 0) ? eps * lm_factor / ((float)n * (float)V) : 0.f;
+    if (W && valid) { a *= w; b *= w; }
     float dot = 0.f;
     for (int i = lane * 8; i < d; i += 512) {
       float x[8];
@@ -575,7 +633,8 @@ __global__ __launch_bounds__(256) void ce_rows_finish_ls_kernel(const float* __r
     if (lane == 0) {
       const float pk = pick != nullptr ? pick[r] : 0.f;
       const float zbar = (dot + bsum) * invV;
-      loss_rows[r] = valid ? __logf(s) - pk + eps * (shift[r] - zbar) : 0.f;
+      const float l = valid ? __logf(s) - pk + eps * (shift[r] - zbar) : 0.f;
+      loss_rows[r] = (W && valid) ? w * l : l;
       srow[r] = valid ? s : 0.f;
       alpha[r] = a;
       beta[r] = b;
@@ -683,11 +742,16 @@ hipError_t kmb_ce_pad_bias_launch(const float* bias, int V, int Vpad, float* out
 }
 hipError_t kmb_ce_rows_finish_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const int64_t* labels,
                                      const int32_t* count, float lm_factor, int rows, int d, int V, const bf16_t* H, int ldh,
-                                     float* loss_rows, float* srow, float* alpha, bf16_t* ah, bf16_t* P, int ldp, hipStream_t stream) {
+                                     float* loss_rows, float* srow, float* alpha, bf16_t* ah, bf16_t* P, int ldp, hipStream_t stream,
+                                     const float* weights) {
   if (rows <= 0) return hipSuccess;
   if ((d & 7) || (ldh & 7)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ce_rows_finish_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, row_sums, ld_sums, nparts, pick, labels, count,
-                     lm_factor, rows, d, V, H, ldh, loss_rows, srow, alpha, ah, P, ldp);
+  if (weights != nullptr)
+    hipLaunchKernelGGL(ce_rows_finish_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, stream, row_sums, ld_sums, nparts, pick, labels, count,
+                       lm_factor, rows, d, V, H, ldh, loss_rows, srow, alpha, ah, P, ldp, weights);
+  else
+    hipLaunchKernelGGL(ce_rows_finish_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, stream, row_sums, ld_sums, nparts, pick, labels, count,
+                       lm_factor, rows, d, V, H, ldh, loss_rows, srow, alpha, ah, P, ldp, nullptr);
   return hipGetLastError();
 }
 hipError_t kmb_ce_dgrad_finish_launch(const float* slab, int nslabs, size_t stride, const float* alpha, bf16_t* out, int rows, int d,
@@ -725,12 +789,17 @@ int kmb_ce_rows_slots(int rows) {
 hipError_t kmb_ce_rows_finish_ls_launch(const float* row_sums, int ld_sums, int nparts, const float* pick, const float* shift,
                                         const int64_t* labels, const int32_t* count, float lm_factor, float eps, int rows, int d, int V,
                                         const bf16_t* H, int ldh, const float* wsum, float* loss_rows, float* srow, float* alpha, float* beta,
-                                        bf16_t* ah, bf16_t* P, int ldp, float* u_partials, float* neg_u, hipStream_t stream) {
+                                        bf16_t* ah, bf16_t* P, int ldp, float* u_partials, float* neg_u, hipStream_t stream,
+                                        const float* weights) {
   if (rows <= 0) return hipSuccess;
   if (d <= 0 || (d & 7) || (ldh & 7) || d > 4096 || ((uintptr_t)wsum & 15) || (u_partials == nullptr) != (neg_u == nullptr)) return hipErrorInvalidValue;
   const int slots = kmb_ce_rows_slots(rows);
-  hipLaunchKernelGGL(ce_rows_finish_ls_kernel, dim3(slots), dim3(256), (size_t)4 * d * sizeof(float), stream, row_sums, ld_sums, nparts, pick, shift,
-                     labels, count, lm_factor, eps, rows, d, V, H, ldh, wsum, loss_rows, srow, alpha, beta, ah, P, ldp, u_partials);
+  if (weights != nullptr)
+    hipLaunchKernelGGL(ce_rows_finish_ls_kernel<true>, dim3(slots), dim3(256), (size_t)4 * d * sizeof(float), stream, row_sums, ld_sums, nparts, pick,
+                       shift, labels, count, lm_factor, eps, rows, d, V, H, ldh, wsum, loss_rows, srow, alpha, beta, ah, P, ldp, u_partials, weights);
+  else
+    hipLaunchKernelGGL(ce_rows_finish_ls_kernel<false>, dim3(slots), dim3(256), (size_t)4 * d * sizeof(float), stream, row_sums, ld_sums, nparts, pick,
+                       shift, labels, count, lm_factor, eps, rows, d, V, H, ldh, wsum, loss_rows, srow, alpha, beta, ah, P, ldp, u_partials, nullptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || neg_u == nullptr) return e;
   return kmb_reduce_parts_launch(u_partials, slots, d, neg_u, d, stream);
@@ -764,40 +833,64 @@ hipError_t kmb_count_valid_launch(const int64_t* labels, int n, int V, int32_t* 
   return hipGetLastError();
 }
 
+hipError_t kmb_count_flag_launch(const int32_t* count, int32_t* flag, hipStream_t stream) {
+  hipLaunchKernelGGL(count_flag_kernel, dim3(1), dim3(64), 0, stream, count, flag);
+  return hipGetLastError();
+}
+
+namespace {
+// one launch line per row kernel: the weighted instance with weights, the instance there always was without
+template <bool LS, bool W>
+void ce_f32_pick(const float* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count, float grad_scale,
+                 float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps, const float* weights) {
+  if (ldv <= 13 * 4096)
+    hipLaunchKernelGGL((ce_kernel_reg<13, LS, W>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps, weights);
+  else
+    hipLaunchKernelGGL((ce_kernel<LS, W>), dim3(rows), dim3(256), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps, weights);
+}
+template <bool LS, bool W>
+void ce_bf16_pick(const bf16_t* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count, float grad_scale,
+                  float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps, const float* weights) {
+  if (ldv <= 7 * 8192)
+    hipLaunchKernelGGL((ce_kernel_reg_bf16<7, LS, W>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps, weights);
+  else
+    hipLaunchKernelGGL((ce_kernel_reg_bf16<8, LS, W>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps, weights);
+}
+}  // namespace
+
 hipError_t kmb_ce_launch(const float* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count,
-                         float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps) {
+                         float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps, const float* weights) {
   if (rows <= 0) return hipSuccess;
   if ((ldv & 7) || ((uintptr_t)logits & 15) || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
-  if (eps > 0.f) {
-    if (ldv <= 13 * 4096)
-      hipLaunchKernelGGL((ce_kernel_reg<13, true>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
-    else
-      hipLaunchKernelGGL(ce_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
-  } else if (ldv <= 13 * 4096)
-    hipLaunchKernelGGL((ce_kernel_reg<13, false>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
-  else
-    hipLaunchKernelGGL(ce_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
+  if (weights != nullptr) {
+    if (eps > 0.f) ce_f32_pick<true, true>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, eps, weights);
+    else ce_f32_pick<false, true>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, 0.f, weights);
+  } else if (eps > 0.f) {
+    ce_f32_pick<true, false>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, eps, nullptr);
+  } else {
+    ce_f32_pick<false, false>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, 0.f, nullptr);
+  }
   return hipGetLastError();
 }
 
 hipError_t kmb_ce_bf16_launch(const bf16_t* logits, int ldv, int V, const int64_t* labels, int rows, const int32_t* count,
-                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps) {
+                              float grad_scale, float* loss_rows, bf16_t* dlogits, hipStream_t stream, float eps, const float* weights) {
   if (rows <= 0) return hipSuccess;
   if ((ldv & 7) || ((uintptr_t)logits & 15) || ldv > 8 * 8192 || !(eps >= 0.f && eps < 1.f)) return hipErrorInvalidValue;
-  if (eps > 0.f) {
-    if (ldv <= 7 * 8192)
-      hipLaunchKernelGGL((ce_kernel_reg_bf16<7, true>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
-    else
-      hipLaunchKernelGGL((ce_kernel_reg_bf16<8, true>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, eps);
-  } else if (ldv <= 7 * 8192)
-    hipLaunchKernelGGL((ce_kernel_reg_bf16<7, false>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
-  else
-    hipLaunchKernelGGL((ce_kernel_reg_bf16<8, false>), dim3(rows), dim3(1024), 0, stream, logits, ldv, V, labels, count, grad_scale, loss_rows, dlogits, 0.f);
+  if (weights != nullptr) {
+    if (eps > 0.f) ce_bf16_pick<true, true>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, eps, weights);
+    else ce_bf16_pick<false, true>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, 0.f, weights);
+  } else if (eps > 0.f) {
+    ce_bf16_pick<true, false>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, eps, nullptr);
+  } else {
+    ce_bf16_pick<false, false>(logits, ldv, V, labels, rows, count, grad_scale, loss_rows, dlogits, stream, 0.f, nullptr);
+  }
   return hipGetLastError();
 }
 
 hipError_t kmb_loss_finish_launch(const float* loss_rows, int rows, const int32_t* count, float* loss,
-                                  hipStream_t stream) {
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(1024), 0, stream, loss_rows, rows, count, loss);
+                                  hipStream_t stream, bool sum) {
+  if (sum) hipLaunchKernelGGL(loss_finish_kernel<true>, dim3(1), dim3(1024), 0, stream, loss_rows, rows, count, loss);
+  else hipLaunchKernelGGL(loss_finish_kernel<false>, dim3(1), dim3(1024), 0, stream, loss_rows, rows, count, loss);
   return hipGetLastError();
 }

@@ -38,7 +38,8 @@ class KmbPretrain(C.Structure):
 
 
 class KmbForwardOpts(C.Structure):
-    _fields_ = [("encoder_states", c_p), ("decoder_states_out", c_p), ("skip_head", i32)]
+    _fields_ = [("encoder_states", c_p), ("decoder_states_out", c_p), ("skip_head", i32),
+                ("row_weights", c_p), ("loss_reduction", i32)]
 
 
 class KmbGemm(C.Structure):
@@ -120,6 +121,7 @@ PROTOTYPES = {
     "kmb_set_label_smoothing": (C.c_int, [c_p, f32]),
     "kmb_last_head_form": (C.c_int, [c_p]),
     "kmb_abi_sizeof_attn":(C.c_int, []),
+    "kmb_abi_sizeof_forward_opts": (C.c_int, []),
     "kmb_bucket_count": (C.c_int, [c_p]),
     "kmb_bucket_range": (C.c_int, [c_p, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
     "kmb_stream_wait_bucket": (C.c_int, [c_p, C.c_int, c_p]),
@@ -263,6 +265,10 @@ PROTOTYPES = {
     "kmb_op_ce_rows_finish_smooth": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p, f32, f32, C.c_int, C.c_int, C.c_int, c_p, C.c_int,
                                                c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.c_int, c_p, c_p, c_p]),
     "kmb_op_ce_dgrad_finish_smooth": (C.c_int, [c_p, C.c_int, i64, c_p, c_p, c_p, c_p, C.c_int, C.c_int, c_p]),
+    "kmb_op_ce_weighted": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, f32, f32, c_p, C.c_int, c_p, c_p, c_p, c_p, c_p]),
+    "kmb_op_ce_bf16_weighted": (C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, f32, f32, c_p, C.c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "kmb_op_ce_rows_finish_weighted": (C.c_int, [c_p, C.c_int, C.c_int, c_p, c_p, c_p, c_p, f32, f32, c_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 c_p, C.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.c_int, c_p, c_p, c_p]),
     "kmb_op_reduce_slabs_rowvec": (C.c_int, [c_p, C.c_int, i64, c_p, C.c_int, C.c_int, f32, c_p, c_p]),
     "kmb_op_kl_div":(C.c_int, [c_p, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, c_p, c_p, C.c_int, c_p]),
     "kmb_op_gather_rows_bf16": (C.c_int, [c_p, C.c_int, c_p, c_p, C.c_int, C.c_int, C.c_int, c_p]),

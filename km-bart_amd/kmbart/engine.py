@@ -14,6 +14,9 @@ _CFG_INT_FIELDS = ("vocab_size", "d_model", "encoder_layers", "decoder_layers", 
                    "img_feat_id", "cls_token_id")
 
 
+LOSS_REDUCTIONS = {"mean": 0, "sum": 1}   # kmb_forward_opts.loss_reduction
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -266,13 +269,35 @@ class Engine:
         keep = [input_ids, packed, offsets, attention_mask, decoder_input_ids, decoder_attention_mask, labels]
         return b, keep, (B, S, T, ntot)
 
+    def _loss_opts(self, opts, keep, loss_weights, loss_reduction, labels, B, T):
+        """Fills kmb_forward_opts.row_weights / loss_reduction: [B] weights are broadcast over T, the result is a contiguous float32
+        [B, T] on the device that `keep` holds until the forward is enqueued.  Device ops only."""
+        if loss_reduction not in LOSS_REDUCTIONS:
+            raise ValueError("loss_reduction must be 'mean' or 'sum', got %r" % (loss_reduction,))
+        opts.loss_reduction = LOSS_REDUCTIONS[loss_reduction]
+        if loss_weights is None:
+            return
+        if labels is None:
+            raise ValueError("loss_weights weigh the rows' cross-entropy: they need labels")
+        w = loss_weights.detach().to(device=self.device, dtype=torch.float32)
+        if tuple(w.shape) == (B,):
+            w = w.unsqueeze(1).expand(B, T)
+        elif tuple(w.shape) != (B, T):
+            raise ValueError("loss_weights must be [batch] or [batch, tgt_len] = %s, got %s" % ((B, T), tuple(loss_weights.shape)))
+        w = w.contiguous()
+        opts.row_weights = ptr(w)
+        keep.append(w)
+
     # ---- training step ----------------------------------------------------------------------
     def forward(self, input_ids, image_features, attention_mask=None, decoder_input_ids=None,
                 decoder_attention_mask=None, labels=None, train=False, need_grad=False, want_logits=False,
-                want_encoder=True, encoder_states=None, want_decoder_states=False, skip_head=False):
+                want_encoder=True, encoder_states=None, want_decoder_states=False, skip_head=False,
+                loss_weights=None, loss_reduction="mean"):
         """Returns (loss [1] or None, logits [B,T,V] fp32 or None, encoder_out [B,S,D] or None); with
         want_decoder_states a 4th element, the last decoder hidden states [B,T,D].  `encoder_states` [B,S,D] skips the
-        encoder (reference src/model/model.py:76-83); activations are bf16 (float32 in the fp32 validation mode)."""
+        encoder (reference src/model/model.py:76-83); activations are bf16 (float32 in the fp32 validation mode).
+        `loss_weights` ([B, T] per decoder row or [B] per sequence, indexed like `labels`) and `loss_reduction` ("mean" / "sum"):
+        kmb_forward_opts.row_weights / loss_reduction."""
         with torch.cuda.device(self.device):
             b, keep, (B, S, T, ntot) = self._batch(input_ids, image_features if encoder_states is None else [],
                                                    attention_mask, decoder_input_ids, decoder_attention_mask, labels)
@@ -299,6 +324,7 @@ class Engine:
                 dec = torch.empty((B, T, D), dtype=self.act_dtype, device=self.device)
                 opts.decoder_states_out = ptr(dec)
             opts.skip_head = 1 if skip_head else 0
+            self._loss_opts(opts, keep, loss_weights, loss_reduction, labels, B, T)
             self.fwd_serial += 1
             check(self.lib.kmb_forward_ex(self.h, C.byref(b), C.byref(opts), 1 if train else 0, 1 if need_grad else 0,
                                           ptr(loss), ptr(logits), ptr(enc), _stream()))
@@ -389,11 +415,12 @@ class Engine:
 
     def forward_pretrain(self, input_ids, image_features, attention_mask, decoder_input_ids, decoder_attention_mask,
                          labels, mrm=None, attr=None, rel=None, factors=(1.0, 1.0, 1.0, 1.0), train=False,
-                         need_grad=False, want_logits=False, encoder_states=None, want_encoder=False):
+                         need_grad=False, want_logits=False, encoder_states=None, want_encoder=False,
+                         loss_weights=None, loss_reduction="mean"):
         """mrm = (rows int32 [n], soft targets fp32 [n, C]); attr = (rows, labels int64); rel = (obj rows, subj rows,
         labels).  Returns (losses fp32 [5] = total, lm, mrm, attribute, relation; logits or None) -- plus the encoder states
         with want_encoder.  `encoder_states` [B,S,D] skips the encoder (reference src/model/model.py:225-242 passes
-        `encoder_outputs` through to self.model)."""
+        `encoder_outputs` through to self.model).  `loss_weights` / `loss_reduction` as in `forward`: the LM term only."""
         refuse_ignored_head_labels("attribute", None if attr is None else attr[1])
         refuse_ignored_head_labels("relation", None if rel is None else rel[2])
         with torch.cuda.device(self.device):
@@ -440,6 +467,7 @@ class Engine:
                 opts.encoder_states = ptr(encoder_states)
                 keep.append(encoder_states)
             enc = torch.empty((B, S, D), dtype=self.act_dtype, device=dev) if want_encoder else None
+            self._loss_opts(opts, keep, loss_weights, loss_reduction, labels, B, T)
             check(self.lib.kmb_forward_pretrain_ex(self.h, C.byref(b), C.byref(ex), C.byref(opts), 1 if train else 0,
                                                    1 if need_grad else 0, ptr(logits), ptr(enc), _stream()))
             self._keep = keep

@@ -449,6 +449,13 @@ class _EncoderHandle:
     forward = __call__
 
 
+def _check_loss_args(loss_weights, loss_reduction, labels):
+    if loss_reduction not in ("mean", "sum"):
+        raise ValueError("loss_reduction must be 'mean' or 'sum', got %r" % (loss_reduction,))
+    if loss_weights is not None and labels is None:
+        raise ValueError("loss_weights weigh the rows' cross-entropy: they need labels")
+
+
 def _check_label_smoothing(eps):
     eps = float(eps)
     if not (0.0 <= eps < 1.0):   # (NaN fails both)
@@ -608,15 +615,26 @@ class MultiModalBartForConditionalGeneration(nn.Module):
     # ------------------------------------------------------------------ forward / backward
     def forward(self, input_ids, image_features, attention_mask=None, encoder_outputs=None, decoder_input_ids=None,
                 decoder_attention_mask=None, decoder_cached_states=None, labels=None, use_cache=None,
-                output_attentions=None, output_hidden_states=None, return_logits=None, **unused):
+                output_attentions=None, output_hidden_states=None, return_logits=None, loss_weights=None,
+                loss_reduction="mean", **unused):
         """Reference src/model/model.py:325-405.  Returns (loss, logits, encoder_last_hidden) with labels,
         (logits, encoder_last_hidden) without; with `use_cache=True` (and no labels) the KV-cached step of
         src/model/model.py:384-397: (logits of the LAST decoder position [rows, 1, V], decoder_cached_states,
         encoder_last_hidden), see _forward_cached.  Deliberate difference: `use_cache=None` means False here -- the
         reference falls back to config.use_cache (True), i.e. an eval forward without labels returns only the last
         position there; no caller of the reference relies on that (fine_tune / validation pass labels, generate passes
-        use_cache), and the teacher-forced logits of every position are what the parity tests compare."""
+        use_cache), and the teacher-forced logits of every position are what the parity tests compare.
+        `loss_weights` (not in the reference; float32 [B, T] per decoder row or [B] per sequence, indexed like `labels`) and
+        `loss_reduction` ("mean", the default, or "sum") turn the loss into  sum_r w_r nll_r / D  over the rows with a valid label,
+        D = their number ("mean") or 1 ("sum"); nll_r carries the label-smoothing term when `label_smoothing` is on.  Signed
+        per-sequence weights (reward - baseline) / B with "sum" make it the REINFORCE / self-critical objective
+        (src/training.py::self_critical_step); positive ones re-weight samples or tasks.  The weights are constants of the loss (no
+        gradient flows to them); a row whose label is -100 contributes exactly nothing whatever its weight holds, NaN included; a
+        valid row with weight 0 still counts in D.  The gradient is that of the FULL log-softmax: it equals the gradient of a
+        sampler's sum_logprobs only when sampling ran unfiltered (top_k=0, top_p=1.0) -- the restricted-support softmax of top-k /
+        top-p sampling is not covered."""
         eng = self._need_engine()
+        _check_loss_args(loss_weights, loss_reduction, labels)
         use_cache = self._resolve_use_cache(use_cache, labels is not None, decoder_input_ids, decoder_cached_states,
                                             output_attentions, output_hidden_states)
         if use_cache or decoder_cached_states is not None:
@@ -645,7 +663,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         lazy_enc = need_grad and enc_states is None and not eng.fp32_mode
         loss, logits, enc = eng.forward(input_ids, image_features, attention_mask, decoder_input_ids,
                                         decoder_attention_mask, labels, train=self.training, need_grad=need_grad,
-                                        want_logits=want_logits, encoder_states=enc_states, want_encoder=not lazy_enc)
+                                        want_logits=want_logits, encoder_states=enc_states, want_encoder=not lazy_enc,
+                                        loss_weights=loss_weights, loss_reduction=loss_reduction)
         if lazy_enc:
             enc = LazyEncoderStates(eng)
         # output_hidden_states / output_attentions (src/model/modules.py:143-165, transformers 3.0.2 BartDecoder; the tuple
@@ -1348,13 +1367,17 @@ class MultiModalBartForPreTraining(MultiModalBartForConditionalGeneration):
     def forward(self, input_ids, image_features, attention_mask=None, encoder_outputs=None, decoder_input_ids=None,
                 decoder_attention_mask=None, decoder_cached_states=None, labels=None, mrm_labels=None, mrm_mask=None,
                 attribute_labels=None, attribute_mask=None, relation_labels=None, use_cache=None,
-                output_attentions=None, output_hidden_states=None, return_logits=None, **unused):
+                output_attentions=None, output_hidden_states=None, return_logits=None, loss_weights=None,
+                loss_reduction="mean", **unused):
         """Reference src/model/model.py:162-309.  With any label the loss dict comes first: (losses, logits[, decoder hidden
         states, decoder attentions], encoder states[, encoder hidden states, encoder attentions]) -- `outputs[1:]` of the bare
         model behind the logits (:291, :309); without labels it is the conditional-generation forward (cache included).
-        `encoder_outputs` is passed through to the model as there (:225-242)."""
+        `encoder_outputs` is passed through to the model as there (:225-242).  `loss_weights` / `loss_reduction` (see the
+        conditional-generation forward) touch the LM term only: `lm_loss_factor` multiplies the weighted term, the MRM, attribute and
+        relation terms and their factors are as they were."""
         eng = self._need_engine()
         cfg = self.config
+        _check_loss_args(loss_weights, loss_reduction, labels)
         if labels is None and mrm_labels is None and attribute_labels is None and relation_labels is None:
             return super().forward(input_ids, image_features, attention_mask=attention_mask, encoder_outputs=encoder_outputs,
                                    decoder_input_ids=decoder_input_ids, decoder_attention_mask=decoder_attention_mask,
@@ -1405,7 +1428,7 @@ class MultiModalBartForPreTraining(MultiModalBartForConditionalGeneration):
                                    decoder_attention_mask, lm_labels, mrm=mrm, attr=attr, rel=rel,
                                    factors=factors, train=self.training, need_grad=need_grad,
                                    want_logits=bool(return_logits), encoder_states=enc_states,
-                                   want_encoder=not lazy_enc)
+                                   want_encoder=not lazy_enc, loss_weights=loss_weights, loss_reduction=loss_reduction)
         losses, logits = res[0], res[1]
         enc = LazyEncoderStates(eng) if lazy_enc else res[2]
         dec_extra, enc_extra = (), ()

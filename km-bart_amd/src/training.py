@@ -277,3 +277,54 @@ def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callb
     if tb_writer is not None:
         tb_writer.add_scalars("loss/epoch", {"train": loss_sum / max(n_steps, 1)}, epoch + 1)
     return loss_sum / max(n_steps, 1)
+
+
+def self_critical_step(model, batch, reward_fn, device, baseline="greedy", sample_kwargs=None):
+    """One REINFORCE / self-critical loss (Rennie et al. 2017) on `batch` (input_ids, image_features, attention_mask):
+    under no_grad one `generate(do_sample=True, num_beams=1, top_k=0, top_p=1.0, ...)` draws a sequence per input from the model's
+    full distribution; `reward_fn(ids) -> float32 [B]` (the caller's: no metric is part of this package) scores it; the advantage is
+    A = reward(sample) - baseline with baseline = the reward of one greedy `generate(num_beams=1)` ("greedy"), zero (None) or a
+    given [B] tensor.  Then ONE teacher-forced forward on the samples (src/model/utils.py::labels_from_generated) with
+    `loss_weights = A / B, loss_reduction="sum"`:  loss = -(1 / B) sum_b A_b log p(y_b | x_b), whose gradient is the policy gradient.
+    Returns (loss, info); the caller runs `loss.backward()` and steps its optimizer.  info: `sample_ids`, `advantages`, `rewards`
+    and `baseline` as device tensors (and `greedy_ids` with the greedy baseline); nothing here reads a value back.
+    `sample_kwargs` goes to both generate calls (max_length, min_length, ...); its `pad_to_multiple_of` (optional) goes to
+    labels_from_generated instead.  Sampling is unfiltered on purpose: the forward's gradient is that of the full log-softmax, which is
+    the sampler's log-probability only without top-k / top-p filtering."""
+    from src.model.utils import labels_from_generated
+
+    kw = dict(sample_kwargs or {})
+    pad_to = kw.pop("pad_to_multiple_of", None)
+    for fixed in ("do_sample", "num_beams", "top_k", "top_p"):
+        if fixed in kw:
+            raise ValueError("self_critical_step fixes %s itself (unfiltered one-beam sampling)" % fixed)
+    input_ids = batch["input_ids"].to(device)
+    image_features = _features(batch["image_features"], device)
+    attention_mask = batch["attention_mask"].to(device)
+    info = {}
+    with torch.no_grad():
+        sample_ids = model.generate(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
+                                    do_sample=True, num_beams=1, top_k=0, top_p=1.0, **kw)
+        rewards = reward_fn(sample_ids).to(device=device, dtype=torch.float32)
+        if baseline is None:
+            base = torch.zeros_like(rewards)
+        elif isinstance(baseline, str):
+            if baseline != "greedy":
+                raise ValueError("baseline must be 'greedy', None or a [B] tensor, got %r" % (baseline,))
+            greedy_ids = model.generate(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
+                                        do_sample=False, num_beams=1, **kw)
+            base = reward_fn(greedy_ids).to(device=device, dtype=torch.float32)
+            info["greedy_ids"] = greedy_ids
+        else:
+            base = baseline.to(device=device, dtype=torch.float32)
+        advantages = rewards - base
+    cfg = getattr(model, "module", model).config
+    pad_id = kw.get("pad_token_id", cfg.pad_token_id)
+    eos_id = kw.get("eos_token_id", cfg.eos_token_id)
+    dec_in, dec_mask, labels = labels_from_generated(sample_ids, pad_id, eos_id, pad_to_multiple_of=pad_to)
+    B = sample_ids.shape[0]
+    outputs = model.forward(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
+                            decoder_input_ids=dec_in, decoder_attention_mask=dec_mask, labels=labels,
+                            loss_weights=advantages / B, loss_reduction="sum")
+    info.update(sample_ids=sample_ids, advantages=advantages, rewards=rewards, baseline=base)
+    return outputs[0], info
