@@ -548,6 +548,29 @@ int kmb_logits_process(float* logits, int ld, int V, int R, const int64_t* ids, 
  * kmb_gen_sample_step folds in is not affected. */
 int kmb_gen_logits_process(kmb_handle* h, float* logits, int ld, const int64_t* ids, int ld_ids, int t, float repetition_penalty,
                            int no_repeat_ngram_size, const int32_t* bad_tokens, const int32_t* bad_offsets, int n_bad, void* stream);
+/* CIDEr / CIDEr-D over TOKEN IDS as a sequence-level reward (self-critical training): out[b] (fp32 [B], device) = the score of row b
+ * of ids [B, ld] (int64, device, L columns read) against the references of item item_of_row[b] (int32 [B], device).  ONE launch, one
+ * workgroup per row, stateless, no host synchronisation.  Not the word-level metric of the reference's evaluation: tokens are ids.
+ * Tokens of a row: column 0 (the decoder start token) is skipped, the row stops in front of the first eos_token behind it, every
+ * pad_token and bos_token is dropped (and any id outside [0, 65536)).  With g_x,n(w) = count_x(w) * idf_n(w) over the n-grams w of
+ * order n = 1..4:  s_n(h, r) = sum_{w in h} num / (||g_h,n|| ||g_r,n||), 0 when a norm is 0, num = min(g_h, g_r) * g_r (variant 0,
+ * CIDEr-D) or g_h * g_r (variant 1, plain CIDEr); pen = exp(-(L_h - L_r)^2 / (2 sigma^2)) (variant 0) or 1;
+ * score = (10 / m) sum_r pen * 1/4 sum_n s_n over the item's m references.  An item index outside [0, n_items), an item without
+ * references and an empty hypothesis score 0 and read no table.
+ * The tables (src/rewards.py build_cider_tables; device memory except df_offsets, 5 int64 on the HOST, read at the call): an n-gram
+ * is the key sum_k tok[k] << 16 (n - 1 - k), one key space per order, ordered UNSIGNED (int64 bit patterns);
+ *   df_keys / df_idf [df_offsets[4]]: order n's distinct n-grams in [df_offsets[n - 1], df_offsets[n]), ascending, with
+ *     idf = log N - log max(1, df); idf_miss = float32(log N) for an n-gram in no reference;
+ *   item_ref_offsets [n_items + 1]; ref_len [n_refs]; ref_norm [n_refs, 4] = ||g_r,n||;
+ *   ref_ng_offsets [4 n_refs + 1]: slice 4 r + (n - 1) of ref_keys (ascending) / ref_w (count * idf), n_ref_entries in all.
+ * Lookups are binary searches; fp32, no atomics, fixed reduction order: the same input gives the same bits.  Needs
+ * 1 <= L <= 256 (KMB_CIDER_MAX_T, csrc/cider_reward.h), ld >= L, B >= 0, sigma finite and > 0, variant 0 or 1 and no null
+ * pointer; fails with a message and launches nothing otherwise. */
+int kmb_cider_reward(const int64_t* ids, int ld, int B, int L, int pad_token, int bos_token, int eos_token, const int32_t* item_of_row,
+                     int n_items, const int64_t* df_keys, const float* df_idf, const int64_t* df_offsets, float idf_miss,
+                     const int32_t* item_ref_offsets, int n_refs, const int32_t* ref_len, const float* ref_norm,
+                     const int32_t* ref_ng_offsets, const int64_t* ref_keys, const float* ref_w, int64_t n_ref_entries, int variant,
+                     float sigma, float* out, void* stream);
 /* One step of greedy beam search with generate()'s score processors (transformers 3.0.2 _generate_beam_search: log_softmax, then
  * postprocess_next_token_scores on the LOG-PROBABILITIES, then + beam score and the 2 * num_beams best per batch item): kmb_beam_step's
  * arguments, outputs and selection, plus kmb_logits_process's processor arguments and the beams' token histories.  At most three

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libkmbart_hip.so")
-SOURCES = ["gemm.hip", "gemm_pair.hip", "gemm_lean.hip", "attention.hip", "norm.hip", "embed.hip", "loss.hip", "beam_step.hip", "optim.hip", "heads.hip", "fp32_validate.hip", "decode.hip", "sample.hip", "beam_sample.hip", "greedy.hip", "logits_process.hip", "beam_process.hip", "engine.cpp", "engine_train.cpp", "engine_comm.cpp", "engine_gen.cpp",
+SOURCES = ["gemm.hip", "gemm_pair.hip", "gemm_lean.hip", "attention.hip", "norm.hip", "embed.hip", "loss.hip", "beam_step.hip", "optim.hip", "heads.hip", "fp32_validate.hip", "decode.hip", "sample.hip", "beam_sample.hip", "greedy.hip", "logits_process.hip", "beam_process.hip", "cider_reward.hip", "engine.cpp", "engine_train.cpp", "engine_comm.cpp", "engine_gen.cpp",
            "capi_ops.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"]
 # -fno-slp-vectorize: with SLP-packed fp32 math (v_pk_add_f32 / v_pk_mul_f32 with op_sel / neg modifiers on register pairs

@@ -10,6 +10,7 @@
 #include "greedy.h"
 #include "beam_process.h"
 #include "logits_process.h"
+#include "cider_reward.h"
 
 extern "C" const char* kmb_last_error(void);
 int kmb_set_error(const char* msg);  // engine.cpp
@@ -592,6 +593,20 @@ int kmb_logits_process(float* logits, int ld, int V, int R, const int64_t* ids, 
                  "logits_process");
 }
 
+int kmb_cider_reward(const int64_t* ids, int ld, int B, int L, int pad_token, int bos_token, int eos_token, const int32_t* item_of_row,
+                     int n_items, const int64_t* df_keys, const float* df_idf, const int64_t* df_offsets, float idf_miss,
+                     const int32_t* item_ref_offsets, int n_refs, const int32_t* ref_len, const float* ref_norm,
+                     const int32_t* ref_ng_offsets, const int64_t* ref_keys, const float* ref_w, int64_t n_ref_entries, int variant,
+                     float sigma, float* out, void* stream) {
+  if (!df_offsets) return kmb_set_error("kmb_cider_reward: df_offsets (host, 5 x int64) is required");
+  KmbCiderTables t{n_items, (const uint64_t*)df_keys, df_idf, {df_offsets[0], df_offsets[1], df_offsets[2], df_offsets[3], df_offsets[4]},
+                   idf_miss, item_ref_offsets, n_refs, ref_len, ref_norm, ref_ng_offsets, (const uint64_t*)ref_keys, ref_w, n_ref_entries};
+  if (kmb_cider_reward_validate("kmb_cider_reward", ids, ld, B, L, item_of_row, t, variant, sigma, out) != 0) return -1;
+  return hipfail(kmb_cider_reward_launch(ids, ld, B, L, pad_token, bos_token, eos_token, item_of_row, t, variant, sigma, out,
+                                         (hipStream_t)stream),
+                 "cider_reward");
+}
+
 int64_t kmb_beam_step_processed_scratch(int rows, int t, int n_bad) {
   return (int64_t)kmb_beam_step_processed_scratch_floats(rows, t, n_bad);
 }
@@ -733,5 +748,27 @@ int kmb_logits_process_validate(const char* who, const float* logits, int ld, in
   if (no_repeat_ngram_size < 0) return bad("no_repeat_ngram_size must be >= 0");
   if (n_bad < 0 || n_bad > KMB_PROCESS_MAX_BAD) return bad("need 0 <= n_bad <= 4096");
   if (n_bad > 0 && (!bad_tokens || !bad_offsets)) return bad("bad_tokens and bad_offsets (n_bad + 1 of them) are required with n_bad > 0");
+  return 0;
+}
+
+// The argument checks of kmb_cider_reward (`who` names the caller in the message).
+int kmb_cider_reward_validate(const char* who, const int64_t* ids, int ld, int B, int L, const int32_t* item_of_row,
+                              const KmbCiderTables& t, int variant, float sigma, const float* out) {
+  char buf[256];
+  auto bad = [&](const char* what) {
+    snprintf(buf, sizeof(buf), "%s: %s", who, what);
+    return kmb_set_error(buf);
+  };
+  if (!ids || !item_of_row || !out) return bad("ids, item_of_row and out are required");
+  if (!t.df_keys || !t.df_idf || !t.item_ref_offsets || !t.ref_len || !t.ref_norm || !t.ref_ng_offsets || !t.ref_keys || !t.ref_w)
+    return bad("every table pointer is required (an empty table still has an allocation behind it)");
+  if (B < 0) return bad("need B >= 0");
+  if (L < 1 || L > KMB_CIDER_MAX_T || ld < L) return bad("need 1 <= L <= 256 (KMB_CIDER_MAX_T) and ld >= L");
+  if (variant != KMB_CIDER_VARIANT_D && variant != KMB_CIDER_VARIANT_PLAIN) return bad("variant must be 0 (CIDEr-D) or 1 (plain CIDEr)");
+  if (!(sigma > 0.f) || std::isinf(sigma)) return bad("sigma must be finite and > 0");
+  if (t.n_items < 0 || t.n_refs < 0 || t.n_ref_entries < 0) return bad("need n_items >= 0, n_refs >= 0, n_ref_entries >= 0");
+  if (t.df_offsets[0] != 0) return bad("df_offsets must start at 0");
+  for (int n = 0; n < KMB_CIDER_ORDERS; ++n)
+    if (t.df_offsets[n + 1] < t.df_offsets[n]) return bad("df_offsets must ascend");
   return 0;
 }

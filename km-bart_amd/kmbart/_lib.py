@@ -183,6 +183,8 @@ PROTOTYPES = {
                                       c_p]),
     "kmb_logits_process": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
     "kmb_gen_logits_process": (C.c_int, [c_p, c_p, C.c_int, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),
+    "kmb_cider_reward": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_p, C.c_int, c_p, c_p, c_p, f32, c_p, C.c_int,
+                                   c_p, c_p, c_p, c_p, c_p, i64, C.c_int, f32, c_p, c_p]),
     "kmb_beam_step_processed_scratch": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "kmb_beam_step_processed": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, c_p, C.c_int, C.c_int, C.c_int, c_p, C.c_int, c_p, c_p,
                                           c_p, c_p, C.c_int64, c_p, c_p, C.c_int, C.c_int, f32, C.c_int, c_p, c_p, C.c_int, c_p]),

@@ -279,11 +279,81 @@ def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callb
     return loss_sum / max(n_steps, 1)
 
 
+def self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args, reward, logger=None, callback=None,
+                            log_interval=1, tb_writer=None, tb_interval=1, baseline="greedy", sample_kwargs=None):
+    """`fine_tune` with the self-critical loss in place of the cross-entropy: per batch `self_critical_step` with
+    `reward.for_batch(batch)` (src.rewards.CiderReward: the reward is computed on the device), then zero_grad -> backward ->
+    optimizer step in fine_tune's order, with its accumulation and its data-parallel scopes.  The log line is fine_tune's plus the
+    batch's mean reward and mean advantage:
+    `Epoch [e/E], Step [i/N], Loss: x.xxxx, Reward: x.xxxx, Advantage: x.xxxx, ETA: ...`.
+    Values are read back only where fine_tune reads its loss: step i's after step i + 1 has been enqueued.  Returns the epoch's
+    mean loss.  baseline: "greedy" or None; sample_kwargs goes to self_critical_step (max_length, ...)."""
+    n_accum = _accumulation_steps(args)
+    try:
+        if n_accum > 1:
+            _accumulate(model, True)
+        return _self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args, reward, logger, callback,
+                                        log_interval, tb_writer, tb_interval, baseline, sample_kwargs, n_accum)
+    finally:
+        _release(model, optimizer, n_accum > 1)
+
+
+def _self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args, reward, logger, callback, log_interval,
+                             tb_writer, tb_interval, baseline, sample_kwargs, n_accum=1):
+    n_steps = len(train_loader)
+    model.train()
+    t0 = datetime.now()
+    _allow_overlap(optimizer, True)
+    _attach(model, optimizer, True)
+    pending = None
+    state = {"sum": 0.0}
+
+    def report(item):
+        if item is None:
+            return
+        j, dev_values, _, record = item
+        loss_value, reward_value, advantage_value = dev_values.tolist()   # one read for the three
+        state["sum"] += loss_value
+        if logger is not None and j % log_interval == 0:
+            eta = (n_steps - (j + 1)) / (j + 1) * (datetime.now() - t0)
+            logger.info("Epoch [{}/{}], Step [{}/{}], Loss: {:.4f}, Reward: {:.4f}, Advantage: {:.4f}, ETA: {}".format(
+                epoch + 1, args.epochs, j + 1, n_steps, loss_value, reward_value, advantage_value, str(eta)))
+            _norm_line(record, logger, epoch, args, j, n_steps)
+        if tb_writer is not None and j % tb_interval == 0:
+            tb_writer.add_scalars("loss/step", {"loss": loss_value, "reward": reward_value, "advantage": advantage_value},
+                                  epoch * n_steps + j + 1)
+
+    for i, batch in enumerate(train_loader):
+        loss, info = self_critical_step(model, batch, reward.for_batch(batch), device, baseline=baseline,
+                                        sample_kwargs=sample_kwargs)
+        first, last = _micro_step(i, n_steps, n_accum)
+        if first:
+            optimizer.zero_grad()
+        micro_loss = loss if n_accum == 1 else loss / n_accum
+        with _sync_scope(model, last):
+            micro_loss.backward()
+        if last:
+            optimizer.step()
+        report(pending)                       # step i-1, while step i runs on the GPU
+        values = torch.stack([loss.detach().float().reshape(()), info["rewards"].mean(), info["advantages"].mean()])
+        pending = (i, values, None, _step_record(optimizer) if last else None)
+        if callback is not None:
+            report(pending)
+            pending = None
+            callback(step=i, epoch=epoch, model=model, train_loader=train_loader, optimizer=optimizer, args=args,
+                     logger=logger)
+    report(pending)
+    loss_sum = state["sum"]
+    if tb_writer is not None:
+        tb_writer.add_scalars("loss/epoch", {"train": loss_sum / max(n_steps, 1)}, epoch + 1)
+    return loss_sum / max(n_steps, 1)
+
+
 def self_critical_step(model, batch, reward_fn, device, baseline="greedy", sample_kwargs=None):
     """One REINFORCE / self-critical loss (Rennie et al. 2017) on `batch` (input_ids, image_features, attention_mask):
     under no_grad one `generate(do_sample=True, num_beams=1, top_k=0, top_p=1.0, ...)` draws a sequence per input from the model's
-    full distribution; `reward_fn(ids) -> float32 [B]` (the caller's: no metric is part of this package) scores it; the advantage is
-    A = reward(sample) - baseline with baseline = the reward of one greedy `generate(num_beams=1)` ("greedy"), zero (None) or a
+    full distribution; `reward_fn(ids) -> float32 [B]` scores it (any callable; src.rewards.CiderReward.for_batch(batch) is a CIDEr-D
+    computed on the device); the advantage is A = reward(sample) - baseline with baseline = the reward of one greedy `generate(num_beams=1)` ("greedy"), zero (None) or a
     given [B] tensor.  Then ONE teacher-forced forward on the samples (src/model/utils.py::labels_from_generated) with
     `loss_weights = A / B, loss_reduction="sum"`:  loss = -(1 / B) sum_b A_b log p(y_b | x_b), whose gradient is the policy gradient.
     Returns (loss, info); the caller runs `loss.backward()` and steps its optimizer.  info: `sample_ids`, `advantages`, `rewards`

@@ -24,7 +24,7 @@ from kmbart.parallel import DistributedDataParallel  # noqa: E402
 from kmbart.data import DevicePrefetcher  # noqa: E402
 from src.data.synthetic import make_batch  # noqa: E402
 from src.model import MultiModalBartConfig, MultiModalBartForConditionalGeneration  # noqa: E402
-from src.training import fine_tune  # noqa: E402
+from src.training import fine_tune, self_critical_fine_tune  # noqa: E402
 from src.utils import Logger, cleanup_process, load_training_data, save_training_data, setup_process  # noqa: E402
 
 
@@ -62,6 +62,32 @@ def build_vcg_loader(args, rank, device, split="train"):
     return DevicePrefetcher(loader, device)
 
 
+def build_reward(args, config, loader, device):
+    """--self_critical: the CIDEr-D / CIDEr reward over token ids (src/rewards.py) with the training split's targets as references,
+    grouped by (index, task_type).  Synthetic batches carry their targets as label ids; real data is tokenised as the Collator
+    tokenises a target."""
+    from src.rewards import CiderReward, reward_tokens
+    variant = {"cider_d": "D", "cider": "plain"}[args.sc_reward]
+    if args.synthetic > 0:
+        start = config.decoder_start_token_id if getattr(config, "decoder_start_token_id", None) is not None else config.eos_token_id
+        item_of, groups = {}, []
+        for batch in loader:
+            for index, task, row in zip(batch["index"], batch["task_type"], batch["labels"].tolist()):
+                item = item_of.setdefault((index, task), len(groups))
+                if item == len(groups):
+                    groups.append([])
+                groups[item].append(reward_tokens([start] + [t for t in row if t != -100], config.pad_token_id, config.bos_token_id,
+                                                  config.eos_token_id))
+        return CiderReward(groups, config.vocab_size, config.pad_token_id, config.bos_token_id, config.eos_token_id, variant=variant,
+                           device=device, group_keys=list(item_of))
+    from src.data.dataset import VCGDataset
+    from src.data.offline_tokenizer import load_base_tokenizer
+    from src.data.tokenization import ConditionTokenizer
+    tokenizer = ConditionTokenizer(base_tokenizer=load_base_tokenizer(args.tokenizer_json or "facebook/bart-large"))
+    records = VCGDataset(args.data_dir, split="train", use_image=False, use_event=args.use_event)
+    return CiderReward.from_records([records[i] for i in range(len(records))], tokenizer, config, variant=variant, device=device)
+
+
 def main(rank, args):
     distributed = args.gpu_num > 1
     if distributed:
@@ -95,9 +121,19 @@ def main(rank, args):
         loader = SyntheticLoader(args.synthetic, args.batch_size, rank, use_image=args.use_image)
     else:
         loader = build_vcg_loader(args, rank, device)
+    reward = None
+    if args.self_critical:
+        reward = build_reward(args, (model.module if distributed else model).config, loader, device)
+        logger.info("Self-critical training: {} over token ids, {} items, {} references, {:.1f} MB of tables".format(
+            args.sc_reward, reward.n_items, reward.n_refs, reward.table_bytes() / 2 ** 20))
     for epoch in range(start_epoch, args.epochs):
         logger.info("Epoch {}".format(epoch + 1), pad=True)
-        fine_tune(epoch, model, loader, optimizer, device, args, logger=logger, log_interval=args.log_interval)
+        if reward is not None:
+            self_critical_fine_tune(epoch, model, loader, optimizer, device, args, reward, logger=logger,
+                                    log_interval=args.log_interval, baseline="greedy" if args.sc_baseline == "greedy" else None,
+                                    sample_kwargs=dict(max_length=args.sc_max_length))
+        else:
+            fine_tune(epoch, model, loader, optimizer, device, args, logger=logger, log_interval=args.log_interval)
         if rank == 0:
             inner = model.module if distributed else model
             if args.validate_loss and args.synthetic <= 0:
@@ -143,6 +179,13 @@ def parse_args(argv=None):
                    help="optimizer step every N batches on the sum of their gradients, each batch's loss divided by N (default 1)")
     p.add_argument("--label_smoothing", default=0.0, type=float,
                    help="label smoothing of the LM cross-entropy, in [0, 1) (default 0.0: the model config's value, if it has one, stays)")
+    p.add_argument("--self_critical", action="store_true",
+                   help="self-critical sequence training: REINFORCE on sampled sequences with a reward computed on the device "
+                        "(token-id-level CIDEr, not the word-level evaluation metric) in place of the cross-entropy")
+    p.add_argument("--sc_reward", default="cider_d", choices=["cider_d", "cider"], help="the reward of --self_critical")
+    p.add_argument("--sc_baseline", default="greedy", choices=["greedy", "none"],
+                   help="the baseline of --self_critical: the reward of a greedy decode, or none")
+    p.add_argument("--sc_max_length", default=32, type=int, help="max_length of the sampled and greedy sequences (<= 256)")
     p.add_argument("--master_port", type=str, default="12355")
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--num_workers", type=int, default=0)
@@ -158,6 +201,11 @@ def parse_args(argv=None):
         raise ValueError("--accumulation_steps must be >= 1, got %d" % args.accumulation_steps)
     if not (0.0 <= args.label_smoothing < 1.0):
         raise ValueError("--label_smoothing must be in [0, 1), got %r" % (args.label_smoothing,))
+    if args.self_critical:
+        if not 2 <= args.sc_max_length <= 256:
+            raise ValueError("--sc_max_length must be in [2, 256] (the reward kernel's width), got %d" % args.sc_max_length)
+        if args.amp:
+            raise ValueError("--self_critical does not take --amp (the loss scaler has no place in the reward-weighted step)")
     if args.checkpoint is None and args.model_config is None:
         raise ValueError("--model_config and --checkpoint cannot be empty at the same time")
     if args.synthetic <= 0 and args.data_dir is None:
