@@ -130,6 +130,9 @@ typedef struct KmbAttnDecode {
    * t < Tk-1 of row r is read from cache row hist[r*Tmax + t]; the launch records hist[r*Tmax + Tk-1] = r for the row it appends.  A beam
    * reorder then permutes these small rows instead of copying the caches (src/model/mixins.py:419-434 _reorder_cache). */
   int32_t* hist;
+  /* kmb_op_attn_decode refuses (before any GPU call): Tk < 1 or Tk > Tmax; Tk > 4096 (16 Tk bytes of LDS per workgroup, 64 KB); a missing
+   * Q / Kc / Vc / O; new_k, new_v, Kw, Vw not all or none; Q, Kc, Vc, new_k, new_v not 16-byte aligned; ldq, ldc, ld_new not multiples
+   * of 8; key_mask with mask_ld < Tk.  R * H <= 0 is nothing to do.  A row whose keys are all masked gets zeros. */
 } KmbAttnDecode;
 
 /* One fused block of a KV-cached decode step (csrc/decode.hip): [LayerNorm ->] projection of R rows [-> attention].
@@ -649,6 +652,20 @@ int kmb_gemm_shared_device(int on);
  * (variant 0: the narrow kernel), kernel variant that runs it (honours kmb_gemm_shared_device), tile_order it is launched
  * with).  Returns the number of int32 words written, -1 for a problem kmb_op_gemm refuses or a cap too small. */
 int kmb_debug_gemm_route(const KmbGemm* p, int forced_variant, int32_t* out, int32_t cap);
+
+/* Diagnostic: the kernel kmb_op_decode_block would run for *p, decided by the function the launch itself asks -- no GPU call, the
+ * operands are never dereferenced.  Kind 0: the wide projection (two 16-column tiles per wave, N >= 1536) or the one-tile projection with
+ * 2 / 4 / 6 staged 16-byte chunks per lane (K = 768 | 1536 | 2304, 3072); kind 1: the self-attention block; kind 2: the vector
+ * cross-attention block, or the one that stages each batch item's keys / values in LDS and runs on the matrix cores (kv_group >= 4,
+ * Tk <= 120 and 160 KB of LDS: Tk <= 104 at K = 768).  Returns -1 for a block kmb_op_decode_block refuses. */
+#define KMB_DECODE_ROUTE_PROJ_WIDE 0
+#define KMB_DECODE_ROUTE_PROJ2 1
+#define KMB_DECODE_ROUTE_PROJ4 2
+#define KMB_DECODE_ROUTE_PROJ6 3
+#define KMB_DECODE_ROUTE_ATTN_SELF 4
+#define KMB_DECODE_ROUTE_ATTN_CROSS 5
+#define KMB_DECODE_ROUTE_ATTN_CROSS_KVLDS 6
+int kmb_debug_decode_route(const KmbDecodeBlock* p);
 
 /* ================= data parallelism: native RCCL (vcg_train.py:98 DDP, src/utils.py:9-17 init_process_group) =================
  * One process per GPU; the library owns the communicator and a communication stream, and a step's whole gradient

@@ -1087,6 +1087,23 @@ hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// one wave's score row is Tk floats, four waves per workgroup, and the launcher never raises the default dynamic LDS limit
+constexpr size_t ATTN_DECODE_LDS_MAX = 64 * 1024;
+
+const char* kmb_attn_decode_check(const KmbAttnDecode& p) {
+  if (p.R <= 0 || p.H <= 0) return nullptr;   // nothing to do: the launcher returns at once
+  if (p.Tk < 1 || p.Tk > p.Tmax) return "attention decode: Tk must be in 1 .. Tmax";
+  if ((size_t)4 * p.Tk * sizeof(float) > ATTN_DECODE_LDS_MAX) return "attention decode: Tk > 4096 does not fit the score rows in LDS";
+  if (!p.Q || !p.Kc || !p.Vc || !p.O) return "attention decode: missing tensor";
+  const int nnew = (p.new_k != nullptr) + (p.new_v != nullptr) + (p.Kw != nullptr) + (p.Vw != nullptr);
+  if (nnew != 0 && nnew != 4) return "attention decode: new_k / new_v / Kw / Vw must be given all four or none";
+  if (((uintptr_t)p.Q & 15) || ((uintptr_t)p.Kc & 15) || ((uintptr_t)p.Vc & 15) || ((uintptr_t)p.new_k & 15) || ((uintptr_t)p.new_v & 15))
+    return "attention decode: Q / Kc / Vc / new_k / new_v must be 16-byte aligned";
+  if ((p.ldq & 7) || (p.ldc & 7) || (nnew && (p.ld_new & 7))) return "attention decode: ldq / ldc / ld_new must be multiples of 8";
+  if (p.key_mask != nullptr && p.mask_ld < p.Tk) return "attention decode: mask_ld must be at least Tk";
+  return nullptr;
+}
+
 hipError_t kmb_attn_decode_launch(const KmbAttnDecode& p, hipStream_t stream) {
   const int items = p.R * p.H;
   if (items <= 0) return hipSuccess;

@@ -126,6 +126,9 @@ int kmb_op_attn_bwd(const KmbAttn* p, void* stream) {
   return hipfail(kmb_attn_bwd_launch(*p, (hipStream_t)stream), "attn_bwd");
 }
 int kmb_op_attn_decode(const KmbAttnDecode* p, void* stream) {
+  if (!p) return kmb_set_error("kmb_op_attn_decode: null problem");
+  const char* why = kmb_attn_decode_check(*p);
+  if (why) return kmb_set_error(why);
   return hipfail(kmb_attn_decode_launch(*p, (hipStream_t)stream), "attn_decode");
 }
 int kmb_op_decode_block(const KmbDecodeBlock* p, void* stream) {
@@ -516,6 +519,10 @@ int kmb_debug_gemm_route(const KmbGemm* p, int forced_variant, int32_t* out, int
   if (!p || !out || cap < 1 || forced_variant < 0) return -1;
   if (kmb_gemm_check(*p) != nullptr) return -1;
   return kmb_gemm_route(*p, forced_variant, out, cap);
+}
+int kmb_debug_decode_route(const KmbDecodeBlock* p) {
+  if (!p || kmb_decode_block_check(*p) != nullptr) return -1;
+  return kmb_decode_block_route(*p);
 }
 int kmb_beam_merge(const float* val, const int32_t* idx, int B, int num_beams, int k, int V, int32_t* out, void* stream) {
   return hipfail(kmb_beam_merge_launch(val, idx, B, num_beams, k, V, out, -1, nullptr, nullptr, nullptr, (hipStream_t)stream), "beam_merge");

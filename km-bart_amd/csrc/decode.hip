@@ -376,7 +376,8 @@ __global__ __launch_bounds__(256, 2) void decode_proj_wide_kernel(const KmbDecod
 //   output  O^T = V_staged^T (e_hi + e_lo)^T : values read as transposed fragments (ds_read_b64_tr_b16), wave w owns
 //                                  head dimensions 16 w .. 16 w + 15; scaled by 1 / sum(e) at the store.
 constexpr int KV_ITEMS = 4;      // batch items a 16-row tile can touch when kv_group >= 4
-constexpr int NKV = 15;          // 16-byte chunks per thread and operand: KV_ITEMS * Tk * 8 <= NKV * 256  (Tk <= 120)
+constexpr int NKV = 15;          // 16-byte chunks per thread and operand: KV_ITEMS * Tk * 8 <= NKV * 256  (Tk <= 120); the staged keys / values,
+                                 // masks and e_hi / e_lo also have to fit 160 KB of LDS (kmb_decode_block_route): Tk <= 104 at K = 768
 constexpr int KS = 144;          // LDS row stride of a staged key row (128 + 16: conflict-free 16-row fragment reads)
 __host__ __device__ constexpr int kv_pad(int Tk) { return (KV_ITEMS * Tk + 31) & ~31; }     // staged keys, padded to MFMA K steps
 __host__ __device__ constexpr int pb_stride(int Tk) { return kv_pad(Tk) * 2 + 16; }          // bytes per row of e_hi / e_lo
@@ -780,10 +781,32 @@ const char* kmb_decode_block_check(const KmbDecodeBlock& p) {
   return nullptr;
 }
 
+namespace {
+// LDS of the attention kinds: activation rows, projected tile, score tile; KVLDS adds the staged keys / values / masks, e_lo and 1 / sum
+size_t attn_lds(const KmbDecodeBlock& p) {
+  return (size_t)RT * (p.K + 8) * 2 + (size_t)RT * ((p.kind == 1 ? 3 * HD : HD) + 8) * 2 + (((size_t)RT * p.Tk * sizeof(float) + 15) & ~(size_t)15);
+}
+size_t attn_lds_kv(const KmbDecodeBlock& p) {
+  return attn_lds(p) + (size_t)KV_ITEMS * p.Tk * (KS + 128 + sizeof(float)) + (size_t)RT * pb_stride(p.Tk) + RT * sizeof(float);
+}
+}  // namespace
+
+// The kernel kmb_decode_block_launch runs for p (a KMB_DECODE_ROUTE_* id); p has passed kmb_decode_block_check.  No GPU call.
+int kmb_decode_block_route(const KmbDecodeBlock& p) {
+  if (p.kind == 0) {
+    const int nch = (p.K / 8 + 63) / 64;
+    if (nch <= 2 && (p.N % 128) == 0 && p.N >= 1536) return KMB_DECODE_ROUTE_PROJ_WIDE;   // half as many LayerNorm prologues
+    return nch <= 2 ? KMB_DECODE_ROUTE_PROJ2 : nch <= 4 ? KMB_DECODE_ROUTE_PROJ4 : KMB_DECODE_ROUTE_PROJ6;
+  }
+  if (p.kind == 1) return KMB_DECODE_ROUTE_ATTN_SELF;
+  if (p.kv_group >= 4 && KV_ITEMS * p.Tk * 8 <= NKV * 256 && attn_lds_kv(p) <= 160 * 1024) return KMB_DECODE_ROUTE_ATTN_CROSS_KVLDS;
+  return KMB_DECODE_ROUTE_ATTN_CROSS;
+}
+
 hipError_t kmb_decode_block_launch(const KmbDecodeBlock& p, hipStream_t stream) {
   const int tiles = (p.R + RT - 1) / RT;
   const size_t a_bytes = (size_t)RT * (p.K + 8) * 2;
-  const int nch = (p.K / 8 + 63) / 64;
+  const int route = kmb_decode_block_route(p);
   hipError_t e = hipSuccess;
   if (p.kind == 0) {
     static size_t set[4] = {0, 0, 0, 0};
@@ -792,21 +815,19 @@ hipError_t kmb_decode_block_launch(const KmbDecodeBlock& p, hipStream_t stream) 
     if (a_bytes > set[SLOT]) { e = set_lds(KERNEL, a_bytes); if (e != hipSuccess) return e; set[SLOT] = a_bytes; }     \
     hipLaunchKernelGGL(KERNEL, dim3(unit_grid(p.N / (64 * NTW), tiles)), dim3(256), a_bytes, stream, p);              \
   } while (0)
-    if (nch <= 2 && (p.N % 128) == 0 && p.N >= 1536) KMB_PROJ(0, decode_proj_wide_kernel, 2);   // half as many LayerNorm prologues
-    else if (nch <= 2) KMB_PROJ(1, decode_proj_kernel<2>, 1);
-    else if (nch <= 4) KMB_PROJ(2, decode_proj_kernel<4>, 1);
+    if (route == KMB_DECODE_ROUTE_PROJ_WIDE) KMB_PROJ(0, decode_proj_wide_kernel, 2);
+    else if (route == KMB_DECODE_ROUTE_PROJ2) KMB_PROJ(1, decode_proj_kernel<2>, 1);
+    else if (route == KMB_DECODE_ROUTE_PROJ4) KMB_PROJ(2, decode_proj_kernel<4>, 1);
     else KMB_PROJ(3, decode_proj_kernel<6>, 1);
 #undef KMB_PROJ
     return hipGetLastError();
   }
-  const bool self = p.kind == 1;
-  const size_t lds = a_bytes + (size_t)RT * ((self ? 3 * HD : HD) + 8) * 2 + (((size_t)RT * p.Tk * sizeof(float) + 15) & ~(size_t)15);
-  const size_t lds_kv = lds + (size_t)KV_ITEMS * p.Tk * (KS + 128 + sizeof(float)) + (size_t)RT * pb_stride(p.Tk) + RT * sizeof(float);
+  const size_t lds = attn_lds(p), lds_kv = attn_lds_kv(p);
   static size_t set_s = 0, set_c = 0, set_l = 0;
-  if (self) {
+  if (route == KMB_DECODE_ROUTE_ATTN_SELF) {
     if (lds > set_s) { e = set_lds(decode_attn_kernel<true, false>, lds); if (e != hipSuccess) return e; set_s = lds; }
     hipLaunchKernelGGL((decode_attn_kernel<true, false>), dim3(unit_grid(p.H, tiles)), dim3(256), lds, stream, p);
-  } else if (p.kv_group >= 4 && KV_ITEMS * p.Tk * 8 <= NKV * 256 && lds_kv <= 160 * 1024) {
+  } else if (route == KMB_DECODE_ROUTE_ATTN_CROSS_KVLDS) {
     if (lds_kv > set_l) { e = set_lds(decode_attn_kernel<false, true>, lds_kv); if (e != hipSuccess) return e; set_l = lds_kv; }
     hipLaunchKernelGGL((decode_attn_kernel<false, true>), dim3(unit_grid(p.H, tiles)), dim3(256), lds_kv, stream, p);
   } else {

@@ -246,6 +246,7 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
     // this step's key / value: attended to from the projection output and appended to the cache by the same launch
     a.new_k = G.L.qkv + d; a.new_v = G.L.qkv + 2 * d; a.ld_new = 3 * d; a.Kw = G.L.kc[l]; a.Vw = G.L.vc[l];
     a.hist = G.L.hist[G.hcur];
+    if (const char* why = kmb_attn_decode_check(a)) return fail("kmb_gen_step: %s", why);
     HIPCHK(kmb_attn_decode_launch(a, s));
     KCHK(proj_ln(G.L.o, d, L.sa.o_w, L.sa.o_b, x, L.sa.ln_g, L.sa.ln_b, G.L.y));
     // cross attention over the cached encoder K|V of the row's batch item
@@ -256,6 +257,7 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
     a.Q = G.L.cq; a.ldq = d; a.Kc = G.L.ckv[l]; a.Vc = G.L.ckv[l] + d; a.Tmax = G.S; a.ldc = h->cfg.decoder_layers * 2 * d; a.kv_row = G.kv_row;
     a.key_mask = G.bt.attention_mask; a.mask_ld = G.S; a.mask_row = G.kv_row;
     a.R = R; a.H = h->Hd; a.Tk = G.S; a.O = G.L.o; a.ldo = d;
+    if (const char* why = kmb_attn_decode_check(a)) return fail("kmb_gen_step: %s", why);
     HIPCHK(kmb_attn_decode_launch(a, s));
     KCHK(proj_ln(G.L.o, d, L.ca.o_w, L.ca.o_b, G.L.y, L.ca.ln_g, L.ca.ln_b, G.L.y));   // in place: a lane rewrites only the chunks it read
     // FFN

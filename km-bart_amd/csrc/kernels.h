@@ -42,12 +42,15 @@ hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream);
 const char* kmb_attn_check(const KmbAttn& p, int backward);
 
 // single-query attention over a KV cache (generation): one query row per (row, head)
+const char* kmb_attn_decode_check(const KmbAttnDecode& p);
 hipError_t kmb_attn_decode_launch(const KmbAttnDecode& p, hipStream_t stream);
 
 // --------------------------------------------------------------- decode.hip
 // fused [LayerNorm ->] projection [-> attention] block of a decode step (R = batch x beams rows)
 const char* kmb_decode_block_check(const KmbDecodeBlock& p);
 hipError_t kmb_decode_block_launch(const KmbDecodeBlock& p, hipStream_t stream);
+// the kernel kmb_decode_block_launch runs for a checked p (KMB_DECODE_ROUTE_*); no GPU call (kmb_debug_decode_route)
+int kmb_decode_block_route(const KmbDecodeBlock& p);
 // packed[i] <- copy of the row-major weight W[i] ([N, K], row stride ld) in the MFMA-fragment order the decode blocks read
 // (N % 16 == 0, K % 64 == 0), n <= 48 matrices in one launch
 hipError_t kmb_decode_pack_launch(const bf16_t* const* W, const int* ld, const int* N, const int* K, bf16_t* const* packed, int n,

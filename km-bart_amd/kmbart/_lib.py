@@ -74,6 +74,10 @@ class KmbDecodeBlock(C.Structure):
                 ("Tmax", i32), ("ldc", i32), ("Tk", i32), ("kv_row", c_p), ("key_mask", c_p), ("mask_ld", i32), ("hist", c_p), ("kv_group", i32)]
 
 
+# kmb_debug_decode_route: the kernel a decode block runs (include/kmbart.h KMB_DECODE_ROUTE_*)
+DECODE_ROUTES = ("proj_wide", "proj2", "proj4", "proj6", "attn_self", "attn_cross", "attn_cross_kvlds")
+
+
 class KmbDrop(C.Structure):
     _fields_ = [("thr16", u32), ("seed", u32), ("scale", f32)]
 
@@ -199,6 +203,7 @@ PROTOTYPES = {
     "kmb_gen_workspace_bytes": (i64, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kmb_gemm_shared_device": (C.c_int, [C.c_int]),
     "kmb_debug_gemm_route": (C.c_int, [C.POINTER(KmbGemm), C.c_int, c_p, C.c_int32]),
+    "kmb_debug_decode_route": (C.c_int, [C.POINTER(KmbDecodeBlock)]),
     "kmb_comm_unique_id": (C.c_int, [c_p]),
     "kmb_comm_init": (C.c_int, [c_p, C.c_int, C.c_int, c_p]),
     "kmb_comm_destroy": (C.c_int, [c_p]),

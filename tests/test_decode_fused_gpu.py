@@ -123,12 +123,13 @@ def test_self_attention_block(R, Tk):
     assert e < 6e-3
 
 
-@pytest.mark.parametrize("B,nb,S,grouped", [(64, 5, 100, True), (64, 5, 100, False), (3, 4, 37, True), (7, 6, 120, True),
+@pytest.mark.parametrize("B,nb,S,grouped", [(64, 5, 100, True), (64, 5, 100, False), (3, 4, 37, True), (7, 6, 120, True), (7, 5, 104, True),
                                             (5, 3, 50, True), (2, 5, 130, True), (140, 5, 100, True), (259, 5, 100, True),
                                             (130, 5, 100, False)])
 def test_cross_attention_block(B, nb, S, grouped):
-    """grouped: kv_group = beams per item (keys / values staged once per item in LDS when the tile allows it);
-    3 beams per item and 130 keys fall back to per-row reads inside the same call."""
+    """grouped: kv_group = beams per item (keys / values staged once per item in LDS when the tile allows it: at least 4 beams per item
+    and at most 104 keys, the last shape whose staging fits 160 KB of LDS); 3 beams per item, 120 keys and 130 keys run the per-row vector
+    kernel inside the same call.  tests/test_decode_attn_gpu.py asserts which kernel each of its cases ran."""
     torch.manual_seed(B + S)
     H, d, R = 12, 768, B * nb
     z = bf(torch.randn(R, d, device=DEV))
