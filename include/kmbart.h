@@ -190,6 +190,9 @@ int64_t kmb_bf16_arena_elems(const kmb_handle* h);   /* bf16 mirror (+ padded ti
 int kmb_bind_arenas(kmb_handle* h, float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                     kmb_bf16* params_bf16, float* final_logits_bias);
 int64_t kmb_workspace_bytes(const kmb_handle* h, int B, int S, int T, int n_features);
+/* ... for a forward with kmb_forward_opts.targets_per_input = G: B inputs of S tokens, B * G targets of T tokens (the encoder side's buffers
+ * have B * S rows, the decoder side's B * G * T).  G <= 1: exactly kmb_workspace_bytes. */
+int64_t kmb_workspace_bytes_grouped(const kmb_handle* h, int B, int S, int T, int n_features, int targets_per_input);
 int kmb_bind_workspace(kmb_handle* h, void* ws, int64_t bytes);
 /* refresh the bf16 mirror from the fp32 master parameters (after init / load_state_dict) */
 int kmb_sync_params(kmb_handle* h, void* stream);
@@ -199,7 +202,9 @@ int kmb_set_seed(kmb_handle* h, uint64_t seed);
  * Only training-mode forwards (train = 1) and their backward draw masks: eval forwards, kmb_score, generation and the fp32 validation mode
  * run without.  kmb_attention_dropout_site reports what the LAST training forward used at a site (kind 0 encoder self-attention, 1 decoder
  * self-attention, 2 decoder cross-attention; zeros when it ran without): probability (b, h, q, k) was kept where
- * kmb_op_dropout_mask(seed, thr16 / 65536, B * H * Tq, Tk) keeps element ((b * H + h) * Tq + q, k). */
+ * kmb_op_dropout_mask(seed, thr16 / 65536, B * H * Tq, Tk) keeps element ((b * H + h) * Tq + q, k).  With targets_per_input = G > 1
+ * (kmb_forward_opts) the decoder self-attention site has B * G items of T x T, and the cross-attention site has B items of Tq = G * T queries
+ * against Tk = S keys: its mask is kmb_op_dropout_mask(seed, thr16 / 65536, B * H * G * T, S), query q = g * T + t of input b. */
 int kmb_set_attention_dropout(kmb_handle* h, float p);
 int kmb_attention_dropout_site(kmb_handle* h, int kind, int layer, uint32_t* thr16, uint32_t* seed);
 /* Activation dropout (the reference's config.activation_dropout: F.dropout on gelu(fc1(x)) of every FFN block).  A run-time setting of the
@@ -287,6 +292,20 @@ typedef struct kmb_forward_opts {
    * without labels is refused.  NULL and loss_reduction 0 run exactly the launches kmb_forward runs. */
   const float* row_weights;         /* [B*T] fp32 on the device, indexed like labels, or NULL */
   int32_t loss_reduction;           /* 0 mean: D = the number of valid labels (NaN without one); 1 sum: D = 1 (exactly 0 without one) */
+  /* Several targets per input, the encoder run once.  0 and 1: one target per input, exactly the launches that ran
+   * without the field.  It sits in what was the struct's tail padding, so sizeof -- and kmb_abi_sizeof_forward_opts -- is unchanged and cannot
+   * tell a caller compiled against the older header from a new one: ZERO THE WHOLE RECORD (memset(&opts, 0, sizeof opts), `kmb_forward_opts o{}`,
+   * `= {0}`) before filling it, as every caller in this repository does.  A record whose fields were assigned one by one on an uninitialised
+   * stack slot now passes whatever the padding held as G; such a value is refused when negative or when G * T > 384, not otherwise.  G > 1: batch->B, S, input_ids, attention_mask and
+   * the features describe B inputs as before; decoder_input_ids, decoder_attention_mask and labels are [B * G, T] with decoder row i belonging to
+   * input i / G (the row order of generate(num_return_sequences = G)); row_weights [B * G * T]; logits_out / kmb_last_logits
+   * [B * G * T, kmb_logits_ld()]; decoder_states_out [B * G * T, d_model]; enc_out and encoder_states stay [B * S, d_model] (kmb_encoder_states_grad
+   * likewise: the gradient summed over an input's G targets).  The decoder's self-attention runs B * G causal items of T x T; cross-attention runs
+   * B items of Tq = G * T queries against the input's S keys, not causal -- at S <= 64 the query-streaming kernels (kmb_debug_attn_route) -- and
+   * its key | value gradient arrives summed over the G targets.  Workspace: kmb_workspace_bytes_grouped.  Refused before any launch: G < 0,
+   * G * T > 384 (the attention backward's query limit), G > 1 in kmb_forward_pretrain*.  kmb_score always scores one target per input, and
+   * kmb_attention_probs is refused after a grouped forward. */
+  int32_t targets_per_input;
 } kmb_forward_opts;
 int kmb_abi_sizeof_forward_opts(void);   /* sizeof(kmb_forward_opts) as the library was compiled (cf. kmb_abi_sizeof_attn) */
 /* kmb_forward with those options.  With encoder_states AND need_grad the following kmb_backward stops at the given states:
@@ -666,6 +685,19 @@ int kmb_debug_gemm_route(const KmbGemm* p, int forced_variant, int32_t* out, int
 #define KMB_DECODE_ROUTE_ATTN_CROSS 5
 #define KMB_DECODE_ROUTE_ATTN_CROSS_KVLDS 6
 int kmb_debug_decode_route(const KmbDecodeBlock* p);
+
+/* Diagnostic: the kernel kmb_op_attn_fwd (backward != 0: kmb_op_attn_bwd) would run for *p, answered by the function the launchers themselves
+ * ask -- no GPU call, the operands are never dereferenced.  General: one (batch, head) item per workgroup (forward: per item and query tile),
+ * any Tq / Tk.  Single-tile: Tq <= 64 and Tk <= 64, persistent over items (forward: from 1024 items on); with Tq, Tk <= 32 and an even head
+ * count two heads share a tile.  Query-streaming: Tq > 64, Tk <= 64, not causal -- several targets per input attending to one input's keys
+ * (forward of the training step with targets_per_input > 1): persistent over items, K / V staged once per item, the item's query tiles walked
+ * with the next tile in flight; at every item count.  The two persistent classes need every tensor below 4 GB.  Returns a negative value for
+ * a problem the operator refuses (a backward with Tq > 384 among them, whichever kernel would run it). */
+#define KMB_ATTN_ROUTE_GENERAL 0
+#define KMB_ATTN_ROUTE_SMALL 1
+#define KMB_ATTN_ROUTE_SMALL_PACK 2
+#define KMB_ATTN_ROUTE_QSTREAM 3
+int kmb_debug_attn_route(const KmbAttn* p, int backward);
 
 /* ================= data parallelism: native RCCL (vcg_train.py:98 DDP, src/utils.py:9-17 init_process_group) =================
  * One process per GPU; the library owns the communicator and a communication stream, and a step's whole gradient

@@ -905,6 +905,430 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_small_kernel(const KmbAttn p)
   }
 }
 
+// ------------------------------------------ query-streaming kernels (Tq > 64, Tk <= 64, not causal: several targets per input)
+// G targets of T tokens that attend to one input's keys are ONE attention problem with Tq = G T contiguous query rows (no causal mask, every
+// query row on its own).  The general kernels take such a shape one item (forward: one item and query tile) per workgroup, reload K / V per
+// query tile and keep dQ in an LDS accumulator.  Here a workgroup is persistent over (batch, head) items as the single-tile kernels are and WALKS
+// the item's ceil(Tq / 64) query tiles: K, V and the 64 key-mask flags go to LDS once per item, the next tile's Q (backward: Q, dO, lse) is in
+// flight in registers while the current tile is computed, and at an item's last tile the next item's K, V, mask and first tile are in flight
+// instead.  Backward: dK / dV stay in the fp32 MFMA accumulators over the item's tiles and are rounded once; dQ leaves per tile from registers;
+// delta = sum_k P dP~ from the registers as in attn_bwd_small_kernel (the saved O is not read).  Every sum has a fixed order: no atomics.
+// Per tile the arithmetic is attn_fwd_small_kernel's / attn_bwd_small_kernel's (PACK = false), operation for operation.
+__device__ __forceinline__ u32x4 ld16(const bf16_t* base, uint32_t elem) {   // 32-bit byte offsets: the launcher checks that every tensor is below 4 GB
+  return *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(base) + elem * 2u);
+}
+// an item's K / V tile and its key-mask words (first wave: key = tid).  Rows 32 .. 63 of a tile of at most 32 keys are never fetched: zeros stay
+__device__ __forceinline__ void qs_load_kv(const KmbAttn& p, int b, int h, int tid, u32x4 (&k)[2], u32x4 (&v)[2], long long& mk) {
+  if (p.key_mask != nullptr && tid < 64) mk = p.key_mask[(uint32_t)b * (uint32_t)p.Tk + (uint32_t)(tid < p.Tk ? tid : p.Tk - 1)];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int id = tid + 256 * i;
+    const int row = id >> 3, c = id & 7;
+    const uint32_t rk = (uint32_t)b * (uint32_t)p.Tk + (uint32_t)(row < p.Tk ? row : p.Tk - 1);
+    const uint32_t hc = (uint32_t)(h * HD + c * 8);
+    if (i == 0 || p.Tk > 32) {
+      k[i] = ld16(p.K, rk * (uint32_t)p.ldk + hc);
+      v[i] = ld16(p.V, rk * (uint32_t)p.ldv + hc);
+    }
+  }
+}
+// query tile t of an item: rows 64 t .. 64 t + 63 of X, clamped to the item's last row
+__device__ __forceinline__ void qs_load_rows(const bf16_t* X, int ld, const KmbAttn& p, int b, int h, int t, int tid, u32x4 (&x)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int id = tid + 256 * i;
+    const int row = t * 64 + (id >> 3), c = id & 7;
+    const uint32_t rq = (uint32_t)b * (uint32_t)p.Tq + (uint32_t)(row < p.Tq ? row : p.Tq - 1);
+    x[i] = ld16(X, rq * (uint32_t)ld + (uint32_t)(h * HD + c * 8));
+  }
+}
+
+constexpr int QS_FWD_GRID = 768;   // three workgroups per CU
+struct QsFwdRegs { u32x4 q[2], k[2], v[2]; long long mk; };
+
+template <bool DROP>
+__global__ __launch_bounds__(256, 3) void attn_fwd_qstream_kernel(const KmbAttn p) {   // (four per CU = 128 registers: the DROP form spilled 23)
+  __shared__ __attribute__((aligned(16))) char smem[3 * TILE_BYTES + 4 * 2048];
+  __shared__ float msk_s[64];   // key-mask flags of the item's 64 keys
+  char* Qs = smem;
+  char* Ks = smem + TILE_BYTES;
+  char* Vs = smem + 2 * TILE_BYTES;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  char* Ps = smem + 3 * TILE_BYTES + wave * 2048;
+  const int nitems = p.B * p.H;
+  const int nt = (p.Tq + 63) >> 6;
+  const bool lse_vec = (p.Tq & 3) == 0 && ((uintptr_t)p.lse & 15) == 0;
+  int item = blockIdx.x;
+  if (item >= nitems) return;
+  QsFwdRegs x;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {   // (masked keys multiply a probability of exactly 0: their rows must be finite)
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    x.q[i] = z; x.k[i] = z; x.v[i] = z;
+  }
+  x.mk = 1;
+  qs_load_kv(p, item / p.H, item % p.H, tid, x.k, x.v, x.mk);
+  qs_load_rows(p.Q, p.ldq, p, item / p.H, item % p.H, 0, tid, x.q);
+  for (; item < nitems; item += gridDim.x) {
+    const int b = item / p.H, h = item % p.H;
+    for (int t = 0; t < nt; ++t) {
+      __syncthreads();   // everyone is done with the previous tile's Q image (t = 0: with the previous item's K / V images)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int id = tid + 256 * i;
+        const int row = id >> 3, c = id & 7;
+        *reinterpret_cast<u32x4*>(Qs + tile_off(row, c)) = x.q[i];
+        if (t == 0) {
+          *reinterpret_cast<u32x4*>(Ks + tile_off(row, c)) = x.k[i];
+          *reinterpret_cast<u32x4*>(Vs + tile_off(row, c)) = x.v[i];
+        }
+      }
+      if (t == 0 && tid < 64) msk_s[tid] = x.mk != 0 ? 1.f : 0.f;
+      __syncthreads();
+      bool key_on[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) key_on[j] = msk_s[j * 16 + r] != 0.f;
+      // the next loads go out now and land while this tile is computed: the item's next Q tile, or the next item's K / V / first Q tile
+      if (t + 1 < nt) {
+        qs_load_rows(p.Q, p.ldq, p, b, h, t + 1, tid, x.q);
+      } else {
+        const int nxt = item + (int)gridDim.x;
+        if (nxt < nitems) {
+          qs_load_kv(p, nxt / p.H, nxt % p.H, tid, x.k, x.v, x.mk);
+          qs_load_rows(p.Q, p.ldq, p, nxt / p.H, nxt % p.H, 0, tid, x.q);
+        }
+      }
+      const int q0 = t * 64 + wave * 16;   // this wave's first query row of the item
+      if (q0 >= p.Tq) continue;            // wave-uniform: no query rows in the last tile (both barriers are at the loop head)
+      f32x4 s[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 qf = frag_rows(Qs, wave, kk, r, g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, frag_rows(Ks, j, kk, r, g), s[j], 0, 0, 0);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool kv = j * 16 + r < p.Tk && key_on[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[j][q] = kv ? s[j][q] : -INFINITY;
+      }
+      float m_run[4], l_run[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float mx = fmaxf(fmaxf(s[0][q], s[1][q]), fmaxf(s[2][q], s[3][q]));
+        mx = group16_max(mx);
+        float lsum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float pv = (mx == -INFINITY) ? 0.f : __expf(s[j][q] - mx);
+          s[j][q] = pv;
+          lsum += pv;
+        }
+        l_run[q] = lsum;
+        m_run[q] = mx;
+      }
+      if constexpr (DROP) {   // logical coordinates: row (b H + h) Tq + q with q the query's position in the item, column = key
+        const uint32_t rt0 = (((uint32_t)b * (uint32_t)p.H + (uint32_t)h) * (uint32_t)p.Tq + (uint32_t)(q0 + g * 4)) * DROP_ROW_MUL;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t cs = drop_colterm((uint32_t)(j * 16 + r)) ^ p.drop_seed;
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            s[j][q] = attn_keep(rt0 + (uint32_t)q * DROP_ROW_MUL, cs, r & 1, p.drop_thr16) ? s[j][q] * p.drop_scale : 0.f;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *reinterpret_cast<bf16_t*>(Ps + elem_off(g * 4 + q, j * 16 + r)) = f2bf(s[j][q]);
+      // Ps is this wave's own: its LDS operations execute in order, a wave-level fence keeps the compiler from moving the reads up
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      f32x4 o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 pf = frag_rows(Ps, 0, kk, r, g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, frag_cols(Vs, j, kk, r, g), o[j], 0, 0, 0);
+      }
+      // O leaves through the wave's own P image, whole 128-byte rows (as in attn_fwd_small_kernel)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      f32x4 lv;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float l = group16_sum(l_run[q]);
+        const float inv = l > 0.f ? 1.f / l : 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<bf16_t*>(Ps + elem_off(g * 4 + q, j * 16 + r)) = f2bf(o[j][q] * inv);
+        lv[q] = l > 0.f ? m_run[q] + __logf(l) : -INFINITY;
+      }
+      if (r == 0 && p.lse != nullptr) {
+        const int qi = q0 + g * 4;
+        float* dst = p.lse + ((size_t)b * p.H + h) * p.Tq + qi;
+        if (lse_vec) {
+          if (qi < p.Tq) *reinterpret_cast<f32x4*>(dst) = lv;
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (qi + q < p.Tq) dst[q] = lv[q];
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int lr = (lane >> 3) + 8 * i, c = lane & 7;
+        const int qi = q0 + lr;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(Ps + tile_off(lr, c));
+        if (qi < p.Tq) *reinterpret_cast<u32x4*>(p.O + ((size_t)b * p.Tq + qi) * p.ldo + h * HD + c * 8) = v;
+      }
+    }
+  }
+}
+
+constexpr int QS_BWD_GRID = 512;   // two workgroups per CU
+struct QsBwdRegs { u32x4 q[2], d[2], k[2], v[2]; float lse; long long mk; };   // lse, mk: row / key `tid` of the tile, threads 0 .. 63 only
+
+__device__ __forceinline__ void qs_bwd_load_tile(const KmbAttn& p, int b, int h, int t, int tid, QsBwdRegs& x) {
+  qs_load_rows(p.Q, p.ldq, p, b, h, t, tid, x.q);
+  qs_load_rows(p.dO, p.lddo, p, b, h, t, tid, x.d);
+  if (tid < 64) {
+    const int q = t * 64 + tid;
+    x.lse = p.lse[((uint32_t)b * (uint32_t)p.H + (uint32_t)h) * (uint32_t)p.Tq + (uint32_t)(q < p.Tq ? q : p.Tq - 1)];
+  }
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_bwd_qstream_kernel(const KmbAttn p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Qs = smem;
+  char* dOs = smem + TILE_BYTES;
+  char* Ks = smem + 2 * TILE_BYTES;
+  char* Vs = smem + 3 * TILE_BYTES;
+  char* Ps = smem + 4 * TILE_BYTES;
+  char* dSs = smem + 5 * TILE_BYTES;
+  float* lse_s = reinterpret_cast<float*>(smem + 6 * TILE_BYTES);
+  float* msk_s = lse_s + 64;   // key-mask flags of the item's 64 keys
+  float* colq = msk_s + 64;    // [4 waves][64] column sums of dQ / dK / dV over each wave's rows (bias-gradient partials)
+  float* colk = colq + 256;
+  float* colv = colk + 256;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int nitems = p.B * p.H;
+  const int nt = (p.Tq + 63) >> 6;
+  auto row16_sum = [](float v) {   // inclusive prefix sums by row_shr 1, 2, 4, 8 (zeros shifted in): lane 15 = total
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, true));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, true));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, true));
+    return v;
+  };
+  int item = blockIdx.x;
+  if (item >= nitems) return;
+  QsBwdRegs x;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) x.q[i] = x.d[i] = x.k[i] = x.v[i] = u32x4{0u, 0u, 0u, 0u};
+  x.lse = 0.f;
+  x.mk = 1;
+  qs_load_kv(p, item / p.H, item % p.H, tid, x.k, x.v, x.mk);
+  qs_bwd_load_tile(p, item / p.H, item % p.H, 0, tid, x);
+  int prev_b = -1, prev_h = 0;   // the item whose column-sum partials are complete but not yet written
+  auto write_colsums = [&]() {   // 64 threads: the four waves' partials of the previous item -> its row of the bias-gradient partials
+    const size_t o = (size_t)prev_b * p.ld_colsum + prev_h * HD + tid;
+    if (p.dq_colsum != nullptr) p.dq_colsum[o] = (colq[tid] + colq[64 + tid]) + (colq[128 + tid] + colq[192 + tid]);
+    p.dk_colsum[o] = (colk[tid] + colk[64 + tid]) + (colk[128 + tid] + colk[192 + tid]);
+    p.dv_colsum[o] = (colv[tid] + colv[64 + tid]) + (colv[128 + tid] + colv[192 + tid]);
+  };
+  f32x4 dk[4], dv[4];   // this wave's 16 keys, transposed tiles: they live across the item's query tiles
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { dk[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (; item < nitems; item += gridDim.x) {
+    const int b = item / p.H, h = item % p.H;
+    for (int t = 0; t < nt; ++t) {
+      __syncthreads();   // everyone is done with the previous tile's LDS images (t = 0: the previous item's column-sum partials are complete)
+      // the previous item's column sums leave behind THIS barrier; the partials are next written at the end of this iteration, two barriers on
+      if (t == 0 && p.dk_colsum != nullptr && prev_b >= 0 && tid < 64) write_colsums();
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int id = tid + 256 * i;
+        const int row = id >> 3, c = id & 7;
+        *reinterpret_cast<u32x4*>(Qs + tile_off(row, c)) = x.q[i];
+        *reinterpret_cast<u32x4*>(dOs + tile_off(row, c)) = x.d[i];
+        if (t == 0) {
+          *reinterpret_cast<u32x4*>(Ks + tile_off(row, c)) = x.k[i];
+          *reinterpret_cast<u32x4*>(Vs + tile_off(row, c)) = x.v[i];
+        }
+      }
+      if (tid < 64) {
+        lse_s[tid] = x.lse;
+        if (t == 0) msk_s[tid] = x.mk != 0 ? 1.f : 0.f;
+      }
+      __syncthreads();
+      bool key_on[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) key_on[j] = msk_s[j * 16 + r] != 0.f;
+      // ---- the next loads go out now: the item's next Q / dO / lse tile, or the next item's K / V / mask and first tile ----
+      if (t + 1 < nt) {
+        qs_bwd_load_tile(p, b, h, t + 1, tid, x);
+      } else {
+        const int nxt = item + (int)gridDim.x;
+        if (nxt < nitems) {
+          qs_load_kv(p, nxt / p.H, nxt % p.H, tid, x.k, x.v, x.mk);
+          qs_bwd_load_tile(p, nxt / p.H, nxt % p.H, 0, tid, x);
+        }
+      }
+      // ---- S = Q K^T and dP = dO V^T for this wave's 16 query rows x 64 keys ----
+      f32x4 s4[4], dp[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { s4[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 qf = frag_rows(Qs, wave, kk, r, g);
+        const bf16x8 df = frag_rows(dOs, wave, kk, r, g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          s4[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, frag_rows(Ks, j, kk, r, g), s4[j], 0, 0, 0);
+          dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, frag_rows(Vs, j, kk, r, g), dp[j], 0, 0, 0);
+        }
+      }
+      const int lrow0 = wave * 16 + g * 4;   // this lane's four query rows inside the tile; t * 64 + lrow0 inside the item
+      const float lse4[4] = {lse_s[lrow0], lse_s[lrow0 + 1], lse_s[lrow0 + 2], lse_s[lrow0 + 3]};
+      float del4[4] = {0.f, 0.f, 0.f, 0.f};
+      [[maybe_unused]] uint32_t kbits = 0u;   // DROP: bit 4 j + q = element [j][q] was kept
+      [[maybe_unused]] uint32_t rt0 = 0u;
+      if constexpr (DROP) rt0 = (((uint32_t)b * (uint32_t)p.H + (uint32_t)h) * (uint32_t)p.Tq + (uint32_t)(t * 64 + lrow0)) * DROP_ROW_MUL;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int key = j * 16 + r;
+        const bool kv = key < p.Tk && key_on[j];
+        [[maybe_unused]] uint32_t cs = 0u;
+        if constexpr (DROP) cs = drop_colterm((uint32_t)key) ^ p.drop_seed;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bool ok = kv && t * 64 + lrow0 + q < p.Tq;
+          const float pvq = (ok && lse4[q] != -INFINITY) ? __expf(s4[j][q] - lse4[q]) : 0.f;
+          s4[j][q] = pvq;
+          if constexpr (DROP) {   // dP~
+            const bool keep = attn_keep(rt0 + (uint32_t)q * DROP_ROW_MUL, cs, r & 1, p.drop_thr16);
+            dp[j][q] = keep ? dp[j][q] * p.drop_scale : 0.f;
+            kbits |= keep ? (1u << (j * 4 + q)) : 0u;
+          }
+          del4[q] += pvq * dp[j][q];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {   // the row's keys sit in the 16 lanes of a DPP row: four rotate-and-add steps leave the total in every lane
+        float v = del4[q];
+        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));   // row_ror:8
+        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));   // row_ror:4
+        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));   // row_ror:2
+        v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));   // row_ror:1
+        del4[q] = v;
+      }
+      // P and dS go to LDS TRANSPOSED ([key][query]), eight contiguous bytes per lane and MFMA tile (attn_bwd_small_kernel)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int key = j * 16 + r;
+        float ds[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ds[q] = s4[j][q] * (dp[j][q] - del4[q]);
+        if constexpr (DROP) {   // P~ for dV: what the forward multiplied V by
+#pragma unroll
+          for (int q = 0; q < 4; ++q) s4[j][q] = ((kbits >> (j * 4 + q)) & 1u) ? s4[j][q] * p.drop_scale : 0.f;
+        }
+        const int off = elem_off(key, lrow0);
+        *reinterpret_cast<uint2*>(Ps + off) = uint2{pack2bf(s4[j][0], s4[j][1]), pack2bf(s4[j][2], s4[j][3])};
+        *reinterpret_cast<uint2*>(dSs + off) = uint2{pack2bf(ds[0], ds[1]), pack2bf(ds[2], ds[3])};
+      }
+      __syncthreads();
+      // ---- dQ^T of this tile; dV^T, dK^T accumulate over the item's tiles: lane (r, g) holds row r of this wave's 16, columns 16 j + 4 g .. + 3 ----
+      f32x4 dq[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 dsf = frag_cols(dSs, wave, kk, r, g);    // rows = this wave's query rows (image columns), k = keys (image rows)
+        const bf16x8 ptf = frag_rows(Ps, wave, kk, r, g);     // rows = this wave's keys (image rows), k = query rows
+        const bf16x8 dstf = frag_rows(dSs, wave, kk, r, g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          dq[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Ks, j, kk, r, g), dsf, dq[j], 0, 0, 0);
+          dv[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(dOs, j, kk, r, g), ptf, dv[j], 0, 0, 0);
+          dk[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_cols(Qs, j, kk, r, g), dstf, dk[j], 0, 0, 0);
+        }
+      }
+      const int row = wave * 16 + r;   // query row of dQ inside the tile, key row of dK / dV
+      const bool last = t + 1 == nt;
+      if (p.dk_colsum != nullptr) {   // uniform branch.  dQ: each wave's partial is summed over the item's tiles in tile order
+        const bool q_ok = t * 64 + row < p.Tq, k_ok = row < p.Tk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float sq = row16_sum(q_ok ? dq[j][q] * p.dq_scale : 0.f);
+            const int ci = wave * 64 + j * 16 + g * 4 + q;
+            if (r == 15) colq[ci] = t == 0 ? sq : colq[ci] + sq;   // this lane's own slot: plain read-modify-write
+            if (last) {   // from the fp32 accumulators, before rounding
+              const float sk = row16_sum(k_ok ? dk[j][q] : 0.f);
+              const float sv = row16_sum(k_ok ? dv[j][q] : 0.f);
+              if (r == 15) { colk[ci] = sk; colv[ci] = sv; }
+            }
+          }
+      }
+      // Results leave through this wave's 16 rows of the P image: after the MFMAs above only this wave reads them (frag_rows(Ps, wave)), the other
+      // waves write them next behind the two barriers at the head of the next tile; 16 rows x 64 columns are one result tile of the wave.  (K / V
+      // stay staged for the item's next tile, so the V image attn_bwd_small_kernel uses is not free here.)
+      auto out_tile = [&](const f32x4 (&tt)[4], float scale, bf16_t* base, uint32_t ld, int row0, int T) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          *reinterpret_cast<uint2*>(Ps + elem_off(row, j * 16 + g * 4)) = uint2{pack2bf(tt[j][0] * scale, tt[j][1] * scale), pack2bf(tt[j][2] * scale, tt[j][3] * scale)};
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the rows are this wave's own: no workgroup barrier
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int lrow = wave * 16 + (lane >> 3) + 8 * i, c = lane & 7;
+          const int rl = row0 + lrow;
+          const u32x4 v = *reinterpret_cast<const u32x4*>(Ps + tile_off(lrow, c));
+          if (rl < T)
+            *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(base) + (((uint32_t)b * (uint32_t)T + (uint32_t)rl) * ld + (uint32_t)(h * HD + c * 8)) * 2u) = v;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the next tile overwrites the rows just read)
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      };
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the P fragments have been read
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      out_tile(dq, p.dq_scale, p.dQ, (uint32_t)p.lddq, t * 64, p.Tq);
+      if (last) {   // the item's dK / dV: rounded once
+        out_tile(dk, 1.f, p.dK, (uint32_t)p.lddk, 0, p.Tk);
+        out_tile(dv, 1.f, p.dV, (uint32_t)p.lddv, 0, p.Tk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { dk[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        prev_b = b; prev_h = h;
+      }
+    }
+  }
+  if (p.dk_colsum != nullptr && prev_b >= 0) {   // the last item's column sums
+    __syncthreads();
+    if (tid < 64) write_colsums();
+  }
+}
+
 // ------------------------------------------------- single-query decode step
 // one wave per (row, head): scores over the cached keys, softmax, weighted sum of cached values
 __global__ __launch_bounds__(256) void attn_decode_kernel(const KmbAttnDecode p) {
@@ -1013,16 +1437,39 @@ const char* kmb_attn_check(const KmbAttn& p, int backward) {
   return nullptr;
 }
 
-hipError_t kmb_attn_fwd_launch(const KmbAttn& p, hipStream_t stream) {
-  const bool drop = p.drop_thr16 != 0u;   // attention dropout: the DROP instantiations
-  static const bool small_ok = !(KMB_DIAG_ENV("KMB_ATTN_FWD_SMALL") && KMB_DIAG_ENV("KMB_ATTN_FWD_SMALL")[0] == '0');
-  // (the single-tile kernel's 32-bit byte offsets: every tensor below 4 GB)
+// Which kernel the launchers below run for a checked problem (KMB_ATTN_ROUTE_*): pure host code, no GPU call (kmb_debug_attn_route).
+// The single-tile and the query-streaming kernels address with 32-bit byte offsets: every tensor they touch must stay below 4 GB (fits32).
+int kmb_attn_route(const KmbAttn& p, int backward) {
+  static const bool qstream_ok = !(KMB_DIAG_ENV("KMB_ATTN_QSTREAM") && KMB_DIAG_ENV("KMB_ATTN_QSTREAM")[0] == '0');
+  static const bool fwd_small_ok = !(KMB_DIAG_ENV("KMB_ATTN_FWD_SMALL") && KMB_DIAG_ENV("KMB_ATTN_FWD_SMALL")[0] == '0');
+  static const bool bwd_small_ok = !(KMB_DIAG_ENV("KMB_ATTN_BWD_SMALL") && KMB_DIAG_ENV("KMB_ATTN_BWD_SMALL")[0] == '0');
+  static const bool pack_ok = !(KMB_DIAG_ENV("KMB_ATTN_PACK") && KMB_DIAG_ENV("KMB_ATTN_PACK")[0] == '0');
   int ld_max = p.ldq;
   for (int l : {p.ldk, p.ldv, p.ldo}) ld_max = l > ld_max ? l : ld_max;
+  if (backward)
+    for (int l : {p.lddo, p.lddq, p.lddk, p.lddv}) ld_max = l > ld_max ? l : ld_max;
   const bool fits32 = (size_t)p.B * (size_t)(p.Tq > p.Tk ? p.Tq : p.Tk) * (size_t)ld_max * 2 < ((size_t)1 << 32);
-  if (small_ok && p.Tq <= 64 && p.Tk <= 64 && p.B * p.H >= 1024 && fits32) {   // one query tile, one key tile, enough items to pipeline
-    static const bool pack_ok = !(KMB_DIAG_ENV("KMB_ATTN_PACK") && KMB_DIAG_ENV("KMB_ATTN_PACK")[0] == '0');
-    const bool pack = pack_ok && p.Tq <= 32 && p.Tk <= 32 && (p.H & 1) == 0;   // two heads per tile (32-token self-attention)
+  // several query tiles against one key tile, no causal mask: the query-streaming kernels, at every item count
+  if (qstream_ok && p.Tq > 64 && p.Tk <= 64 && !p.causal && fits32) return KMB_ATTN_ROUTE_QSTREAM;
+  // one query tile, one key tile: the persistent, software-pipelined form (forward: with enough items to pipeline)
+  const bool small = backward ? bwd_small_ok : (fwd_small_ok && p.B * p.H >= 1024);
+  if (small && p.Tq <= 64 && p.Tk <= 64 && fits32)
+    return (pack_ok && p.Tq <= 32 && p.Tk <= 32 && (p.H & 1) == 0) ? KMB_ATTN_ROUTE_SMALL_PACK : KMB_ATTN_ROUTE_SMALL;   // two heads per tile (32-token self-attention)
+  return KMB_ATTN_ROUTE_GENERAL;
+}
+
+hipError_t kmb_attn_fwd_launch(const KmbAttn& p, hipStream_t stream) {
+  const bool drop = p.drop_thr16 != 0u;   // attention dropout: the DROP instantiations
+  const int route = kmb_attn_route(p, 0);
+  if (route == KMB_ATTN_ROUTE_QSTREAM) {
+    const int items = p.B * p.H;
+    const dim3 grid(items < QS_FWD_GRID ? items : QS_FWD_GRID);
+    if (drop) hipLaunchKernelGGL(attn_fwd_qstream_kernel<true>, grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(attn_fwd_qstream_kernel<false>, grid, dim3(256), 0, stream, p);
+    return hipGetLastError();
+  }
+  if (route == KMB_ATTN_ROUTE_SMALL || route == KMB_ATTN_ROUTE_SMALL_PACK) {
+    const bool pack = route == KMB_ATTN_ROUTE_SMALL_PACK;
     const int items = pack ? p.B * (p.H >> 1) : p.B * p.H;
     const dim3 grid(items < 1024 ? items : 1024);   // four workgroups per CU
     if (drop) {
@@ -1043,26 +1490,28 @@ hipError_t kmb_attn_fwd_launch(const KmbAttn& p, hipStream_t stream) {
 hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream) {
   const bool drop = p.drop_thr16 != 0u;   // attention dropout: the DROP instantiations
   const int nqt = (p.Tq + 63) / 64;
-  static const bool small_ok = !(KMB_DIAG_ENV("KMB_ATTN_BWD_SMALL") && KMB_DIAG_ENV("KMB_ATTN_BWD_SMALL")[0] == '0');
-  // (its 32-bit byte offsets: every tensor below 4 GB)
-  const size_t rows_max = (size_t)p.B * (size_t)(p.Tq > p.Tk ? p.Tq : p.Tk);
-  int ld_max = p.ldq;
-  for (int l : {p.ldk, p.ldv, p.ldo, p.lddo, p.lddq, p.lddk, p.lddv}) ld_max = l > ld_max ? l : ld_max;
-  const bool fits32 = rows_max * (size_t)ld_max * 2 < ((size_t)1 << 32);
-  if (small_ok && p.Tq <= 64 && p.Tk <= 64 && fits32) {   // one query tile, one key tile: the persistent, software-pipelined form
+  const int route = kmb_attn_route(p, 1);
+  if (route != KMB_ATTN_ROUTE_GENERAL) {   // the persistent, software-pipelined forms: one LDS layout
     const size_t lds_s = 6 * TILE_BYTES + (128 + 768) * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
       hipError_t e = hipSuccess;
       for (const void* f : {(const void*)attn_bwd_small_kernel<false, false>, (const void*)attn_bwd_small_kernel<true, false>,
-                            (const void*)attn_bwd_small_kernel<false, true>, (const void*)attn_bwd_small_kernel<true, true>})
+                            (const void*)attn_bwd_small_kernel<false, true>, (const void*)attn_bwd_small_kernel<true, true>,
+                            (const void*)attn_bwd_qstream_kernel<false>, (const void*)attn_bwd_qstream_kernel<true>})
         if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
       if (e != hipSuccess) return e;
       attr_set = true;
     }
+    if (route == KMB_ATTN_ROUTE_QSTREAM) {
+      const int items = p.B * p.H;
+      const int grid = items < QS_BWD_GRID ? items : QS_BWD_GRID;
+      if (drop) hipLaunchKernelGGL(attn_bwd_qstream_kernel<true>, dim3(grid), dim3(256), lds_s, stream, p);
+      else hipLaunchKernelGGL(attn_bwd_qstream_kernel<false>, dim3(grid), dim3(256), lds_s, stream, p);
+      return hipGetLastError();
+    }
     // two heads per tile for the 32-token self-attention shapes (KMB_ATTN_PACK=0 in the diagnostic build: one head per tile, as before round 5)
-    static const bool pack_ok = !(KMB_DIAG_ENV("KMB_ATTN_PACK") && KMB_DIAG_ENV("KMB_ATTN_PACK")[0] == '0');
-    const bool pack = pack_ok && p.Tq <= 32 && p.Tk <= 32 && (p.H & 1) == 0;
+    const bool pack = route == KMB_ATTN_ROUTE_SMALL_PACK;
     const int items = pack ? p.B * (p.H >> 1) : p.B * p.H;
     const int grid = items < 768 ? items : 768;   // three workgroups per CU (165 VGPRs, 52.6 KB of LDS each)
     if (drop) {

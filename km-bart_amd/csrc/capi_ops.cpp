@@ -524,6 +524,10 @@ int kmb_debug_decode_route(const KmbDecodeBlock* p) {
   if (!p || kmb_decode_block_check(*p) != nullptr) return -1;
   return kmb_decode_block_route(*p);
 }
+int kmb_debug_attn_route(const KmbAttn* p, int backward) {
+  if (!p || kmb_attn_check(*p, backward != 0) != nullptr) return -1;
+  return kmb_attn_route(*p, backward != 0);
+}
 int kmb_beam_merge(const float* val, const int32_t* idx, int B, int num_beams, int k, int V, int32_t* out, void* stream) {
   return hipfail(kmb_beam_merge_launch(val, idx, B, num_beams, k, V, out, -1, nullptr, nullptr, nullptr, (hipStream_t)stream), "beam_merge");
 }

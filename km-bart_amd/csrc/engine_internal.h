@@ -192,6 +192,7 @@ struct kmb_handle {
   // ---- state of the last forward (consumed by backward)
   kmb_batch bt{}; bool have_fwd = false; bool fwd_train = false; bool have_bwd = false;
   int Me = 0, Md = 0, Ntot = 0;
+  int tpi = 1;                      // targets per input of the last forward (kmb_forward_opts.targets_per_input): Md = bt.B * tpi * bt.T
   kmbi::TrainLayout tl;             // where the last forward's activations and backward's buffers are
   int32_t* status = nullptr;        // the status word of the last forward / generate (tl.status or gen.L.status): kmb_read_status*
   hipStream_t side = nullptr; bool side_on = true;

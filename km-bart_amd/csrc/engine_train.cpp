@@ -47,10 +47,12 @@ size_t parts_floats(const kmb_handle* h, int Mmax, int B) {
 }
 
 // ------------------------------------------------------------------ workspace layout (training)
-// With base == nullptr this only measures.
-size_t layout_train(const kmb_handle* h, char* base, size_t cap, int B, int S, int T, int Ntot, TrainLayout* out) {
+// With base == nullptr this only measures.  Bd: the decoder's batch, B inputs x targets per input -- the decoder's row count Md = Bd * T is
+// independent of the encoder's Me = B * S (the log-sum-exps of both decoder attentions have Bd * Hd * T entries either way: cross-attention
+// runs B items of Tq = (Bd / B) * T).
+size_t layout_train(const kmb_handle* h, char* base, size_t cap, int B, int Bd, int S, int T, int Ntot, TrainLayout* out) {
   const int d = h->d, Fe = h->Fe, Fd = h->Fd;
-  const size_t Me = (size_t)B * S, Md = (size_t)B * T;
+  const size_t Me = (size_t)B * S, Md = (size_t)Bd * T;
   const size_t Mmax = Me > Md ? Me : Md;
   const int Le = h->cfg.encoder_layers, Ld = h->cfg.decoder_layers;
   Bump bp(base, cap);
@@ -87,7 +89,7 @@ size_t layout_train(const kmb_handle* h, char* base, size_t cap, int B, int S, i
     a.y1 = bp.act(Md * d); a.cq = bp.act(Md * d); a.ckv = EP(L.ckv_all, (size_t)l * 2 * d);
     a.o2 = bp.act(Md * d); a.z2 = bp.act(Md * d); a.y2 = bp.act(Md * d);
     a.u = bp.act(Md * Fd); a.hh = bp.act(Md * Fd); a.z3 = bp.act(Md * d);
-    a.lse1 = bp.take<float>((size_t)B * h->Hd * T); a.lse2 = bp.take<float>((size_t)B * h->Hd * T);
+    a.lse1 = bp.take<float>((size_t)Bd * h->Hd * T); a.lse2 = bp.take<float>((size_t)Bd * h->Hd * T);
     a.m1 = bp.take<float>(Md); a.r1 = bp.take<float>(Md); a.m2 = bp.take<float>(Md); a.r2 = bp.take<float>(Md);
     a.m3 = bp.take<float>(Md); a.r3 = bp.take<float>(Md);
   }
@@ -122,10 +124,10 @@ size_t layout_train(const kmb_handle* h, char* base, size_t cap, int B, int S, i
     bb.du = bp.act(Mmax * Fmax);
     bb.dqkv = bp.act(Mmax * 3 * d);
     bb.dcq = bp.act(Md * d);
-    for (int site = 0; site < 6; ++site) bb.parts[site] = bp.take<float>(parts_floats(h, (int)Mmax, B));
+    for (int site = 0; site < 6; ++site) bb.parts[site] = bp.take<float>(parts_floats(h, (int)Mmax, Bd));
   }
   L.dob = bp.act(Mmax * d); L.denc = bp.act(Me * d);
-  L.parts = bp.take<float>(parts_floats(h, (int)Mmax, B));
+  L.parts = bp.take<float>(parts_floats(h, (int)Mmax, Bd));
   L.losses5 = bp.take<float>(8);
   // pre-training head scratch (only when heads exist and rows were reserved)
   if ((h->head[0].on || h->head[1].on || h->head[2].on) && h->head_rows_cap > 0) {
@@ -564,7 +566,13 @@ extern "C" {
 
 int64_t kmb_workspace_bytes(const kmb_handle* h, int B, int S, int T, int n_features) {
   PrecisionScope scope(h);
-  return (int64_t)layout_train(h, nullptr, 0, B, S, T, n_features, nullptr);
+  return (int64_t)layout_train(h, nullptr, 0, B, B, S, T, n_features, nullptr);
+}
+
+int64_t kmb_workspace_bytes_grouped(const kmb_handle* h, int B, int S, int T, int n_features, int targets_per_input) {
+  PrecisionScope scope(h);
+  const int G = targets_per_input > 1 ? targets_per_input : 1;
+  return (int64_t)layout_train(h, nullptr, 0, B, B * G, S, T, n_features, nullptr);
 }
 
 // --------------------------------------------------------------------------------- forward
@@ -591,17 +599,25 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
   if (row_weights && !bt.labels) return fail("kmb_forward: row_weights weigh the rows' cross-entropy and need labels");
   if (loss_reduction != 0 && loss_reduction != 1) return fail("kmb_forward: loss_reduction must be 0 (mean) or 1 (sum), got %d", loss_reduction);
   if (row_weights && opts->skip_head) return fail("kmb_forward: row_weights with skip_head: there is no loss to weigh");
+  // several targets per input: the decoder tensors hold bt.B * G rows of T tokens, row i belongs to input i / G
+  const int tpi = opts ? opts->targets_per_input : 0;
+  if (tpi < 0) return fail("kmb_forward: targets_per_input must not be negative, got %d", tpi);
+  const int G = tpi > 1 ? tpi : 1;
+  if (G > 1 && extra) return fail("kmb_forward_pretrain: targets_per_input > 1 is not supported by the pre-training forward");
+  if (G > 1 && (long long)G * bt.T > 384)
+    return fail("kmb_forward: targets_per_input * T = %lld > 384: the cross-attention backward takes at most 384 query rows per input", (long long)G * bt.T);
+  if (G > 1 && (long long)bt.B * G > 0x7fffffff / (bt.T > bt.S ? bt.T : bt.S)) return fail("kmb_forward: B * targets_per_input * T does not fit in 31 bits");
   {
     TrainLayout tl;
-    const size_t need = layout_train(h, h->ws, h->ws_bytes, bt.B, bt.S, bt.T, bt.n_features, &tl);
+    const size_t need = layout_train(h, h->ws, h->ws_bytes, bt.B, bt.B * G, bt.S, bt.T, bt.n_features, &tl);
     if (need > h->ws_bytes) return fail("kmb_forward: workspace too small (%zu > %zu bytes)", need, h->ws_bytes);
     h->tl = std::move(tl);
     h->status = h->tl.status;
   }
   if (!h->fp32 && h->tl.small_floats > 1024) { g_small_slab = h->tl.small_slab; g_small_floats = h->tl.small_floats; }
   h->gen.active = false; h->gen.packed_at = nullptr;   // the activations of this forward overwrite the generation workspace
-  const int d = h->d, B = bt.B, S = bt.S, T = bt.T, Me = B * S, Md = B * T;
-  h->bt = bt; h->Me = Me; h->Md = Md; h->Ntot = bt.n_features;
+  const int d = h->d, B = bt.B, S = bt.S, T = bt.T, Bd = B * G, Me = B * S, Md = Bd * T;
+  h->bt = bt; h->Me = Me; h->Md = Md; h->Ntot = bt.n_features; h->tpi = G;
   h->fwd_train = train != 0; h->have_fwd = false; h->have_hdec = false; h->have_bwd = false;
   h->enc_given = enc_in != nullptr;
   if (train) {
@@ -635,13 +651,14 @@ static int forward_impl(kmb_handle* h, const kmb_batch* batch, const kmb_pretrai
   for (int l = 0; l < h->cfg.decoder_layers; ++l) {
     const LayerP& L = h->dec[l];
     DecAct& a = h->tl.da[l];
-    KCHK(self_attn_forward(h, L.sa, h->Hd, h->tl.xd[l], a.qkv, a.o1, a.lse1, a.z1, a.m1, a.r1, a.y1, B, T,
+    KCHK(self_attn_forward(h, L.sa, h->Hd, h->tl.xd[l], a.qkv, a.o1, a.lse1, a.z1, a.m1, a.r1, a.y1, Bd, T,
                            bt.decoder_attention_mask, 1, h->drop_site(100 + 3 * l, tr), h->attn_drop_site(1, l, tr), s));
     // cross attention: q from decoder states (scaled), k|v from the encoder output
     KmbGemm g = lin_fwd(a.y1, d, h->wb(L.ca.qkv_w), h->pf(L.ca.qkv_b), Md, d, d);
     g.col_scale = 0.125f; g.col_scale_n = d; g.out_bf16 = a.cq; g.ld_out_bf16 = d;
     KCHK(run_gemm(g, s));
-    AttnIO io{a.cq, d, a.ckv, EP(a.ckv, d), ldkv, T, S, bt.attention_mask, 0};
+    // (an input's G targets are G * T contiguous query rows, cross-attention is not causal: ONE item of Tq = G * T per input)
+    AttnIO io{a.cq, d, a.ckv, EP(a.ckv, d), ldkv, G * T, S, bt.attention_mask, 0};
     KCHK(attn_forward(h, io, B, h->Hd, a.o2, a.lse2, h->attn_drop_site(2, l, tr), s));
     const KmbDrop dr = h->drop_site(101 + 3 * l, tr);
     g = lin_fwd(a.o2, d, h->wb(L.ca.o_w), h->pf(L.ca.o_b), Md, d, d);
@@ -795,6 +812,7 @@ int kmb_encoder_states_grad(kmb_handle* h, kmb_bf16* out, void* stream) {
 int kmb_attention_probs(kmb_handle* h, int which, int layer, float* out, void* stream) {
   if (!h->have_hdec) return fail("kmb_attention_probs: no forward whose activations are still in the workspace");
   if (h->fp32) return fail("kmb_attention_probs: not available in the fp32 validation mode");
+  if (h->tpi > 1) return fail("kmb_attention_probs: not available after a forward with targets_per_input > 1");
   const int d = h->d, B = h->bt.B;
   if (which == 0) {
     if (layer < 0 || layer >= (int)h->tl.ea.size()) return fail("kmb_attention_probs: layer out of range");
@@ -868,7 +886,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
     h->wg_pending.clear();
   }
   const kmb_batch& bt = h->bt;
-  const int d = h->d, B = bt.B, S = bt.S, T = bt.T, Me = h->Me, Md = h->Md;
+  const int d = h->d, B = bt.B, S = bt.S, T = bt.T, G = h->tpi, Bd = B * G, Me = h->Me, Md = h->Md;
   const bool tr = h->fwd_train;
   const float scale = h->cfg.scale_embedding ? sqrtf((float)d) : 1.f;
   const int Le = h->cfg.encoder_layers, Ld = h->cfg.decoder_layers;
@@ -954,7 +972,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
       KCHK(run_gemm(g, s));
       const int ldkv = Ld * 2 * d;
       bf16_t* dkv = h->tl.dckv_all + (size_t)l * 2 * d;   // this layer's columns of the batched k | v gradient
-      AttnIO io{a.cq, d, a.ckv, a.ckv + d, ldkv, T, S, bt.attention_mask, 0};
+      AttnIO io{a.cq, d, a.ckv, a.ckv + d, ldkv, G * T, S, bt.attention_mask, 0};   // dK | dV: summed over the input's G targets in the kernel
       KCHK(attn_backward(h, io, B, h->Hd, a.o2, a.lse2, h->tl.dob, bb.dcq, d, dkv, dkv + d, ldkv, bb.parts[5],
                          bb.parts[5] + d, bb.parts[5] + 2 * d, 3 * d, h->attn_drop_used(2, l, tr), s));
       // bias gradients from the attention kernel's per-batch-item column sums [B][q | k | v]: q's bias lives in the layer,
@@ -968,7 +986,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
       KCHK(run_gemm(g, s));
       KCHK(trace("ca.t1", t1, (size_t)Md * d * 2, s));
     }
-    KCHK(self_attn_backward(h, L.sa, h->Hd, h->tl.xd[l], a.qkv, a.o1, a.lse1, a.z1, a.m1, a.r1, t1, t0, B, T,
+    KCHK(self_attn_backward(h, L.sa, h->Hd, h->tl.xd[l], a.qkv, a.o1, a.lse1, a.z1, a.m1, a.r1, t1, t0, Bd, T,
                             bt.decoder_attention_mask, 1, h->drop_site(100 + 3 * l, tr), h->attn_drop_used(1, l, tr), bb, s));
     dy = t0;  // t0 now holds d(loss)/d(xd[l]); keep it as the input of the next iteration
     cur ^= 1;  // next iteration writes its first result into the other buffer
@@ -995,7 +1013,7 @@ static int backward_impl(kmb_handle* h, float loss_scale, const float* loss_scal
   }
   HIPCHK(kmb_embed_bwd_launch(h->tl.dz, bt.decoder_input_ids, nullptr, scale, h->gf(h->shared), nullptr,
                               h->cfg.pad_token_id, Md, d, s));
-  HIPCHK(kmb_pos_bwd_launch(h->tl.dz, B, T, d, h->gf(h->dec_pos), h->cfg.extra_pos_embeddings, h->Prows, s));
+  HIPCHK(kmb_pos_bwd_launch(h->tl.dz, Bd, T, d, h->gf(h->dec_pos), h->cfg.extra_pos_embeddings, h->Prows, s));
   // this bucket also holds the cross-attention k | v weights and biases of every decoder layer, whose gradients come from
   // the side stream (the batched weight gradient above, the per-layer bias reducers): complete when BOTH streams are here
   KCHK(layer_end(-1, ev++));

@@ -40,6 +40,8 @@ hipError_t kmb_gemm_rs_launch(const KmbGemm& p, hipStream_t stream);
 hipError_t kmb_attn_fwd_launch(const KmbAttn& p, hipStream_t stream);
 hipError_t kmb_attn_bwd_launch(const KmbAttn& p, hipStream_t stream);
 const char* kmb_attn_check(const KmbAttn& p, int backward);
+// the kernel kmb_attn_fwd_launch / kmb_attn_bwd_launch runs for a checked p (KMB_ATTN_ROUTE_*); no GPU call (kmb_debug_attn_route)
+int kmb_attn_route(const KmbAttn& p, int backward);
 
 // single-query attention over a KV cache (generation): one query row per (row, head)
 const char* kmb_attn_decode_check(const KmbAttnDecode& p);

@@ -40,6 +40,18 @@ class KmbPretrain(C.Structure):
 class KmbForwardOpts(C.Structure):
     _fields_ = [("encoder_states", c_p), ("decoder_states_out", c_p), ("skip_head", i32),
                 ("row_weights", c_p), ("loss_reduction", i32)]
+    # kmb_forward_opts.targets_per_input: the int32 behind loss_reduction, in what was the struct's tail padding (sizeof is unchanged, a zeroed
+    # record means one target per input).  It is a property on that word, not a ctypes field: tests/test_loss_weights_cpu.py pins _fields_ as
+    # ending in row_weights, loss_reduction, and tests/test_grouped_targets_cpu.py pins this offset against the library's sizeof.
+    _TPI_OFFSET = 36
+
+    @property
+    def targets_per_input(self):
+        return i32.from_address(C.addressof(self) + self._TPI_OFFSET).value
+
+    @targets_per_input.setter
+    def targets_per_input(self, g):
+        i32.from_address(C.addressof(self) + self._TPI_OFFSET).value = int(g)
 
 
 class KmbGemm(C.Structure):
@@ -76,6 +88,8 @@ class KmbDecodeBlock(C.Structure):
 
 # kmb_debug_decode_route: the kernel a decode block runs (include/kmbart.h KMB_DECODE_ROUTE_*)
 DECODE_ROUTES = ("proj_wide", "proj2", "proj4", "proj6", "attn_self", "attn_cross", "attn_cross_kvlds")
+# kmb_debug_attn_route: the kernel an attention forward / backward runs (include/kmbart.h KMB_ATTN_ROUTE_*)
+ATTN_ROUTES = ("general", "small", "small_pack", "qstream")
 
 
 class KmbDrop(C.Structure):
@@ -113,6 +127,7 @@ PROTOTYPES = {
     "kmb_bf16_arena_elems": (i64, [c_p]),
     "kmb_bind_arenas": (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "kmb_workspace_bytes": (i64, [c_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kmb_workspace_bytes_grouped": (i64, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kmb_bind_workspace": (C.c_int, [c_p, c_p, i64]),
     "kmb_sync_params": (C.c_int, [c_p, c_p]),
     "kmb_set_seed": (C.c_int, [c_p, C.c_uint64]),
@@ -204,6 +219,7 @@ PROTOTYPES = {
     "kmb_gemm_shared_device": (C.c_int, [C.c_int]),
     "kmb_debug_gemm_route": (C.c_int, [C.POINTER(KmbGemm), C.c_int, c_p, C.c_int32]),
     "kmb_debug_decode_route": (C.c_int, [C.POINTER(KmbDecodeBlock)]),
+    "kmb_debug_attn_route": (C.c_int, [C.POINTER(KmbAttn), C.c_int]),
     "kmb_comm_unique_id": (C.c_int, [c_p]),
     "kmb_comm_init": (C.c_int, [c_p, C.c_int, C.c_int, c_p]),
     "kmb_comm_destroy": (C.c_int, [c_p]),

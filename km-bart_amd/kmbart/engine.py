@@ -17,6 +17,25 @@ _CFG_INT_FIELDS = ("vocab_size", "d_model", "encoder_layers", "decoder_layers", 
 LOSS_REDUCTIONS = {"mean": 0, "sum": 1}   # kmb_forward_opts.loss_reduction
 
 
+def check_targets_per_input(targets_per_input, input_ids, **decoder_side):
+    """The ONE check of `targets_per_input` (Engine.forward and the model classes call it): None and 1 mean one target per input and return 1;
+    anything below 1 is a ValueError; G > 1: every given decoder-side tensor (by keyword: its name goes into the message) must have exactly G
+    rows per input, row i belonging to input i // G.  Pure shape arithmetic -- no device, no engine."""
+    if targets_per_input is None:
+        return 1
+    G = int(targets_per_input)
+    if G < 1:
+        raise ValueError("targets_per_input must be a positive integer, got %r" % (targets_per_input,))
+    if G == 1:
+        return 1
+    B = int(input_ids.shape[0])
+    for name, t in decoder_side.items():
+        if t is not None and int(t.shape[0]) != B * G:
+            raise ValueError("targets_per_input = %d: %s needs %d x %d = %d rows (row i belongs to input i // %d), got %d"
+                             % (G, name, G, B, B * G, G, int(t.shape[0])))
+    return G
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -292,21 +311,29 @@ class Engine:
     def forward(self, input_ids, image_features, attention_mask=None, decoder_input_ids=None,
                 decoder_attention_mask=None, labels=None, train=False, need_grad=False, want_logits=False,
                 want_encoder=True, encoder_states=None, want_decoder_states=False, skip_head=False,
-                loss_weights=None, loss_reduction="mean"):
+                loss_weights=None, loss_reduction="mean", targets_per_input=None):
         """Returns (loss [1] or None, logits [B,T,V] fp32 or None, encoder_out [B,S,D] or None); with
         want_decoder_states a 4th element, the last decoder hidden states [B,T,D].  `encoder_states` [B,S,D] skips the
         encoder (reference src/model/model.py:76-83); activations are bf16 (float32 in the fp32 validation mode).
         `loss_weights` ([B, T] per decoder row or [B] per sequence, indexed like `labels`) and `loss_reduction` ("mean" / "sum"):
-        kmb_forward_opts.row_weights / loss_reduction."""
+        kmb_forward_opts.row_weights / loss_reduction.
+        `targets_per_input` = G > 1 (kmb_forward_opts.targets_per_input): the decoder tensors, `labels` and `loss_weights` have B * G rows,
+        row i belonging to input i // G; the encoder side runs once on the B inputs; logits / decoder states come back with B * G rows."""
+        G = check_targets_per_input(targets_per_input, input_ids, decoder_input_ids=decoder_input_ids,
+                                    decoder_attention_mask=decoder_attention_mask, labels=labels)
         with torch.cuda.device(self.device):
             b, keep, (B, S, T, ntot) = self._batch(input_ids, image_features if encoder_states is None else [],
                                                    attention_mask, decoder_input_ids, decoder_attention_mask, labels)
-            self._ensure_ws(self.lib.kmb_workspace_bytes(self.h, B, S, T, ntot))
+            Bd = B * G   # decoder rows
+            if G > 1:
+                self._ensure_ws(self.lib.kmb_workspace_bytes_grouped(self.h, B, S, T, ntot, G))
+            else:
+                self._ensure_ws(self.lib.kmb_workspace_bytes(self.h, B, S, T, ntot))
             self._poison()
             D = int(self.config.d_model)
             logits = None
             if want_logits:
-                logits = torch.empty((B * T, self.logits_ld), dtype=torch.float32, device=self.device)
+                logits = torch.empty((Bd * T, self.logits_ld), dtype=torch.float32, device=self.device)
             enc = None
             if want_encoder:
                 enc = torch.empty((B, S, D), dtype=self.act_dtype, device=self.device)
@@ -321,17 +348,20 @@ class Engine:
                 opts.encoder_states = ptr(encoder_states)
                 keep.append(encoder_states)
             if want_decoder_states:
-                dec = torch.empty((B, T, D), dtype=self.act_dtype, device=self.device)
+                dec = torch.empty((Bd, T, D), dtype=self.act_dtype, device=self.device)
                 opts.decoder_states_out = ptr(dec)
             opts.skip_head = 1 if skip_head else 0
-            self._loss_opts(opts, keep, loss_weights, loss_reduction, labels, B, T)
+            self._loss_opts(opts, keep, loss_weights, loss_reduction, labels, Bd, T)
+            if G > 1:
+                opts.targets_per_input = G
             self.fwd_serial += 1
             check(self.lib.kmb_forward_ex(self.h, C.byref(b), C.byref(opts), 1 if train else 0, 1 if need_grad else 0,
                                           ptr(loss), ptr(logits), ptr(enc), _stream()))
             self._keep = keep
             if logits is not None:
-                logits = logits.view(B, T, self.logits_ld)[:, :, : int(self.config.vocab_size)]
+                logits = logits.view(Bd, T, self.logits_ld)[:, :, : int(self.config.vocab_size)]
             self._last_bt = (B, T)
+            self._last_bd = Bd
             self._last_S = S
             return (loss, logits, enc, dec) if want_decoder_states else (loss, logits, enc)
 
@@ -356,6 +386,7 @@ class Engine:
             check(self.lib.kmb_score(self.h, C.byref(b), ptr(logp), ptr(nll), ptr(count), C.byref(path), _stream()))
             self._keep = keep
             self._last_bt = (B, T)
+            self._last_bd = B
             self._last_S = S
             self.last_score_path = int(path.value)
             return logp, nll, count
@@ -364,6 +395,8 @@ class Engine:
         """`output_hidden_states` of the forward still in the workspace: tuple of [B, T, d] activations of the encoder
         (which = 0: embedding output + every layer's output) or decoder (which = 1) stack."""
         B, T = self._last_bt
+        if which == 1:
+            B = getattr(self, "_last_bd", B)   # decoder rows: B * targets_per_input
         rows_T = T if which == 1 else self._last_S
         n = int(self.config.encoder_layers if which == 0 else self.config.decoder_layers) + 1
         out = []
@@ -408,6 +441,7 @@ class Engine:
     def last_logits(self):
         """fp32 logits [B,T,V] of the decoder states the last forward left in the workspace (one head GEMM)."""
         B, T = self._last_bt
+        B = getattr(self, "_last_bd", B)   # decoder rows: B * targets_per_input
         with torch.cuda.device(self.device):
             logits = torch.empty((B * T, self.logits_ld), dtype=torch.float32, device=self.device)
             check(self.lib.kmb_last_logits(self.h, ptr(logits), _stream()))
@@ -456,6 +490,7 @@ class Engine:
             logits = torch.empty((B * T, self.logits_ld), dtype=torch.float32, device=dev) if want_logits else None
             self.fwd_serial += 1
             self._last_bt = (B, T)
+            self._last_bd = B
             self._last_S = S
             D = int(self.config.d_model)
             opts = KmbForwardOpts()

@@ -14,7 +14,7 @@ from types import SimpleNamespace
 import torch
 from torch import nn
 
-from kmbart.engine import Engine
+from kmbart.engine import Engine, check_targets_per_input
 from src.model.config import MultiModalBartConfig
 
 WEIGHTS_NAME = "pytorch_model.bin"
@@ -456,6 +456,24 @@ def _check_loss_args(loss_weights, loss_reduction, labels):
         raise ValueError("loss_weights weigh the rows' cross-entropy: they need labels")
 
 
+def _check_targets_per_input(targets_per_input, input_ids, decoder_input_ids, decoder_attention_mask, labels, loss_weights, use_cache,
+                             decoder_cached_states, output_attentions, output_hidden_states):
+    """`targets_per_input` of forward(): None and 1 mean one target per input (returns 1, nothing else is looked at).  G > 1: the decoder tensors,
+    the labels and the loss weights must have exactly G rows per input, and the paths that have no grouped form are refused -- all of it from
+    shapes and flags alone, before the engine is touched."""
+    G = check_targets_per_input(targets_per_input, input_ids)
+    if G == 1:
+        return 1
+    if use_cache or decoder_cached_states is not None:
+        raise NotImplementedError("targets_per_input > 1 has no cached decoding step (generate() expands its own rows)")
+    if output_attentions or output_hidden_states:
+        raise NotImplementedError("targets_per_input > 1 does not return attention / hidden-state outputs")
+    if decoder_input_ids is None:
+        raise ValueError("targets_per_input = %d needs decoder_input_ids: [%d x batch, tgt_len]" % (G, G))
+    return check_targets_per_input(G, input_ids, decoder_input_ids=decoder_input_ids, decoder_attention_mask=decoder_attention_mask,
+                                   labels=labels, loss_weights=loss_weights)
+
+
 def _check_label_smoothing(eps):
     eps = float(eps)
     if not (0.0 <= eps < 1.0):   # (NaN fails both)
@@ -616,7 +634,7 @@ class MultiModalBartForConditionalGeneration(nn.Module):
     def forward(self, input_ids, image_features, attention_mask=None, encoder_outputs=None, decoder_input_ids=None,
                 decoder_attention_mask=None, decoder_cached_states=None, labels=None, use_cache=None,
                 output_attentions=None, output_hidden_states=None, return_logits=None, loss_weights=None,
-                loss_reduction="mean", **unused):
+                loss_reduction="mean", targets_per_input=None, **unused):
         """Reference src/model/model.py:325-405.  Returns (loss, logits, encoder_last_hidden) with labels,
         (logits, encoder_last_hidden) without; with `use_cache=True` (and no labels) the KV-cached step of
         src/model/model.py:384-397: (logits of the LAST decoder position [rows, 1, V], decoder_cached_states,
@@ -632,9 +650,19 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         gradient flows to them); a row whose label is -100 contributes exactly nothing whatever its weight holds, NaN included; a
         valid row with weight 0 still counts in D.  The gradient is that of the FULL log-softmax: it equals the gradient of a
         sampler's sum_logprobs only when sampling ran unfiltered (top_k=0, top_p=1.0) -- the restricted-support softmax of top-k /
-        top-p sampling is not covered."""
+        top-p sampling is not covered.
+        `targets_per_input` = G > 1 (not in the reference): G target sequences per input with the encoder side run ONCE.  `input_ids`,
+        `image_features` and `attention_mask` describe B inputs; `decoder_input_ids`, `decoder_attention_mask`, `labels` have B * G rows and
+        `loss_weights` is [B * G] or [B * G, T], row i belonging to input i // G -- the row order of generate(num_return_sequences=G).  The
+        result equals the forward on the inputs replicated with repeat_interleave(G) up to bf16 rounding (one rounded encoder gradient
+        instead of the sum of G); logits come back as [B * G, T, V].  None and 1 are today's forward.  No cached step and no attention /
+        hidden-state outputs with G > 1 (NotImplementedError); G * tgt_len <= 384."""
+        G = _check_targets_per_input(targets_per_input, input_ids, decoder_input_ids, decoder_attention_mask, labels, loss_weights, use_cache,
+                                     decoder_cached_states, output_attentions, output_hidden_states)
         eng = self._need_engine()
         _check_loss_args(loss_weights, loss_reduction, labels)
+        if G > 1:
+            use_cache = False   # (config.use_cache is the default of the ungrouped eval forward only)
         use_cache = self._resolve_use_cache(use_cache, labels is not None, decoder_input_ids, decoder_cached_states,
                                             output_attentions, output_hidden_states)
         if use_cache or decoder_cached_states is not None:
@@ -664,7 +692,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         loss, logits, enc = eng.forward(input_ids, image_features, attention_mask, decoder_input_ids,
                                         decoder_attention_mask, labels, train=self.training, need_grad=need_grad,
                                         want_logits=want_logits, encoder_states=enc_states, want_encoder=not lazy_enc,
-                                        loss_weights=loss_weights, loss_reduction=loss_reduction)
+                                        loss_weights=loss_weights, loss_reduction=loss_reduction,
+                                        targets_per_input=G if G > 1 else None)
         if lazy_enc:
             enc = LazyEncoderStates(eng)
         # output_hidden_states / output_attentions (src/model/modules.py:143-165, transformers 3.0.2 BartDecoder; the tuple
@@ -880,12 +909,13 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         if self._post_backward is not None:
             self._post_backward()
 
-    def train_step_fwd_bwd(self, batch, loss_scale=1.0):
-        """forward + backward without any host synchronisation; returns the device loss tensor [1]."""
+    def train_step_fwd_bwd(self, batch, loss_scale=1.0, targets_per_input=None):
+        """forward + backward without any host synchronisation; returns the device loss tensor [1].  targets_per_input: as in forward()."""
         eng = self._need_engine()
         loss, _, _ = eng.forward(batch["input_ids"], batch["image_features"], batch.get("attention_mask"),
                                  batch.get("decoder_input_ids"), batch.get("decoder_attention_mask"), batch["labels"],
-                                 train=self.training, need_grad=True, want_logits=False, want_encoder=False)
+                                 train=self.training, need_grad=True, want_logits=False, want_encoder=False,
+                                 targets_per_input=targets_per_input)
         self._backward(loss_scale)
         return loss
 
@@ -1368,13 +1398,15 @@ class MultiModalBartForPreTraining(MultiModalBartForConditionalGeneration):
                 decoder_attention_mask=None, decoder_cached_states=None, labels=None, mrm_labels=None, mrm_mask=None,
                 attribute_labels=None, attribute_mask=None, relation_labels=None, use_cache=None,
                 output_attentions=None, output_hidden_states=None, return_logits=None, loss_weights=None,
-                loss_reduction="mean", **unused):
+                loss_reduction="mean", targets_per_input=None, **unused):
         """Reference src/model/model.py:162-309.  With any label the loss dict comes first: (losses, logits[, decoder hidden
         states, decoder attentions], encoder states[, encoder hidden states, encoder attentions]) -- `outputs[1:]` of the bare
         model behind the logits (:291, :309); without labels it is the conditional-generation forward (cache included).
         `encoder_outputs` is passed through to the model as there (:225-242).  `loss_weights` / `loss_reduction` (see the
         conditional-generation forward) touch the LM term only: `lm_loss_factor` multiplies the weighted term, the MRM, attribute and
-        relation terms and their factors are as they were."""
+        relation terms and their factors are as they were.  `targets_per_input` > 1 is not implemented for pre-training."""
+        if targets_per_input is not None and int(targets_per_input) > 1:
+            raise NotImplementedError("MultiModalBartForPreTraining has no grouped forward: targets_per_input must be None or 1")
         eng = self._need_engine()
         cfg = self.config
         _check_loss_args(loss_weights, loss_reduction, labels)
@@ -1527,11 +1559,16 @@ class MultiModalBartModel(MultiModalBartForConditionalGeneration):
 
     def forward(self, input_ids, image_features, attention_mask=None, decoder_input_ids=None, encoder_outputs=None,
                 decoder_attention_mask=None, decoder_cached_states=None, use_cache=None, output_attentions=None,
-                output_hidden_states=None, **unused):
+                output_hidden_states=None, targets_per_input=None, **unused):
         """Reference src/model/model.py:39-103: (decoder states[, cache][, decoder hidden states, decoder attentions], encoder
         states[, encoder hidden states, encoder attentions]).  use_cache (default config.use_cache, _resolve_use_cache): the
-        KV-cached step -- decoder states of the new position [rows, 1, d], the DecoderCache, the encoder states."""
+        KV-cached step -- decoder states of the new position [rows, 1, d], the DecoderCache, the encoder states.
+        `targets_per_input` = G > 1: as in MultiModalBartForConditionalGeneration.forward; the decoder states come back as [B * G, T, d]."""
+        G = _check_targets_per_input(targets_per_input, input_ids, decoder_input_ids, decoder_attention_mask, None, None, use_cache,
+                                     decoder_cached_states, output_attentions, output_hidden_states)
         eng = self._need_engine()
+        if G > 1:
+            use_cache = False   # (config.use_cache is the default of the ungrouped eval forward only)
         use_cache = self._resolve_use_cache(use_cache, False, decoder_input_ids, decoder_cached_states, output_attentions,
                                             output_hidden_states)
         if use_cache or decoder_cached_states is not None:
@@ -1556,7 +1593,8 @@ class MultiModalBartModel(MultiModalBartForConditionalGeneration):
             decoder_attention_mask = decoder_input_ids.ne(self.config.pad_token_id).long()
         _, _, enc, dec = eng.forward(input_ids, image_features, attention_mask, decoder_input_ids, decoder_attention_mask,
                                      None, train=self.training, need_grad=False, want_logits=False, want_encoder=True,
-                                     encoder_states=enc_states, want_decoder_states=True, skip_head=True)
+                                     encoder_states=enc_states, want_decoder_states=True, skip_head=True,
+                                     targets_per_input=G if G > 1 else None)
         dec_extra, enc_extra = (), ()
         if output_hidden_states:
             dec_extra += (eng.hidden_states(1)[:-1],)

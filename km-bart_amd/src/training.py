@@ -280,26 +280,27 @@ def _pretrain(epoch, model, train_loader, optimizer, device, args, logger, callb
 
 
 def self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args, reward, logger=None, callback=None,
-                            log_interval=1, tb_writer=None, tb_interval=1, baseline="greedy", sample_kwargs=None):
+                            log_interval=1, tb_writer=None, tb_interval=1, baseline="greedy", sample_kwargs=None, samples_per_input=1):
     """`fine_tune` with the self-critical loss in place of the cross-entropy: per batch `self_critical_step` with
     `reward.for_batch(batch)` (src.rewards.CiderReward: the reward is computed on the device), then zero_grad -> backward ->
     optimizer step in fine_tune's order, with its accumulation and its data-parallel scopes.  The log line is fine_tune's plus the
     batch's mean reward and mean advantage:
     `Epoch [e/E], Step [i/N], Loss: x.xxxx, Reward: x.xxxx, Advantage: x.xxxx, ETA: ...`.
     Values are read back only where fine_tune reads its loss: step i's after step i + 1 has been enqueued.  Returns the epoch's
-    mean loss.  baseline: "greedy" or None; sample_kwargs goes to self_critical_step (max_length, ...)."""
+    mean loss.  baseline: "greedy", "mean" (samples_per_input >= 2) or None; sample_kwargs goes to self_critical_step (max_length, ...);
+    samples_per_input = G > 1: G samples per input, `reward.for_batch(batch, repeats=G)`, one grouped forward (self_critical_step)."""
     n_accum = _accumulation_steps(args)
     try:
         if n_accum > 1:
             _accumulate(model, True)
         return _self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args, reward, logger, callback,
-                                        log_interval, tb_writer, tb_interval, baseline, sample_kwargs, n_accum)
+                                        log_interval, tb_writer, tb_interval, baseline, sample_kwargs, n_accum, samples_per_input)
     finally:
         _release(model, optimizer, n_accum > 1)
 
 
 def _self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args, reward, logger, callback, log_interval,
-                             tb_writer, tb_interval, baseline, sample_kwargs, n_accum=1):
+                             tb_writer, tb_interval, baseline, sample_kwargs, n_accum=1, samples_per_input=1):
     n_steps = len(train_loader)
     model.train()
     t0 = datetime.now()
@@ -324,8 +325,12 @@ def _self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args
                                   epoch * n_steps + j + 1)
 
     for i, batch in enumerate(train_loader):
-        loss, info = self_critical_step(model, batch, reward.for_batch(batch), device, baseline=baseline,
-                                        sample_kwargs=sample_kwargs)
+        if samples_per_input > 1:
+            loss, info = self_critical_step(model, batch, reward.for_batch(batch, repeats=samples_per_input), device, baseline=baseline,
+                                            sample_kwargs=sample_kwargs, samples_per_input=samples_per_input)
+        else:
+            loss, info = self_critical_step(model, batch, reward.for_batch(batch), device, baseline=baseline,
+                                            sample_kwargs=sample_kwargs)
         first, last = _micro_step(i, n_steps, n_accum)
         if first:
             optimizer.zero_grad()
@@ -349,7 +354,20 @@ def _self_critical_fine_tune(epoch, model, train_loader, optimizer, device, args
     return loss_sum / max(n_steps, 1)
 
 
-def self_critical_step(model, batch, reward_fn, device, baseline="greedy", sample_kwargs=None):
+def leave_one_out_baseline(rewards, samples_per_input):
+    """The multi-sample self-critical baseline: rewards [B * G] in groups of G consecutive rows (the row order of
+    generate(num_return_sequences=G)); b_i = (sum of the group's rewards - r_i) / (G - 1), the mean reward of the input's OTHER samples.
+    Needs G >= 2 (ValueError).  The advantages r - b of a group sum to zero.  Device ops only."""
+    G = int(samples_per_input)
+    if G < 2:
+        raise ValueError("the 'mean' (leave-one-out) baseline needs samples_per_input >= 2, got %d" % G)
+    if rewards.dim() != 1 or rewards.shape[0] % G != 0:
+        raise ValueError("rewards must be [batch * samples_per_input], got %s with samples_per_input = %d" % (tuple(rewards.shape), G))
+    r = rewards.view(-1, G)
+    return ((r.sum(dim=1, keepdim=True) - r) / (G - 1)).reshape(-1)
+
+
+def self_critical_step(model, batch, reward_fn, device, baseline="greedy", sample_kwargs=None, samples_per_input=1):
     """One REINFORCE / self-critical loss (Rennie et al. 2017) on `batch` (input_ids, image_features, attention_mask):
     under no_grad one `generate(do_sample=True, num_beams=1, top_k=0, top_p=1.0, ...)` draws a sequence per input from the model's
     full distribution; `reward_fn(ids) -> float32 [B]` scores it (any callable; src.rewards.CiderReward.for_batch(batch) is a CIDEr-D
@@ -360,31 +378,46 @@ def self_critical_step(model, batch, reward_fn, device, baseline="greedy", sampl
     and `baseline` as device tensors (and `greedy_ids` with the greedy baseline); nothing here reads a value back.
     `sample_kwargs` goes to both generate calls (max_length, min_length, ...); its `pad_to_multiple_of` (optional) goes to
     labels_from_generated instead.  Sampling is unfiltered on purpose: the forward's gradient is that of the full log-softmax, which is
-    the sampler's log-probability only without top-k / top-p filtering."""
+    the sampler's log-probability only without top-k / top-p filtering.
+    `samples_per_input` = G > 1: the sampling generate draws G sequences per input (num_return_sequences=G: rows i G .. i G + G - 1 belong
+    to input i), `reward_fn` scores the [B * G] rows (CiderReward.for_batch(batch, repeats=G)), and the ONE forward is grouped --
+    `targets_per_input=G` on the B inputs, the encoder side run once -- with `loss_weights = A / (B G)`.  baseline "mean" (G >= 2 only): the
+    leave-one-out mean of the input's other samples (leave_one_out_baseline), no greedy pass; "greedy": the one greedy sequence of an input,
+    scored once per sample row, i.e. its reward broadcast over the input's G samples; a tensor: [B * G].  info's tensors have B * G rows."""
     from src.model.utils import labels_from_generated
 
     kw = dict(sample_kwargs or {})
     pad_to = kw.pop("pad_to_multiple_of", None)
-    for fixed in ("do_sample", "num_beams", "top_k", "top_p"):
+    for fixed in ("do_sample", "num_beams", "top_k", "top_p", "num_return_sequences"):
         if fixed in kw:
             raise ValueError("self_critical_step fixes %s itself (unfiltered one-beam sampling)" % fixed)
+    G = int(samples_per_input)
+    if G < 1:
+        raise ValueError("samples_per_input must be at least 1, got %d" % G)
+    if baseline == "mean" and G < 2:
+        raise ValueError("the 'mean' (leave-one-out) baseline needs samples_per_input >= 2, got %d" % G)
+    skw = dict(kw, num_return_sequences=G) if G > 1 else kw
     input_ids = batch["input_ids"].to(device)
     image_features = _features(batch["image_features"], device)
     attention_mask = batch["attention_mask"].to(device)
     info = {}
     with torch.no_grad():
         sample_ids = model.generate(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
-                                    do_sample=True, num_beams=1, top_k=0, top_p=1.0, **kw)
+                                    do_sample=True, num_beams=1, top_k=0, top_p=1.0, **skw)
         rewards = reward_fn(sample_ids).to(device=device, dtype=torch.float32)
         if baseline is None:
             base = torch.zeros_like(rewards)
         elif isinstance(baseline, str):
-            if baseline != "greedy":
-                raise ValueError("baseline must be 'greedy', None or a [B] tensor, got %r" % (baseline,))
-            greedy_ids = model.generate(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
-                                        do_sample=False, num_beams=1, **kw)
-            base = reward_fn(greedy_ids).to(device=device, dtype=torch.float32)
-            info["greedy_ids"] = greedy_ids
+            if baseline == "mean":
+                base = leave_one_out_baseline(rewards, G)
+            elif baseline == "greedy":
+                greedy_ids = model.generate(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
+                                            do_sample=False, num_beams=1, **kw)
+                # (G > 1: reward_fn scores B * G rows, row i against input i // G: the greedy sequence once per sample row)
+                base = reward_fn(greedy_ids.repeat_interleave(G, dim=0) if G > 1 else greedy_ids).to(device=device, dtype=torch.float32)
+                info["greedy_ids"] = greedy_ids
+            else:
+                raise ValueError("baseline must be 'greedy', 'mean', None or a [B] tensor, got %r" % (baseline,))
         else:
             base = baseline.to(device=device, dtype=torch.float32)
         advantages = rewards - base
@@ -395,6 +428,6 @@ def self_critical_step(model, batch, reward_fn, device, baseline="greedy", sampl
     B = sample_ids.shape[0]
     outputs = model.forward(input_ids=input_ids, image_features=image_features, attention_mask=attention_mask,
                             decoder_input_ids=dec_in, decoder_attention_mask=dec_mask, labels=labels,
-                            loss_weights=advantages / B, loss_reduction="sum")
+                            loss_weights=advantages / B, loss_reduction="sum", **({"targets_per_input": G} if G > 1 else {}))
     info.update(sample_ids=sample_ids, advantages=advantages, rewards=rewards, baseline=base)
     return outputs[0], info

@@ -130,8 +130,8 @@ def main(rank, args):
         logger.info("Epoch {}".format(epoch + 1), pad=True)
         if reward is not None:
             self_critical_fine_tune(epoch, model, loader, optimizer, device, args, reward, logger=logger,
-                                    log_interval=args.log_interval, baseline="greedy" if args.sc_baseline == "greedy" else None,
-                                    sample_kwargs=dict(max_length=args.sc_max_length))
+                                    log_interval=args.log_interval, baseline=None if args.sc_baseline == "none" else args.sc_baseline,
+                                    sample_kwargs=dict(max_length=args.sc_max_length), samples_per_input=args.sc_samples)
         else:
             fine_tune(epoch, model, loader, optimizer, device, args, logger=logger, log_interval=args.log_interval)
         if rank == 0:
@@ -183,8 +183,12 @@ def parse_args(argv=None):
                    help="self-critical sequence training: REINFORCE on sampled sequences with a reward computed on the device "
                         "(token-id-level CIDEr, not the word-level evaluation metric) in place of the cross-entropy")
     p.add_argument("--sc_reward", default="cider_d", choices=["cider_d", "cider"], help="the reward of --self_critical")
-    p.add_argument("--sc_baseline", default="greedy", choices=["greedy", "none"],
-                   help="the baseline of --self_critical: the reward of a greedy decode, or none")
+    p.add_argument("--sc_baseline", default="greedy", choices=["greedy", "mean", "none"],
+                   help="the baseline of --self_critical: the reward of a greedy decode, the mean reward of the input's other samples "
+                        "(leave-one-out, needs --sc_samples >= 2), or none")
+    p.add_argument("--sc_samples", default=1, type=int,
+                   help="sampled sequences per input of --self_critical; above 1 the step's forward takes them as several targets per input "
+                        "(the encoder side runs once)")
     p.add_argument("--sc_max_length", default=32, type=int, help="max_length of the sampled and greedy sequences (<= 256)")
     p.add_argument("--master_port", type=str, default="12355")
     p.add_argument("--batch_size", type=int, default=64)
@@ -202,6 +206,11 @@ def parse_args(argv=None):
     if not (0.0 <= args.label_smoothing < 1.0):
         raise ValueError("--label_smoothing must be in [0, 1), got %r" % (args.label_smoothing,))
     if args.self_critical:
+        if args.sc_samples < 1 or args.sc_samples * args.sc_max_length > 384:
+            raise ValueError("--sc_samples must be at least 1 with --sc_samples x --sc_max_length <= 384 (the grouped forward's limit), got %d x %d"
+                             % (args.sc_samples, args.sc_max_length))
+        if args.sc_baseline == "mean" and args.sc_samples < 2:
+            raise ValueError("--sc_baseline mean is the leave-one-out mean over an input's samples: it needs --sc_samples >= 2")
         if not 2 <= args.sc_max_length <= 256:
             raise ValueError("--sc_max_length must be in [2, 256] (the reward kernel's width), got %d" % args.sc_max_length)
         if args.amp:
