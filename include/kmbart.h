@@ -163,7 +163,14 @@ typedef struct KmbDecodeBlock {
   int32_t kv_group;                         /* kind 2, optional: a promise that kv_row[r] == r / kv_group (beam rows of a
                                              * batch item are consecutive): lets a workgroup stage each item's keys /
                                              * values once for all of its rows.  0: no promise. */
+  /* appended (a zeroed record is a bf16 block, as before): the format of W */
+  int32_t w_format;                         /* KMB_WFMT_BF16: W as above.  KMB_WFMT_FP8_E4M3: W holds one OCP e4m3 code per element
+                                             * (N * K bytes, kmb_op_decode_pack_fp8's order) and row n of the weight is code * 2^w_exp[n];
+                                             * the block returns, bit for bit, what the bf16 block returns on those dequantised weights */
+  const int8_t* w_exp;                      /* [N] row exponents (4-byte aligned), required by KMB_WFMT_FP8_E4M3 */
 } KmbDecodeBlock;
+#define KMB_WFMT_BF16 0
+#define KMB_WFMT_FP8_E4M3 1
 
 typedef struct KmbDrop { uint32_t thr16; uint32_t seed; float scale; } KmbDrop;
 typedef struct KmbAdamW { double lr, beta1, beta2, eps, weight_decay; int32_t step; int32_t correct_bias; float grad_scale; } KmbAdamW;
@@ -657,6 +664,13 @@ int kmb_gen_beam_sample_step(kmb_handle* h, const float* logits, int ld, int num
                              float* next_scores, int64_t* next_tokens, int32_t* next_beam_idx, float* scratch, int64_t scratch_floats,
                              int reorder_step, void* stream);
 int64_t kmb_gen_workspace_bytes(const kmb_handle* h, int B, int S, int num_beams, int max_length, int n_features);
+/* The format of the six per-layer decoder matrices the fused decode blocks read (KMB_WFMT_BF16, the default, or
+ * KMB_WFMT_FP8_E4M3: KmbDecodeBlock.w_format).  State of the handle, read by the kmb_gen_* family only: kmb_gen_workspace_bytes
+ * sizes the packed copies for it (FP8: half the bytes plus the row exponents), the next kmb_gen_begin packs in it, kmb_gen_step
+ * hands it to the blocks; training, scoring and the vocabulary projection never see it.  FP8 exists only where the fused blocks
+ * run: this call refuses it for a configuration they do not take, and kmb_gen_begin refuses it for more than 1024 rows, under
+ * KMB_GEN_FUSED=0 and in the fp32 validation mode -- never a silent bf16 decode.  Ends the active generation. */
+int kmb_gen_set_weight_format(kmb_handle* h, int format);
 
 /* Data-parallel runs share the GPU between the GEMMs and RCCL's all-reduce kernel (reference: torch DDP's NCCL streams,
  * vcg_train.py:98).  The persistent GEMM variants keep one workgroup per CU; with on != 0 they hand out EVERY tile through
@@ -801,6 +815,13 @@ int kmb_op_attn_decode(const KmbAttnDecode* p, void* stream);
 int kmb_op_decode_block(const KmbDecodeBlock* p, void* stream);
 /* packed <- W ([N, K] row-major, row stride ld; N % 16 == 0, K % 64 == 0) in the order KmbDecodeBlock.W is read */
 int kmb_op_decode_pack(const kmb_bf16* W, int ld, int N, int K, kmb_bf16* packed, void* stream);
+/* The FP8 (e4m3) form of W for KmbDecodeBlock.w_format == KMB_WFMT_FP8_E4M3: exps[n] = the smallest integer e with
+ * max_k |W[n, k]| * 2^-e <= 448 (over the row's finite elements; clamped to [-120, 119]; 0 for a zero row), codes = W * 2^-exps[n]
+ * rounded to nearest even into OCP e4m3fn (subnormal codes kept; saturated at +-448 where the exponent was clamped and for
+ * infinities; a NaN becomes the NaN code), N * K bytes in the order the block reads them: one KiB per (16-row tile n, 64-deep
+ * chunk c), lane l's 16 bytes = W[n*16 + (l & 15)][c*64 + (l >> 4)*16 .. + 15].  N % 16 == 0, K % 64 == 0, ld >= K. */
+int kmb_op_decode_pack_fp8(const kmb_bf16* W, int ld, int N, int K, uint8_t* codes, int8_t* exps, void* stream);
+int kmb_abi_sizeof_decode_block(void);
 int kmb_op_ln_fwd(const kmb_bf16* z, const float* gamma, const float* beta, kmb_bf16* y, float* mean, float* rstd,
                   int M, int D, float eps, void* stream);
 /* partials: device float scratch of kmb_op_ln_bwd_scratch(M, D) floats */

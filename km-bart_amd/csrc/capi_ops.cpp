@@ -139,6 +139,11 @@ int kmb_op_decode_block(const KmbDecodeBlock* p, void* stream) {
 int kmb_op_decode_pack(const kmb_bf16* W, int ld, int N, int K, kmb_bf16* packed, void* stream) {
   return hipfail(kmb_decode_pack_launch(&W, &ld, &N, &K, &packed, 1, (hipStream_t)stream), "decode_pack");
 }
+int kmb_op_decode_pack_fp8(const kmb_bf16* W, int ld, int N, int K, uint8_t* codes, int8_t* exps, void* stream) {
+  if (!W || !codes || !exps) return kmb_set_error("kmb_op_decode_pack_fp8: missing tensor");
+  return hipfail(kmb_decode_pack_fp8_launch(&W, &ld, &N, &K, &codes, &exps, 1, (hipStream_t)stream), "decode_pack_fp8");
+}
+int kmb_abi_sizeof_decode_block(void) { return (int)sizeof(KmbDecodeBlock); }
 int kmb_op_ln_fwd(const kmb_bf16* z, const float* gamma, const float* beta, kmb_bf16* y, float* mean, float* rstd,
                   int M, int D, float eps, void* stream) {
   return hipfail(kmb_ln_fwd_launch(z, gamma, beta, y, mean, rstd, M, D, eps, (hipStream_t)stream), "ln_fwd");

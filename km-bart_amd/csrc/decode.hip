@@ -73,29 +73,79 @@ constexpr int HD = 64;
 // weights laid out in the order the fragments are consumed: fragment (16-row tile n, 64-deep chunk c, half s) is ONE
 // contiguous KiB, lane l's eight elements at l*8 -- W[n*16 + (l & 15)][c*64 + (l >> 4)*16 + s*8 ...].  Packed once per
 // generate() by pack_weights_kernel (99 MB for the six decoder layers of vcg_base, 0.1 ms).
-struct WBlock { u32x4 w[24]; };   // one 16-column tile x 768 K
+//
+// FP8 weights (KmbDecodeBlock.w_format == 1): one OCP e4m3 code per element and a power-of-two exponent per
+// weight row.  The copy is in the same order with ONE KiB per (tile n, chunk c): lane l's sixteen codes at l*16 are
+// W[n*16 + (l & 15)][c*64 + (l >> 4)*16 ...], bytes 0-7 the first MFMA's K elements and bytes 8-15 the second's -- the K elements
+// the two bf16 fragments hold, in their order, from one 16-byte request instead of two.  The codes are widened to bf16 in registers
+// (every e4m3 value is a bf16 number) and fed to the same MFMAs; 2^e of the row scales the accumulator column once, after the K
+// loop (scale_acc).  F8 is a compile-time parameter of the blocks: the K loop has no branch on the format.
+template <bool F8>
+struct WBlock { u32x4 w[F8 ? 12 : 24]; };   // one 16-column tile x 768 K
 
 __device__ __forceinline__ bf16x8 as_frag(const u32x4& v) { return __builtin_bit_cast(bf16x8, v); }
 
-__device__ __forceinline__ void load_wblock(WBlock& f, const bf16_t* __restrict__ Wp, int K, int ntile, int k0, int lane) {
-  const bf16_t* p = Wp + ((size_t)ntile * (K >> 6) + (k0 >> 6)) * 1024 + lane * 8;
+// eight e4m3 codes -> one bf16 MFMA fragment: v_cvt_pk_f32_fp8 is exact, and the upper half of such a float is the whole of it
+__device__ __forceinline__ bf16x8 widen_fp8(uint32_t lo, uint32_t hi) {
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  // v_perm_b32 {y, x} bytes 7 6 3 2: (x >> 16) | (y & 0xffff0000)
+  auto pk = [](float x, float y) { return __builtin_amdgcn_perm(__float_as_uint(y), __float_as_uint(x), 0x07060302u); };
+  return as_frag(u32x4{pk(a[0], a[1]), pk(b[0], b[1]), pk(c[0], c[1]), pk(d[0], d[1])});
+}
+
+template <bool F8>
+__device__ __forceinline__ void load_wblock(WBlock<F8>& f, const bf16_t* __restrict__ Wp, int K, int ntile, int k0, int lane) {
+  if constexpr (F8) {
+    const char* p = reinterpret_cast<const char*>(Wp) + ((size_t)ntile * (K >> 6) + (k0 >> 6)) * 1024 + lane * 16;
 #pragma unroll
-  for (int c = 0; c < 12; ++c) {
-    f.w[2 * c] = *reinterpret_cast<const u32x4*>(p + c * 1024);
-    f.w[2 * c + 1] = *reinterpret_cast<const u32x4*>(p + c * 1024 + 512);
+    for (int c = 0; c < 12; ++c) f.w[c] = *reinterpret_cast<const u32x4*>(p + c * 1024);
+  } else {
+    const bf16_t* p = Wp + ((size_t)ntile * (K >> 6) + (k0 >> 6)) * 1024 + lane * 8;
+#pragma unroll
+    for (int c = 0; c < 12; ++c) {
+      f.w[2 * c] = *reinterpret_cast<const u32x4*>(p + c * 1024);
+      f.w[2 * c + 1] = *reinterpret_cast<const u32x4*>(p + c * 1024 + 512);
+    }
+  }
+}
+
+// FP8: the exponents of the four weight rows (= output columns col .. col + 3, col % 4 == 0) a lane's accumulator holds; bf16: none
+template <bool F8>
+__device__ __forceinline__ uint32_t load_wexp(const int8_t* __restrict__ w_exp, int col) {
+  if constexpr (F8) return *reinterpret_cast<const uint32_t*>(w_exp + col);
+  else return 0u;
+}
+// acc[e] *= 2^exponent of its column: exact (the exponents lie in [-120, 119], so the factor is a normal float), and it commutes
+// with every rounding of the sum, so the result is the bf16 block's on the dequantised weights, bit for bit
+template <bool F8>
+__device__ __forceinline__ void scale_acc(f32x4& acc, uint32_t ex4) {
+  if constexpr (F8) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int ex = (int)(int8_t)(ex4 >> (8 * e));
+      acc[e] *= __uint_as_float((uint32_t)(ex + 127) << 23);
+    }
   }
 }
 
 // acc (C^T tile: lane (r, g) holds columns n0 + 4g .. 4g+3 of row r) += W block x activation rows in LDS
-__device__ __forceinline__ void mma_wblock(f32x4& acc, const WBlock& f, const char* lds_a, int a_stride, int k0, int lane) {
+template <bool F8>
+__device__ __forceinline__ void mma_wblock(f32x4& acc, const WBlock<F8>& f, const char* lds_a, int a_stride, int k0, int lane) {
   const int r = lane & 15, g = lane >> 4;
   const char* pa = lds_a + r * a_stride + (k0 + g * 16) * 2;
 #pragma unroll
   for (int c = 0; c < 12; ++c) {
     const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(pa + c * 128);
     const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(pa + c * 128 + 16);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(f.w[2 * c]), a0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(f.w[2 * c + 1]), a1, acc, 0, 0, 0);
+    if constexpr (F8) {
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(widen_fp8(f.w[c][0], f.w[c][1]), a0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(widen_fp8(f.w[c][2], f.w[c][3]), a1, acc, 0, 0, 0);
+    } else {
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(f.w[2 * c]), a0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(f.w[2 * c + 1]), a1, acc, 0, 0, 0);
+    }
   }
 }
 
@@ -114,6 +164,91 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const PackArgs a) {
     const int c = cc % kc, nt = cc / kc;
     const bf16_t* src = d.src + (size_t)(nt * 16 + (lane & 15)) * d.ld + c * 64 + (lane >> 4) * 16 + sub * 8;
     *reinterpret_cast<u32x4*>(d.dst + (size_t)o * 8) = *reinterpret_cast<const u32x4*>(src);
+  }
+}
+
+// ---- FP8 (e4m3) form of the weights: DESIGN.md section 6u ----
+// Row n of a matrix gets the exponent e_n = the smallest integer with amax_n * 2^-e_n <= 448 (amax_n over the row's FINITE elements),
+// from the bits of amax_n: a bf16 magnitude (1 + man / 128) * 2^(ex - 127) is at most 1.75 * 2^(8 + e) from e = ex - 135 on, one more when
+// man / 128 > 0.75.  Clamped to [-120, 119] (2^e and 2^-e stay normal floats and 448 * 2^e a finite bf16); 0 for a row without a finite
+// non-zero element.  Element code = W * 2^-e_n (exact), clamped to +-448 (acts only where e_n was clamped at 119, and on infinities),
+// rounded to nearest even into OCP e4m3fn with subnormal codes kept; a NaN becomes the NaN code 0x7f | sign.  Integer arithmetic
+// throughout, so that tests/fp8_ref.py and this kernel cannot differ by a rounding of log2 or of a conversion mode.
+constexpr int FP8_E_MIN = -120, FP8_E_MAX = 119;
+
+__device__ __forceinline__ int fp8_row_exponent(uint32_t amax) {   // amax: the largest finite bf16 magnitude of the row, as its 15 bits
+  if (amax == 0) return 0;
+  const int ex = (int)(amax >> 7), man = (int)(amax & 0x7f);
+  int e = ex == 0 ? FP8_E_MIN : ex - 135 + (man > 0x60 ? 1 : 0);
+  e = e < FP8_E_MIN ? FP8_E_MIN : e;
+  return e > FP8_E_MAX ? FP8_E_MAX : e;
+}
+
+__device__ __forceinline__ uint32_t fp8_code(uint32_t h, float inv_scale) {   // h: the bf16 bits of the weight, inv_scale = 2^-e
+  const uint32_t sign = (h >> 8) & 0x80u;
+  if ((h & 0x7fffu) > 0x7f80u) return sign | 0x7fu;            // NaN
+  float a = __uint_as_float((h & 0x7fffu) << 16) * inv_scale;  // |W| * 2^-e: exact (inf stays inf)
+  a = a > 448.f ? 448.f : a;
+  if (a < 0.015625f) return sign | (uint32_t)rintf(a * 512.f); // below 2^-6: subnormal codes, multiples of 2^-9 (8 = the smallest normal)
+  const uint32_t b = __float_as_uint(a);
+  const uint32_t r = (b + 0x7ffffu + ((b >> 20) & 1u)) >> 20;  // nearest even at 3 mantissa bits: exponent << 3 | mantissa
+  return sign | (r - (120u << 3));                             // e4m3 bias 7 against 127
+}
+
+struct PackFp8Desc { const bf16_t* src; uint8_t* codes; int8_t* exps; int ld, N, K; int first; };   // first: index of its first 16-row tile
+struct PackFp8Args { PackFp8Desc m[PACK_MAX]; int n; int tiles; };
+
+// one workgroup per 16-row tile of one matrix.  Pass 1: 16 threads per row find its largest finite magnitude (bf16 magnitudes order
+// as their bits) and the row's exponent; pass 2: wave w writes the 64-deep chunks w, w + 4, ... of the tile in fragment order (the
+// second read of the tile's <= 96 KB comes from the cache), and the exponents go to exps beside them.
+__global__ __launch_bounds__(256) void pack_weights_fp8_kernel(const PackFp8Args a) {
+  __shared__ int s_exp[16];
+  const int tile = blockIdx.x;
+  if (tile >= a.tiles) return;
+  int mi = 0;
+  while (mi + 1 < a.n && a.m[mi + 1].first <= tile) ++mi;
+  const PackFp8Desc& d = a.m[mi];
+  const int nt = tile - d.first;
+  {
+    const int r = threadIdx.x >> 4, s = threadIdx.x & 15;
+    const bf16_t* src = d.src + (size_t)(nt * 16 + r) * d.ld;
+    uint32_t amax = 0;
+    for (int j = s; j < (d.K >> 3); j += 16) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(src + j * 8);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t lo = v[e] & 0x7fffu, hi = (v[e] >> 16) & 0x7fffu;
+        if (lo < 0x7f80u && lo > amax) amax = lo;
+        if (hi < 0x7f80u && hi > amax) amax = hi;
+      }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      const uint32_t other = (uint32_t)__shfl_xor((int)amax, o, 16);
+      amax = other > amax ? other : amax;
+    }
+    if (s == 0) {
+      const int e = fp8_row_exponent(amax);
+      s_exp[r] = e;
+      d.exps[nt * 16 + r] = (int8_t)e;
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int kc = d.K >> 6;
+  const float inv_scale = __uint_as_float((uint32_t)(127 - s_exp[lane & 15]) << 23);
+  const bf16_t* row = d.src + (size_t)(nt * 16 + (lane & 15)) * d.ld + (lane >> 4) * 16;
+  for (int c = wave; c < kc; c += 4) {
+    const u32x4 v0 = *reinterpret_cast<const u32x4*>(row + c * 64);
+    const u32x4 v1 = *reinterpret_cast<const u32x4*>(row + c * 64 + 8);
+    u32x4 out;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const uint32_t x = w < 2 ? v0[2 * w] : v1[2 * w - 4], y = w < 2 ? v0[2 * w + 1] : v1[2 * w - 3];
+      out[w] = fp8_code(x & 0xffffu, inv_scale) | fp8_code(x >> 16, inv_scale) << 8 | fp8_code(y & 0xffffu, inv_scale) << 16 |
+               fp8_code(y >> 16, inv_scale) << 24;
+    }
+    *reinterpret_cast<u32x4*>(d.codes + ((size_t)nt * kc + c) * 1024 + lane * 16) = out;
   }
 }
 
@@ -261,7 +396,7 @@ inline int unit_grid(int nslices, int tiles) {
 // ------------------------------------------------------------------------------------------ kind 0: projection
 // one workgroup per (64 * NTW-column block, row tile), see unit_of; wave w owns 16-column tiles w*NTW .. of the block.
 // NTW = 2 (the wide fc1): one 768-deep K block only.
-template <int NCH, int NTW>
+template <int NCH, int NTW, bool F8>
 __device__ __forceinline__ void decode_proj_body(const KmbDecodeBlock& p, char* smem) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int nb, rt;
@@ -282,7 +417,7 @@ __device__ __forceinline__ void decode_proj_body(const KmbDecodeBlock& p, char* 
   // staged rows have left, instead of into slot 0 after the first block's MFMAs -- 9.8 -> 10.2 us: the block is bound by the
   // number of requests its CU issues, not by when the last one is issued.)
   constexpr int NWB = NTW == 2 ? 2 : 3;
-  WBlock wb[NWB];
+  WBlock<F8> wb[NWB];
   load_wblock(wb[0], p.W, p.K, nt0, 0, lane);
   if (NTW == 1) {
     if (nblk > 1) load_wblock(wb[1], p.W, p.K, nt0, KBLK, lane);
@@ -290,11 +425,13 @@ __device__ __forceinline__ void decode_proj_body(const KmbDecodeBlock& p, char* 
   }
   f32x4 bias[NTW];
   uint2 res[NTW];
+  [[maybe_unused]] uint32_t wex[NTW];   // FP8: the row exponents of the lane's four columns, requested with the bias
   auto load_bias_res = [&]() {
 #pragma unroll
     for (int t = 0; t < NTW; ++t) {
       const int col = (nt0 + t) * 16 + g * 4;
       bias[t] = *reinterpret_cast<const f32x4*>(p.bias + col);
+      wex[t] = load_wexp<F8>(p.w_exp, col);
       res[t] = (p.residual != nullptr && row < p.R) ? *reinterpret_cast<const uint2*>(p.residual + (size_t)row * p.ld_res + col) : uint2{0u, 0u};
     }
   };
@@ -329,6 +466,7 @@ __device__ __forceinline__ void decode_proj_body(const KmbDecodeBlock& p, char* 
   for (int t = 0; t < NTW; ++t) {
     const int col = (nt0 + t) * 16 + g * 4;
     float v[4];
+    scale_acc<F8>(acc[t], wex[t]);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = acc[t][e] + bias[t][e];
     if (p.act == 1) {
@@ -343,15 +481,16 @@ __device__ __forceinline__ void decode_proj_body(const KmbDecodeBlock& p, char* 
   DSTAMP(stype, 4);
 }
 
-template <int NCH>
+template <int NCH, bool F8>
 __global__ __launch_bounds__(256) void decode_proj_kernel(const KmbDecodeBlock p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  decode_proj_body<NCH, 1>(p, smem);
+  decode_proj_body<NCH, 1, F8>(p, smem);
 }
 // the wide fc1: 480 workgroups, two per CU -> two waves per SIMD, 256 registers each
+template <bool F8>
 __global__ __launch_bounds__(256, 2) void decode_proj_wide_kernel(const KmbDecodeBlock p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  decode_proj_body<2, 2>(p, smem);
+  decode_proj_body<2, 2, F8>(p, smem);
 }
 
 // ------------------------------------------------------------------------------------------ kinds 1, 2: attention
@@ -382,7 +521,7 @@ constexpr int KS = 144;          // LDS row stride of a staged key row (128 + 16
 __host__ __device__ constexpr int kv_pad(int Tk) { return (KV_ITEMS * Tk + 31) & ~31; }     // staged keys, padded to MFMA K steps
 __host__ __device__ constexpr int pb_stride(int Tk) { return kv_pad(Tk) * 2 + 16; }          // bytes per row of e_hi / e_lo
 
-template <bool SELF, bool KVLDS>
+template <bool SELF, bool KVLDS, bool F8>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const KmbDecodeBlock p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(!(SELF && KVLDS), "the self-attention cache is per row");
@@ -404,8 +543,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const KmbDecodeBlock p
   DSTAMP(stype, 0);
   RowRegs<2> rr;
   rows_issue<2>(rr, p.in, p.ld_in, row0, p.R, p.K, p.gamma, p.beta, wave, lane);
-  WBlock wb[NTW];   // every tile's fragments in flight at once (one workgroup per CU: the registers are free)
+  WBlock<F8> wb[NTW];   // every tile's fragments in flight at once (one workgroup per CU: the registers are free)
   f32x4 acc[NTW], bias[NTW];
+  [[maybe_unused]] uint32_t wex[NTW];   // FP8: the row exponents of the lane's four columns, requested with the bias
 #pragma unroll
   for (int t = 0; t < NTW; ++t) load_wblock(wb[t], p.W, p.K, tile_of(wave * NTW + t), 0, lane);
   // SELF: the first 4 * KU cached keys and VU cached values of this thread's row (all of them for max_length <= 21 / 11)
@@ -471,6 +611,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const KmbDecodeBlock p
   for (int t = 0; t < NTW; ++t) {
     const int tile = wave * NTW + t;
     bias[t] = *reinterpret_cast<const f32x4*>(p.bias + (tile >> 2) * d + h * HD + (tile & 3) * 16 + (lane >> 4) * 4);
+    wex[t] = load_wexp<F8>(p.w_exp, (tile >> 2) * d + h * HD + (tile & 3) * 16 + (lane >> 4) * 4);
   }
   if (SELF) {
     const int prow = row0 + a_lr < p.R ? row0 + a_lr : 0;
@@ -501,6 +642,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const KmbDecodeBlock p
       const int tile = wave * NTW + t, part = tile >> 2;
       const int col = (tile & 3) * 16 + g * 4;           // within the head
       float v[4];
+      scale_acc<F8>(acc[t], wex[t]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = acc[t][e] + bias[t][e];
       if (part == 0) {
@@ -763,6 +905,9 @@ const char* kmb_decode_block_check(const KmbDecodeBlock& p) {
   if ((p.gamma == nullptr) != (p.beta == nullptr)) return "decode block: gamma and beta come together";
   if (p.gamma && p.K != KBLK) return "decode block: the LayerNorm input must be 768 wide";
   if (p.ln_out && (!p.gamma || ((uintptr_t)p.ln_out & 15))) return "decode block: ln_out needs the LayerNorm";
+  if (p.w_format != KMB_WFMT_BF16 && p.w_format != KMB_WFMT_FP8_E4M3) return "decode block: unknown w_format (0 = bf16, 1 = FP8 e4m3)";
+  if (p.w_format == KMB_WFMT_FP8_E4M3 && (!p.w_exp || ((uintptr_t)p.w_exp & 3)))
+    return "decode block: w_format 1 (FP8 e4m3) needs w_exp, the row exponents, 4-byte aligned";
   if (p.kind == 0) {
     if (p.N <= 0 || (p.N & 63)) return "decode block: N must be a multiple of 64";
     if (p.residual && ((p.ld_res & 3) || ((uintptr_t)p.residual & 7))) return "decode block: residual alignment";
@@ -807,34 +952,39 @@ hipError_t kmb_decode_block_launch(const KmbDecodeBlock& p, hipStream_t stream) 
   const int tiles = (p.R + RT - 1) / RT;
   const size_t a_bytes = (size_t)RT * (p.K + 8) * 2;
   const int route = kmb_decode_block_route(p);
-  hipError_t e = hipSuccess;
-  if (p.kind == 0) {
-    static size_t set[4] = {0, 0, 0, 0};
-#define KMB_PROJ(SLOT, KERNEL, NTW)                                                                                   \
-  do {                                                                                                                \
-    if (a_bytes > set[SLOT]) { e = set_lds(KERNEL, a_bytes); if (e != hipSuccess) return e; set[SLOT] = a_bytes; }     \
-    hipLaunchKernelGGL(KERNEL, dim3(unit_grid(p.N / (64 * NTW), tiles)), dim3(256), a_bytes, stream, p);              \
-  } while (0)
-    if (route == KMB_DECODE_ROUTE_PROJ_WIDE) KMB_PROJ(0, decode_proj_wide_kernel, 2);
-    else if (route == KMB_DECODE_ROUTE_PROJ2) KMB_PROJ(1, decode_proj_kernel<2>, 1);
-    else if (route == KMB_DECODE_ROUTE_PROJ4) KMB_PROJ(2, decode_proj_kernel<4>, 1);
-    else KMB_PROJ(3, decode_proj_kernel<6>, 1);
-#undef KMB_PROJ
+  const bool f8 = p.w_format == KMB_WFMT_FP8_E4M3;   // the format selects the instance, not the route
+  // one slot per kernel instance: the largest dynamic LDS size it has been given so far
+  auto run = [&](auto* kernel, size_t& have, size_t lds, int grid) -> hipError_t {
+    if (lds > have) {
+      const hipError_t e = set_lds(kernel, lds);
+      if (e != hipSuccess) return e;
+      have = lds;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, p);
     return hipGetLastError();
+  };
+  if (p.kind == 0) {
+    static size_t set[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    const int g1 = unit_grid(p.N / 64, tiles);
+    if (route == KMB_DECODE_ROUTE_PROJ_WIDE) {
+      const int g2 = unit_grid(p.N / 128, tiles);
+      return f8 ? run(decode_proj_wide_kernel<true>, set[1][0], a_bytes, g2) : run(decode_proj_wide_kernel<false>, set[0][0], a_bytes, g2);
+    }
+    if (route == KMB_DECODE_ROUTE_PROJ2)
+      return f8 ? run(decode_proj_kernel<2, true>, set[1][1], a_bytes, g1) : run(decode_proj_kernel<2, false>, set[0][1], a_bytes, g1);
+    if (route == KMB_DECODE_ROUTE_PROJ4)
+      return f8 ? run(decode_proj_kernel<4, true>, set[1][2], a_bytes, g1) : run(decode_proj_kernel<4, false>, set[0][2], a_bytes, g1);
+    return f8 ? run(decode_proj_kernel<6, true>, set[1][3], a_bytes, g1) : run(decode_proj_kernel<6, false>, set[0][3], a_bytes, g1);
   }
   const size_t lds = attn_lds(p), lds_kv = attn_lds_kv(p);
-  static size_t set_s = 0, set_c = 0, set_l = 0;
-  if (route == KMB_DECODE_ROUTE_ATTN_SELF) {
-    if (lds > set_s) { e = set_lds(decode_attn_kernel<true, false>, lds); if (e != hipSuccess) return e; set_s = lds; }
-    hipLaunchKernelGGL((decode_attn_kernel<true, false>), dim3(unit_grid(p.H, tiles)), dim3(256), lds, stream, p);
-  } else if (route == KMB_DECODE_ROUTE_ATTN_CROSS_KVLDS) {
-    if (lds_kv > set_l) { e = set_lds(decode_attn_kernel<false, true>, lds_kv); if (e != hipSuccess) return e; set_l = lds_kv; }
-    hipLaunchKernelGGL((decode_attn_kernel<false, true>), dim3(unit_grid(p.H, tiles)), dim3(256), lds_kv, stream, p);
-  } else {
-    if (lds > set_c) { e = set_lds(decode_attn_kernel<false, false>, lds); if (e != hipSuccess) return e; set_c = lds; }
-    hipLaunchKernelGGL((decode_attn_kernel<false, false>), dim3(unit_grid(p.H, tiles)), dim3(256), lds, stream, p);
-  }
-  return hipGetLastError();
+  const int ga = unit_grid(p.H, tiles);
+  static size_t set_a[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  if (route == KMB_DECODE_ROUTE_ATTN_SELF)
+    return f8 ? run(decode_attn_kernel<true, false, true>, set_a[1][0], lds, ga) : run(decode_attn_kernel<true, false, false>, set_a[0][0], lds, ga);
+  if (route == KMB_DECODE_ROUTE_ATTN_CROSS_KVLDS)
+    return f8 ? run(decode_attn_kernel<false, true, true>, set_a[1][1], lds_kv, ga)
+              : run(decode_attn_kernel<false, true, false>, set_a[0][1], lds_kv, ga);
+  return f8 ? run(decode_attn_kernel<false, false, true>, set_a[1][2], lds, ga) : run(decode_attn_kernel<false, false, false>, set_a[0][2], lds, ga);
 }
 
 // packed[i] <- fragment-order copy of W[i] ([N, K] row-major with row stride ld; N % 16 == 0, K % 64 == 0), all in ONE
@@ -857,5 +1007,28 @@ hipError_t kmb_decode_pack_launch(const bf16_t* const* W, const int* ld, const i
   int grid = (int)((total + 255) / 256);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+// codes[i], exps[i] <- the FP8 form of W[i] (above pack_weights_fp8_kernel), all in ONE launch (n <= 48 matrices): codes in
+// fragment order (N * K bytes), exps the [N] row exponents
+hipError_t kmb_decode_pack_fp8_launch(const bf16_t* const* W, const int* ld, const int* N, const int* K, uint8_t* const* codes,
+                                      int8_t* const* exps, int n, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (n > PACK_MAX) return hipErrorInvalidValue;
+  PackFp8Args a;
+  memset(&a, 0, sizeof(a));
+  long long tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    if (N[i] <= 0 || K[i] <= 0 || (N[i] & 15) || (K[i] & 63) || (ld[i] & 7) || ld[i] < K[i] || ((uintptr_t)W[i] & 15) ||
+        ((uintptr_t)codes[i] & 15) || !exps[i])
+      return hipErrorInvalidValue;
+    a.m[i] = PackFp8Desc{W[i], codes[i], exps[i], ld[i], N[i], K[i], (int)tiles};
+    tiles += N[i] / 16;
+    if (tiles > 0x7fffffffLL / 16) return hipErrorInvalidValue;
+  }
+  a.n = n;
+  a.tiles = (int)tiles;
+  hipLaunchKernelGGL(pack_weights_fp8_kernel, dim3((int)tiles), dim3(256), 0, stream, a);
   return hipGetLastError();
 }

@@ -50,8 +50,17 @@ size_t layout_gen(const kmb_handle* h, char* base, size_t cap, int B, int S, int
   if (gen_fused_eligible(h)) {
     const size_t dd = (size_t)d * d, fd = (size_t)Fd * d;
     const size_t sizes[6] = {3 * dd, dd, dd, dd, fd, fd};
+    const size_t rows[6] = {3 * (size_t)d, (size_t)d, (size_t)d, (size_t)d, (size_t)Fd, (size_t)d};
+    const bool f8 = h->gen.w_format == KMB_WFMT_FP8_E4M3;   // one byte per element and one exponent per weight row
     for (int l = 0; l < Ld; ++l)
-      for (int i = 0; i < 6; ++i) g.wp.push_back(bp.act(sizes[i]));
+      for (int i = 0; i < 6; ++i) {
+        if (f8) {
+          g.wp.push_back(reinterpret_cast<bf16_t*>(bp.take<uint8_t>(sizes[i])));
+          g.wexp.push_back(bp.take<int8_t>(rows[i]));
+        } else {
+          g.wp.push_back(bp.act(sizes[i]));
+        }
+      }
   }
   g.hist[0] = bp.take<int32_t>(R * Tmax); g.hist[1] = bp.take<int32_t>(R * Tmax);
   g.head_stats = bp.take<float>(kmb_gemm_allrows_stats_floats(h->V));
@@ -67,6 +76,29 @@ int64_t kmb_gen_workspace_bytes(const kmb_handle* h, int B, int S, int num_beams
   return (int64_t)layout_gen(h, nullptr, 0, B, S, num_beams, max_length, n_features, nullptr);
 }
 
+// FP8 decoder weights exist only in the fused decode blocks: why a generation of `rows` rows cannot run on them (NULL: it can).  There
+// is no bf16 fall-back -- it would return other tokens.
+static const char* fp8_refusal(const kmb_handle* h, long long rows) {
+  if (!gen_fused_eligible(h))
+    return "the fused decode blocks do not take this configuration (d_model 768, 64-wide heads, decoder FFN 768 .. 3072 in steps of 768)";
+  if (h->fp32) return "the fp32 validation mode has no generation and no reduced-precision weights";
+  const char* fused_env = getenv("KMB_GEN_FUSED");
+  if (fused_env && fused_env[0] == '0') return "KMB_GEN_FUSED=0 selects the launch-per-operation path, which reads bf16 weights";
+  if (rows > 1024) return "more than 1024 rows (batch x beams) take the GEMM path, which reads bf16 weights";
+  return nullptr;
+}
+
+int kmb_gen_set_weight_format(kmb_handle* h, int format) {
+  if (!h) return fail("kmb_gen_set_weight_format: null handle");
+  if (format != KMB_WFMT_BF16 && format != KMB_WFMT_FP8_E4M3)
+    return fail("kmb_gen_set_weight_format: unknown weight format %d (0 = bf16, 1 = FP8 e4m3)", format);
+  if (format == KMB_WFMT_FP8_E4M3 && !gen_fused_eligible(h))
+    return fail("kmb_gen_set_weight_format: FP8 decoder weights need the fused decode blocks: %s", fp8_refusal(h, 0));
+  h->gen.w_format = format;
+  h->gen.active = false;   // the active generation's copies are in the other format and the workspace is sized anew
+  return 0;
+}
+
 int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_length, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   KCHK(check_bound(h));
@@ -75,6 +107,13 @@ int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_
   if (max_length > h->cfg.max_position_embeddings) return fail("kmb_gen_begin: max_length exceeds max_position_embeddings");
   const kmb_batch& bt = *batch;
   const int d = h->d, B = bt.B, S = bt.S, Me = B * S;
+  const bool f8 = h->gen.w_format == KMB_WFMT_FP8_E4M3;
+  if (f8) {   // before anything is queued
+    if (const char* why = fp8_refusal(h, (long long)B * num_beams)) {
+      h->gen.active = false;
+      return fail("kmb_gen_begin: FP8 decoder weights: %s", why);
+    }
+  }
   GenLayout g;
   const size_t need = layout_gen(h, h->ws, h->ws_bytes, B, S, num_beams, max_length, bt.n_features, &g);
   if (need > h->ws_bytes) return fail("kmb_gen_begin: workspace too small (%zu > %zu bytes)", need, h->ws_bytes);
@@ -99,7 +138,7 @@ int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_
   }
   // (skipped when the copies of the last kmb_gen_begin are still there: same place in the workspace, the bf16 mirror unchanged since,
   //  no training forward in between -- that one re-uses the workspace and clears packed_at)
-  if (!G.L.wp.empty() && !(G.packed_at == G.L.wp[0] && G.packed_version == h->mirror_version)) {   // fragment-order copies of the decoder weights for the fused decode blocks, one launch per 48
+  if (!G.L.wp.empty() && !(G.packed_at == G.L.wp[0] && G.packed_version == h->mirror_version && G.packed_format == G.w_format)) {   // fragment-order copies of the decoder weights for the fused decode blocks, one launch per 48
     std::vector<const bf16_t*> src; std::vector<bf16_t*> dst; std::vector<int> ld, nn, kk;
     for (int l = 0; l < Ld; ++l) {
       const LayerP& L = h->dec[l];
@@ -111,9 +150,13 @@ int kmb_gen_begin(kmb_handle* h, const kmb_batch* batch, int num_beams, int max_
     }
     for (size_t i0 = 0; i0 < src.size(); i0 += 48) {
       const int n = (int)std::min<size_t>(48, src.size() - i0);
-      HIPCHK(kmb_decode_pack_launch(src.data() + i0, ld.data() + i0, nn.data() + i0, kk.data() + i0, dst.data() + i0, n, s));
+      if (f8)   // (the same slots hold codes, and the exponents go beside them)
+        HIPCHK(kmb_decode_pack_fp8_launch(src.data() + i0, ld.data() + i0, nn.data() + i0, kk.data() + i0,
+                                          reinterpret_cast<uint8_t* const*>(dst.data() + i0), G.L.wexp.data() + i0, n, s));
+      else
+        HIPCHK(kmb_decode_pack_launch(src.data() + i0, ld.data() + i0, nn.data() + i0, kk.data() + i0, dst.data() + i0, n, s));
     }
-    G.packed_at = G.L.wp[0]; G.packed_version = h->mirror_version;
+    G.packed_at = G.L.wp[0]; G.packed_version = h->mirror_version; G.packed_format = G.w_format;
   }
   // beam row -> batch item, written on the device: a host table needed a copy and a stream synchronisation here, and the
   // host then sat out the encoder (1.1 ms at batch 64) instead of queueing the first decode steps behind it
@@ -184,10 +227,18 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
   // the blocks work on 16-row tiles that each stream the layer's weights through L2: their time grows with the rows, while
   // the 128-row GEMM tiles of the launch-per-operation path amortise the weights (even at 1280 rows, faster below)
   const bool fused = !(fused_env && fused_env[0] == '0') && !G.L.wp.empty() && R <= 1024;
+  const bool f8 = G.w_format == KMB_WFMT_FP8_E4M3;
+  if (f8 && !fused) {   // (kmb_gen_begin has checked; the environment may have changed since)
+    const char* why = fp8_refusal(h, R);
+    return fail("kmb_gen_step: FP8 decoder weights: %s", why ? why : "the fused decode blocks are not available");
+  }
   if (fused) {
     const bf16_t* zin = G.L.x0;                       // layer input: normalised rows (layer 0) or pre-LayerNorm sums
     const float *lg = nullptr, *lb = nullptr;       // ... and the LayerNorm that turns them into the layer input
-    auto block = [&](const KmbDecodeBlock& b) -> int {
+    // wi: the block's weight among the layer's six packed copies (FP8: its row exponents go with it)
+    auto block = [&](KmbDecodeBlock& b, size_t wi) -> int {
+      b.W = G.L.wp[wi];
+      if (f8) { b.w_format = KMB_WFMT_FP8_E4M3; b.w_exp = G.L.wexp[wi]; }
       const char* why = kmb_decode_block_check(b);
       if (why) return fail("kmb_gen_step: %s", why);
       HIPCHK(kmb_decode_block_launch(b, s));
@@ -198,33 +249,33 @@ int kmb_gen_step(kmb_handle* h, const int64_t* tokens, int step, float* logits_o
       KmbDecodeBlock b;
       memset(&b, 0, sizeof(b));
       b.kind = 1; b.in = zin; b.ld_in = d; b.gamma = lg; b.beta = lb; b.eps = eps; b.ln_out = lg ? G.L.x1 : nullptr;
-      b.W = G.L.wp[(size_t)l * 6 + 0]; b.bias = h->pf(L.sa.qkv_b); b.R = R; b.K = d; b.N = 3 * d; b.out = G.L.o; b.ld_out = d;
+      b.bias = h->pf(L.sa.qkv_b); b.R = R; b.K = d; b.N = 3 * d; b.out = G.L.o; b.ld_out = d;
       b.H = h->Hd; b.q_scale = 0.125f; b.Kc = G.L.kc[l]; b.Vc = G.L.vc[l]; b.Tmax = G.Tmax; b.ldc = d; b.Tk = step + 1;
       b.hist = G.L.hist[G.hcur];
-      KCHK(block(b));
+      KCHK(block(b, (size_t)l * 6 + 0));
       const bf16_t* xres = lg ? G.L.x1 : zin;
       memset(&b, 0, sizeof(b));
-      b.kind = 0; b.in = G.L.o; b.ld_in = d; b.W = G.L.wp[(size_t)l * 6 + 1]; b.bias = h->pf(L.sa.o_b); b.R = R; b.K = d; b.N = d;
+      b.kind = 0; b.in = G.L.o; b.ld_in = d; b.bias = h->pf(L.sa.o_b); b.R = R; b.K = d; b.N = d;
       b.residual = xres; b.ld_res = d; b.out = G.L.z; b.ld_out = d;
-      KCHK(block(b));
+      KCHK(block(b, (size_t)l * 6 + 1));
       memset(&b, 0, sizeof(b));
       b.kind = 2; b.in = G.L.z; b.ld_in = d; b.gamma = h->pf(L.sa.ln_g); b.beta = h->pf(L.sa.ln_b); b.eps = eps; b.ln_out = G.L.y;
-      b.W = G.L.wp[(size_t)l * 6 + 2]; b.bias = h->pf(L.ca.qkv_b); b.R = R; b.K = d; b.N = d; b.out = G.L.o; b.ld_out = d;
+      b.bias = h->pf(L.ca.qkv_b); b.R = R; b.K = d; b.N = d; b.out = G.L.o; b.ld_out = d;
       b.H = h->Hd; b.q_scale = 0.125f; b.Kc = G.L.ckv[l]; b.Vc = G.L.ckv[l] + d; b.Tmax = G.S; b.ldc = h->cfg.decoder_layers * 2 * d; b.Tk = G.S;
       b.kv_row = G.kv_row; b.key_mask = G.bt.attention_mask; b.mask_ld = G.S; b.kv_group = G.nb;   // kv_row[i] = i / nb
-      KCHK(block(b));
+      KCHK(block(b, (size_t)l * 6 + 2));
       memset(&b, 0, sizeof(b));
-      b.kind = 0; b.in = G.L.o; b.ld_in = d; b.W = G.L.wp[(size_t)l * 6 + 3]; b.bias = h->pf(L.ca.o_b); b.R = R; b.K = d; b.N = d;
+      b.kind = 0; b.in = G.L.o; b.ld_in = d; b.bias = h->pf(L.ca.o_b); b.R = R; b.K = d; b.N = d;
       b.residual = G.L.y; b.ld_res = d; b.out = G.L.z; b.ld_out = d;
-      KCHK(block(b));
+      KCHK(block(b, (size_t)l * 6 + 3));
       memset(&b, 0, sizeof(b));
       b.kind = 0; b.in = G.L.z; b.ld_in = d; b.gamma = h->pf(L.ca.ln_g); b.beta = h->pf(L.ca.ln_b); b.eps = eps; b.ln_out = G.L.y;
-      b.W = G.L.wp[(size_t)l * 6 + 4]; b.bias = h->pf(L.fc1_b); b.R = R; b.K = d; b.N = F; b.act = 1; b.out = G.L.hh; b.ld_out = F;
-      KCHK(block(b));
+      b.bias = h->pf(L.fc1_b); b.R = R; b.K = d; b.N = F; b.act = 1; b.out = G.L.hh; b.ld_out = F;
+      KCHK(block(b, (size_t)l * 6 + 4));
       memset(&b, 0, sizeof(b));
-      b.kind = 0; b.in = G.L.hh; b.ld_in = F; b.W = G.L.wp[(size_t)l * 6 + 5]; b.bias = h->pf(L.fc2_b); b.R = R; b.K = F; b.N = d;
+      b.kind = 0; b.in = G.L.hh; b.ld_in = F; b.bias = h->pf(L.fc2_b); b.R = R; b.K = F; b.N = d;
       b.residual = G.L.y; b.ld_res = d; b.out = G.L.z; b.ld_out = d;
-      KCHK(block(b));
+      KCHK(block(b, (size_t)l * 6 + 5));
       zin = G.L.z; lg = h->pf(L.ln_g); lb = h->pf(L.ln_b);
     }
     G.last_x = nullptr; G.last_z = G.L.z; G.last_g = lg; G.last_b = lb;

@@ -150,6 +150,7 @@ struct GenLayout {
   float *mean = nullptr, *rstd = nullptr;
   float* slab = nullptr;   // split-K partial sums of the residual projections of a decode step
   std::vector<bf16_t*> wp;   // per layer: self q|k|v, self out, cross q, cross out, fc1, fc2 in fragment order (decode.hip); empty: not eligible
+  std::vector<int8_t*> wexp; // the weight format FP8 e4m3 (kmb_gen_set_weight_format): wp[i] holds codes (half the bytes), wexp[i] the row exponents; else empty
   // History index of the self-attention caches (round 5): position t of beam row r lives in cache row hist[r][t].  A beam reorder
   // (mixins.py:419-434 _reorder_cache) permutes these [R, Tmax] int rows into the other copy instead of gathering every layer's
   // K and V cache ([R, t, d] x 12 buffers: 5-40 us per decode step at batch 64 x 5 beams); the caches are never copied.
@@ -225,6 +226,9 @@ struct kmb_handle {
     // kmb_gen_step(tokens = NULL) of exactly that step uses them instead of embedding.  -1: nothing pending
     int x0_step = -1;
     uint64_t packed_version = 0; const bf16_t* packed_at = nullptr;   // the fragment-order copies at L.wp[0] were made from mirror version ...
+    int packed_format = 0;                 // ... in this weight format
+    int w_format = 0;                      // KMB_WFMT_* (kmb_gen_set_weight_format, which ends the active generation): the format
+                                           // kmb_gen_workspace_bytes sizes for, kmb_gen_begin packs in and kmb_gen_step hands to the blocks
   } gen;
 
   // ---- dropout sites.  ONE derivation for every site: the 16-bit threshold (rounded, capped), the seed drawn from the handle's seed and the

@@ -57,6 +57,10 @@ int kmb_decode_block_route(const KmbDecodeBlock& p);
 // (N % 16 == 0, K % 64 == 0), n <= 48 matrices in one launch
 hipError_t kmb_decode_pack_launch(const bf16_t* const* W, const int* ld, const int* N, const int* K, bf16_t* const* packed, int n,
                                   hipStream_t stream);
+// the FP8 (e4m3) form of the same weights (KmbDecodeBlock.w_format == 1): codes[i] in fragment order (N * K bytes), exps[i] the [N]
+// row exponents; one launch for n <= 48 matrices
+hipError_t kmb_decode_pack_fp8_launch(const bf16_t* const* W, const int* ld, const int* N, const int* K, uint8_t* const* codes,
+                                      int8_t* const* exps, int n, hipStream_t stream);
 
 // ---------------------------------------------------------------- norm.hip
 

@@ -83,7 +83,12 @@ class KmbDecodeBlock(C.Structure):
     _fields_ = [("kind", i32), ("in_", c_p), ("ld_in", i32), ("gamma", c_p), ("beta", c_p), ("eps", f32), ("ln_out", c_p),
                 ("W", c_p), ("bias", c_p), ("R", i32), ("K", i32), ("N", i32), ("act", i32), ("residual", c_p),
                 ("ld_res", i32), ("out", c_p), ("ld_out", i32), ("H", i32), ("q_scale", f32), ("Kc", c_p), ("Vc", c_p),
-                ("Tmax", i32), ("ldc", i32), ("Tk", i32), ("kv_row", c_p), ("key_mask", c_p), ("mask_ld", i32), ("hist", c_p), ("kv_group", i32)]
+                ("Tmax", i32), ("ldc", i32), ("Tk", i32), ("kv_row", c_p), ("key_mask", c_p), ("mask_ld", i32), ("hist", c_p), ("kv_group", i32),
+                ("w_format", i32), ("w_exp", c_p)]   # appended: a zeroed record is a bf16 block
+
+
+# KmbDecodeBlock.w_format / kmb_gen_set_weight_format (include/kmbart.h KMB_WFMT_*)
+WEIGHT_FORMATS = {"bf16": 0, "fp8_e4m3": 1}
 
 
 # kmb_debug_decode_route: the kernel a decode block runs (include/kmbart.h KMB_DECODE_ROUTE_*)
@@ -216,6 +221,7 @@ PROTOTYPES = {
     "kmb_gen_beam_sample_step": (C.c_int, [c_p, c_p, C.c_int, C.c_int, c_p, f32, C.c_int, f32, C.c_int, c_p, C.c_int, C.c_int, c_p,
                                            C.c_int, c_p, c_p, c_p, c_p, C.c_int64, C.c_int, c_p]),
     "kmb_gen_workspace_bytes": (i64, [c_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kmb_gen_set_weight_format": (C.c_int, [c_p, C.c_int]),
     "kmb_gemm_shared_device": (C.c_int, [C.c_int]),
     "kmb_debug_gemm_route": (C.c_int, [C.POINTER(KmbGemm), C.c_int, c_p, C.c_int32]),
     "kmb_debug_decode_route": (C.c_int, [C.POINTER(KmbDecodeBlock)]),
@@ -253,6 +259,8 @@ PROTOTYPES = {
     "kmb_op_attn_decode": (C.c_int, [C.POINTER(KmbAttnDecode), c_p]),
     "kmb_op_decode_block": (C.c_int, [C.POINTER(KmbDecodeBlock), c_p]),
     "kmb_op_decode_pack": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, c_p]),
+    "kmb_op_decode_pack_fp8": (C.c_int, [c_p, C.c_int, C.c_int, C.c_int, c_p, c_p, c_p]),
+    "kmb_abi_sizeof_decode_block": (C.c_int, []),
     "kmb_op_ln_fwd": (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, C.c_int, C.c_int, f32, c_p]),
     "kmb_op_ln_bwd_scratch": (i64, [C.c_int, C.c_int]),
     "kmb_op_ln_bwd": (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.POINTER(KmbDrop), C.POINTER(KmbDrop), c_p, c_p,

@@ -159,6 +159,7 @@ class Engine:
         self.fwd_serial = 0      # bumped by every call that rewrites the workspace (LazyLogits validity)
         self.gen_logits_bytes = 4   # bytes per element of the decode step's logits buffer
         self.fp32_mode = False
+        self.gen_weight_format = "bf16"
 
     def __del__(self):
         try:
@@ -818,6 +819,18 @@ class Engine:
         return out
 
     # ---- generation -------------------------------------------------------------------------
+    def set_gen_weight_format(self, name):
+        """The format of the six per-layer decoder matrices the fused decode blocks read: "bf16" (default) or "fp8_e4m3" (OCP e4m3
+        codes with a power-of-two scale per weight row: half the weight bytes of a decode step).  Read by gen_begin and the decode
+        steps only.  FP8 exists only where the fused blocks run; anything else raises, here or in gen_begin (kmb_gen_set_weight_format)."""
+        if name not in _lib.WEIGHT_FORMATS:
+            raise ValueError("decoder weight format must be one of %s, got %r" % (sorted(_lib.WEIGHT_FORMATS), name))
+        if name == self.gen_weight_format:
+            return
+        torch.cuda.synchronize(self.device)   # the packed copies of a generation still in flight are about to be resized
+        check(self.lib.kmb_gen_set_weight_format(self.h, _lib.WEIGHT_FORMATS[name]))
+        self.gen_weight_format = name
+
     def gen_begin(self, input_ids, image_features, attention_mask, num_beams, max_length):
         with torch.cuda.device(self.device):
             b, keep, (B, S, _, ntot) = self._batch(input_ids, image_features, attention_mask, None, None, None)

@@ -511,6 +511,32 @@ class MultiModalBartForConditionalGeneration(nn.Module):
         self._post_backward = None  # set by the data-parallel wrapper
         self._dec_hidden_for_logits = None
         self._label_smoothing = _check_label_smoothing(getattr(config, "label_smoothing", 0.0))
+        self._decoder_weight_format = "bf16"
+
+    @property
+    def decoder_weight_format(self):
+        """"bf16" (default) or "fp8_e4m3": see set_decoder_weight_format."""
+        return self._decoder_weight_format
+
+    def set_decoder_weight_format(self, name):
+        """Opt-in reduced-precision inference: "fp8_e4m3" stores the six per-layer decoder matrices the fused decode blocks read (the
+        self-attention's q | k | v and output projection, the cross-attention's q and output projection, fc1, fc2) as OCP FP8 e4m3
+        codes with a power-of-two scale per weight row -- half the weight bytes of a decode step; "bf16" (the default) leaves every
+        launch, buffer and bit as it was.  The FP8 copy is made from the bf16 weights at the start of a generation and again after
+        every change of them.  It covers everything that starts a generation on the engine: every generate() route (greedy, beam
+        search, sampling, beam sampling, with or without score processors, device or host loop) and the cached forward
+        (forward(use_cache=True) / decoder_cached_states).  forward(labels=...), score() and training never see it, nor do
+        activations, caches, biases, LayerNorms or the vocabulary projection.  FP8 exists only where the fused blocks run: d_model
+        768 with 64-wide heads and a decoder FFN of 768 .. 3072, at most 1024 rows (batch x beams), not under KMB_GEN_FUSED=0 and not
+        in the fp32 validation mode -- anything else raises, nothing falls back to bf16 weights.  Callable before or after
+        .to(device); a setting of this object, not part of the state dict."""
+        from kmbart import _lib
+        if name not in _lib.WEIGHT_FORMATS:
+            raise ValueError("decoder weight format must be one of %s, got %r" % (sorted(_lib.WEIGHT_FORMATS), name))
+        if self._engine is not None:
+            self._engine.set_gen_weight_format(name)
+        self._decoder_weight_format = name
+        return self
 
     @property
     def label_smoothing(self):
@@ -586,6 +612,8 @@ class MultiModalBartForConditionalGeneration(nn.Module):
             return self
         eng = Engine(self.config, device, with_heads=self._with_heads)
         eng.set_label_smoothing(self._label_smoothing)
+        if self._decoder_weight_format != "bf16":
+            eng.set_gen_weight_format(self._decoder_weight_format)
         with torch.no_grad():
             for n in self._names:
                 eng.view(eng.params, n).copy_(self._p[n].detach().to(device))

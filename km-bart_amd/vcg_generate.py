@@ -32,6 +32,7 @@ def main(args):
     logger = Logger(args.log_dir)
     model = MultiModalBartForConditionalGeneration.from_pretrained(args.checkpoint)
     model.to(device)
+    model.set_decoder_weight_format(args.decoder_weights)
     if args.device_processors:
         model._device_processors = True
     if args.device_beam_processors:
@@ -85,6 +86,9 @@ def parse_args(argv=None):
     p.add_argument("--device_beam_processors", action="store_true",
                    help="with --num_beams > 1 (no --do_sample): apply them on the device inside the pipelined beam loop "
                         "(model._device_beam_processors) instead of taking the host beam loop")
+    p.add_argument("--decoder_weights", default="bf16", choices=("bf16", "fp8_e4m3"),
+                   help="format of the decoder matrices the fused decode blocks read (model.set_decoder_weight_format): fp8_e4m3 "
+                        "halves their bytes; refused where the fused blocks do not run")
     p.add_argument("--gpu_num", default=1, type=int)
     p.add_argument("--cpu", action="store_true")
     p.add_argument("--amp", action="store_true")
