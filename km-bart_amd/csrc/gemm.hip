@@ -1976,7 +1976,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_narrow(const KmbGemm p) {
     }
     if (p.out_f32 != nullptr) {
       float* o = p.out_f32 + (size_t)grow * p.ld_out_f32 + gcol;
-      for (int e = 0; e < nvalid; ++e) o[e] = v[e] + (p.beta != 0.f ? p.beta * o[e] : 0.f);
+      for (int e = 0; e < nvalid; ++e) o[e] = p.beta != 0.f ? v[e] + p.beta * o[e] : v[e];   // (not v + 0.f: GeLU's -0.0 of a far negative input keeps its sign, as under variant 7)
     }
   }
 }

@@ -1,6 +1,7 @@
 """GPU: every HIP kernel, called through the C-ABI, against a plain PyTorch fp32 computation of the same
 op on the same (bf16-rounded) inputs.  Tolerances: fp32 outputs differ from the reference only by
-accumulation order (<= 1e-4 relative); bf16 outputs carry one bf16 rounding (2^-9 = 2e-3)."""
+accumulation order (<= 1e-4 relative); bf16 outputs carry one bf16 rounding (2^-9 = 2e-3).
+The GEMM epilogues are pinned element by element to float64, per launch variant, in test_gemm_epilogue_gpu.py (gemm_epi_ref.py, test_gemm_epilogue_cpu.py)."""
 import ctypes as C
 import math
 
